@@ -75,3 +75,64 @@ def test_profile_summaries_are_matched_per_part():
     assert bench._matches({"source_hash_gibbs": hg, "source_hash_kmc": "0" * 16, "source_hash": "0" * 16}, "gibbs")
     assert not bench._matches({"source_hash_gibbs": hg, "source_hash_kmc": "0" * 16, "source_hash": hall}, "kmc")
     assert bench._matches({"source_hash": hall}, "kmc") and not bench._matches({"source_hash": "0" * 16}, "gibbs")
+
+
+def test_prepared_batch_is_the_generated_one(tmp_path, monkeypatch):
+    """build() stores the default command's input batch (bench.prepare); a run memory-maps it instead of generating it — the same arrays"""
+    import bench
+    from bayestyper_amd import synth
+
+    monkeypatch.setattr(bench, "CACHE_DIR", str(tmp_path / "cache"))
+    first = bench.prepare(["--groups", "200", "--samples", "2"])
+    assert first and bench.prepare(["--groups", "300", "--samples", "2"]) != first
+    assert os.listdir(bench.CACHE_DIR) == [os.path.basename(bench._mixture_dir(300, 2, 1000, None))], "a new batch replaces the stored one"
+    flat = bench.rank_batch(300, 2, 0, 1, "weak")[0]
+    want = synth.make_mixture(300, 2, seed=1000)
+    assert isinstance(flat["kmer_counts"], np.memmap), "read from the store"
+    assert sorted(flat) == sorted(want)
+    for k, v in want.items():
+        assert np.array_equal(flat[k], v) if isinstance(v, np.ndarray) else flat[k] == v, k
+    other = bench.rank_batch(300, 2, 1, 2, "weak")[0]   # (rank 1's block is not stored: generated)
+    assert not isinstance(other["kmer_counts"], np.memmap)
+
+
+def test_dump_outputs_sample_the_last_step(tmp_path, monkeypatch):
+    """--dump-outputs: float .npy files within the size budget; the Gibbs files hold exactly the sampled clusters' rows of the results"""
+    import bench
+
+    rng = np.random.default_rng(5)
+    C, S = 500, 3
+    nd, nc = rng.integers(1, 30, C), rng.integers(1, 12, C)
+    nD, nC = int(nd.sum()), int(nc.sum())
+    res = {"dip_off": np.concatenate([[0], np.cumsum(nd)]).astype(np.uint64), "h1": rng.integers(0, 9, nD).astype(np.uint16),
+           "h2": rng.integers(0, 9, nD).astype(np.uint16), "freq": rng.integers(0, 5000, (nD, S)).astype(np.uint32),
+           "cell_off": np.concatenate([[0], np.cumsum(nc)]).astype(np.uint64), "stats": rng.random((nC, 3, 4))}
+
+    keys = rng.integers(0, 2 ** 63, (1000, 2), dtype=np.uint64)
+    keys[:500, 1] = 7   # (ties on the high word)
+    kcounts = rng.integers(0, 256, (1000, S)).astype(np.uint8)
+
+    class Table:   # the export comes in slot order: any order
+        def __init__(self, seed):
+            self.perm = np.random.default_rng(seed).permutation(len(keys))
+
+        def export(self):
+            return keys[self.perm], kcounts[self.perm], np.zeros((len(keys), 4), np.uint8)
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    for seed in (0, 1):
+        bench.dump_outputs(str(tmp_path / str(seed)), res, Table(seed), S)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, "0", f)) for f in os.listdir(tmp_path / "0")}
+    assert all(np.array_equal(v, np.load(os.path.join(tmp_path, "1", k + ".npy"))) for k, v in got.items()), "the slot order does not matter"
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, "0", f)) for f in os.listdir(tmp_path / "0")) <= 200_000
+    by_kmer = np.lexsort((keys[:, 0], keys[:, 1]))
+    assert got["kmc_num_keys"][0] == 1000
+    assert np.array_equal(got["kmc_kmers"], keys[by_kmer].view(np.uint32)) and np.array_equal(got["kmc_counts"], kcounts[by_kmer])
+    ids = got["gibbs_cluster_ids"].astype(np.int64)
+    assert 0 < len(ids) < C and np.all(np.diff(ids) > 0)
+    d0, c0 = res["dip_off"].astype(np.int64), res["cell_off"].astype(np.int64)
+    dip = np.concatenate([np.column_stack([res["h1"], res["h2"], res["freq"]])[d0[i]:d0[i + 1]] for i in ids])
+    assert np.array_equal(got["gibbs_diplotypes"], dip) and np.array_equal(got["gibbs_num_diplotypes"], nd[ids])
+    assert np.array_equal(got["gibbs_kmer_stats"], np.concatenate([res["stats"][c0[i]:c0[i + 1]] for i in ids]))
+    assert np.array_equal(got["gibbs_num_cells"], nc[ids])
