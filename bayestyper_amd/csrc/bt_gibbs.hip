@@ -2096,6 +2096,25 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
             fprintf(stderr, "bt_gibbs: %u tiles in %zu launch classes:", ntiles, g->classes.size());
             for (auto &c : g->classes) fprintf(stderr, " [%zu tiles, lds %u B, split %u%s%s]", c.tiles.size(), c.lds, c.split, c.simple ? ", simple" : "", c.single ? ", single" : (c.hot ? ", hot" : ""));
             fprintf(stderr, "; tile 0: hot_bytes %u lds_stride %u copies %u\n", g->tiles[0].hot_bytes, g->tiles[0].lds_stride, g->tiles[0].copies);
+            // per class, its distinct tile set-ups (tests/test_gibbs_edges_gpu.py reads these): the kernel of its sampling operations, the table of
+            // unique-k-mer sums (tagged: the direct-mapped cache; whole: a dense table rebuilt whole when cleared; invalidated: one invalidated block-wise by the
+            // tile; wide: ... by the whole GPU between noise iterations), the teams of copies and the length of the per-sample cache (0: off)
+            for (size_t i = 0; i < g->classes.size(); ++i) {
+                const auto &c = g->classes[i];
+                std::map<std::string, uint32_t> setups;
+                for (uint32_t ti : c.tiles) {
+                    const TileDesc &d = g->tiles[ti];
+                    const bool inval = d.cache_mode == 0 && d.cache_entries > BT_UC_INVALIDATE_MIN;
+                    const bool wide = inval && !d.simple && d.hoff[A_UCACHE] == NOHOT;
+                    char buf[256];
+                    snprintf(buf, sizeof buf, "Hm=%u nvm=%u NMm=%u lanes=%u cache_mode=%u entries=%u table=%s teams=%u copies=%u scache_n=%u", d.Hm, d.nvm, d.NMm, d.num_lanes,
+                             d.cache_mode, d.cache_entries, d.cache_mode ? "tagged" : (wide ? "wide" : (inval ? "invalidated" : "whole")), d.teams, d.copies, d.scache_n);
+                    setups[buf] += 1;
+                }
+                fprintf(stderr, "bt_gibbs: class %zu kernel=%s:", i, c.simple ? "simple" : (c.single ? "single" : (c.hot ? "hot" : "generic")));
+                for (auto &s : setups) fprintf(stderr, " [%s tiles=%u]", s.first.c_str(), s.second);
+                fprintf(stderr, "\n");
+            }
         }
     }
     BT_TRYHIP(hipStreamSynchronize(ctx->stream));

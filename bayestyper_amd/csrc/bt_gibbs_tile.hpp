@@ -1295,11 +1295,12 @@ __device__ inline bool is_missing(const Vx &c, uint32_t var, uint32_t a) { retur
 
 // r repetitions of KmerStats::addValue(value) on a register copy.  Once an accumulator has converged onto the value
 // (delta == 0 and the non-zero fraction saturated) every further addValue only increments the count, so the remaining
-// repetitions collapse into one exact addition.
+// repetitions collapse into one exact addition.  (delta itself is tested, not m == value: an infinite value — a count over a
+// multiplicity that wrapped to 0 — equals an infinite mean, but its delta is inf - inf = NaN, which the reference carries into the mean.)
 __device__ inline void ks_add_rep(KS &k, double value, uint32_t r) {
     const double nzv = value == 0.0 ? 0.0 : 1.0;
     for (uint32_t i = 0; i < r; ++i) {
-        if (k.m == value && k.f == nzv && k.c > 0.0) {
+        if (value - k.m == 0.0 && k.f == nzv && k.c > 0.0) {
             k.c += (double)(r - i);
             return;
         }

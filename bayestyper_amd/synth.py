@@ -418,6 +418,84 @@ def make_batch(shape, n_groups, S, seed, templates=1):
     return replicate(tmpl, reps, rng)
 
 
+def edge_group(rng, spec, cid=0):
+    """One group of EXACTLY the dimensions of `spec` (a dict; make_edge_batch):
+      V, H                  variants and haplotype candidates of the root cluster (2**V >= H, or candidates repeat)
+      kpa                   k-mers per allele (default 1), flank / ic_kmers: k-mers on every haplotype / allele k-mers with an intercluster copy
+      ic                    the intercluster multiplicities (female, male) of the ic k-mers (default (2, 2))
+      mult                  the haplotype matrix's non-zero entries become this value (a number, one per k-mer row or a (K, H) array), default: as built (1).
+                            Rows: kpa k-mers of allele 0 then of allele 1 for every variant, then the flank k-mers, then the ic k-mers
+      kids                  nested children: a list of dicts with V, H, kpa (and mult); each shares `shared` (default 1) multicluster k-mers with the root
+      shared_mult           (root, child) multiplicity of the shared k-mers on the haplotypes that carry them (default (1, 1))
+      shared_ic             intercluster multiplicities (female, male) of the shared k-mers (default (0, 0))"""
+    def build(s):
+        c = make_cluster(rng, s["V"], s["H"], s.get("kpa", 1), flank_kmers=s.get("flank", 0), ic_kmers=s.get("ic_kmers", 0), has_dependency=s.get("dep", False))
+        if "ic" in s:
+            c.ic[c.ic.any(axis=1)] = np.asarray(s["ic"], np.uint8)
+        if "mult" in s:
+            m = np.asarray(s["mult"], np.int64)
+            m = np.broadcast_to(m if m.ndim == 2 else m.reshape(-1, 1), c.M.shape)
+            c.M = np.where(c.M > 0, m, 0).astype(np.uint8)
+        return c
+
+    root = build(spec)
+    kids = [build(dict(k, dep=True)) for k in spec.get("kids", [])]
+    if not kids:
+        return GroupSpec([root], [cid])
+    cids = [cid + i for i in range(1 + len(kids))]
+    for h in range(root.H):   # haplotypes without variant 0's alternative allele run through the nested regions (group_shape_C)
+        if root.hap_allele[h, 0] == 0:
+            root.hap_nested[h] = sorted(cids[1:])
+    for ch in cids[1:]:
+        root.nestdep[ch] = [0]
+    rm, km = spec.get("shared_mult", (1, 1))
+    sic = spec.get("shared_ic", (0, 0))
+    n_sh = 0
+    for kid, ks in zip(kids, spec["kids"]):
+        n = int(ks.get("shared", 1))
+        ids = np.arange(n_sh, n_sh + n, dtype=np.int32)
+        carriers = root.hap_allele[:, 0] == 0
+        root.add_kmers(np.tile(carriers.astype(np.uint8) * rm, (n, 1)), [[(0, carriers.copy())] for _ in range(n)], ic=sic, shared=ids)
+        kid.add_kmers(np.full((n, kid.H), km, np.uint8), [[] for _ in range(n)], ic=sic, shared=ids)
+        n_sh += n
+    return GroupSpec([root] + kids, cids, edges=[list(range(1, 1 + len(kids)))] + [[] for _ in kids], sources=[0], num_shared=n_sh)
+
+
+def make_edge_batch(specs, S, seed, ploidy=None, gender=None, counts=None):
+    """Groups of exactly the requested dimensions (edge_group: one spec per group), for tests at the boundaries of the tile builder's decisions.
+    ploidy: (G, S) per (group, sample), gender: per sample (flatten).  counts: {(group, cluster of the group, k-mer row): value or per-sample values}
+    overrides the generated counts (the k-mer is then in the count table); the rows of a multicluster k-mer keep one count."""
+    rng = np.random.default_rng(seed)
+    groups, cid = [], 0
+    for spec in specs:
+        g = edge_group(rng, spec, cid)
+        cid += len(g.clusters)
+        groups.append(g)
+    flat = flatten(groups, S, rng, ploidy=ploidy, gender=gender)
+    if counts:
+        cnt = flat["kmer_counts"].reshape(-1, S)
+        koff = flat["kmer_off"].astype(np.int64)
+        goff = flat["group_cluster_off"].astype(np.int64)
+        for (g, ci, k), v in counts.items():
+            c = int(goff[g]) + ci
+            assert k < koff[c + 1] - koff[c], "count override outside its cluster"
+            row = int(koff[c]) + k
+            cnt[row] = np.broadcast_to(np.asarray(v, np.uint8), (S,))
+            flat["kmer_has_counts"][row] = 1
+        sh = flat["kmer_shared"]
+        for g in range(flat["num_groups"]):   # multicluster k-mers are ONE k-mer: the first row of each record sets the others
+            r0, r1 = int(koff[goff[g]]), int(koff[goff[g + 1]])
+            first = {}
+            for r in range(r0, r1):
+                if sh[r] >= 0:
+                    if int(sh[r]) in first:
+                        cnt[r] = cnt[first[int(sh[r])]]
+                    else:
+                        first[int(sh[r])] = r
+        flat["kmer_counts"] = np.ascontiguousarray(cnt.reshape(-1))
+    return flat
+
+
 def make_hetero_batch(shape, n_groups, S, seed):
     """n_groups groups of one shape class, every one with its own dimensions (hetero_group) — built group by group (tests)"""
     rng = np.random.default_rng(seed)
