@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <chrono>
 #include <fcntl.h>
+#include <functional>
 #include <unistd.h>
 #include <cstring>
 #include <numeric>
@@ -1065,6 +1066,109 @@ __global__ __launch_bounds__(BLOCK) void kmc_make_bloom_kernel(KmcView v, BloomV
     }
 }
 
+// getKmerStats (src/bayesTyperTools/scripts/getKmerStats.cpp:87-127): one histogram bin per (count, #A, #C, #G), #T = k - the rest.
+// Bin layout (include/btgpu.h): count * C(k+3,3) + comp_index(a, c, g), the compositions a + c + g <= k in (a, c, g) lexicographic order.
+constexpr uint32_t KSTATS_NONE = 0xFFFFFFFFu;   // no bin: record outside the count range, above 255, or no record
+constexpr unsigned KSTATS_CACHE = 1024;         // per-workgroup LDS table of bins (power of two)
+
+__host__ __device__ inline uint32_t kstats_tri(uint32_t m) { return (m + 1) * (m + 2) / 2; }               // #(c, g) with c + g <= m
+__host__ __device__ inline uint32_t kstats_tet(uint32_t m) { return (m + 1) * (m + 2) * (m + 3) / 6; }     // #(a, c, g) with a + c + g <= m = C(m+3,3)
+__device__ inline uint32_t kstats_comp_index(uint32_t k, uint32_t a, uint32_t c, uint32_t g) {
+    return kstats_tet(k) - kstats_tet(k - a) + kstats_tri(k - a) - kstats_tri(k - a - c) + g;
+}
+
+// #C, #G, #T of a packed k-mer (symbol i = bits 2i, 2i+1; A=0 C=1 G=2 T=3): the low bit of a group is set for C and T, the high bit for G and T.
+// The groups at and above k are masked off, so padding never counts.
+__device__ inline void kstats_composition(Kmer x, uint32_t k, uint32_t &c, uint32_t &g, uint32_t &t) {
+    constexpr uint64_t L = 0x5555555555555555ULL;
+    const uint64_t mlo = k >= 32 ? L : L & ((1ULL << (2u * k)) - 1ULL);
+    const uint64_t mhi = k <= 32 ? 0ULL : (k == 64 ? L : L & ((1ULL << (2u * (k - 32u))) - 1ULL));
+    const uint32_t low = __popcll(x.lo & mlo) + __popcll(x.hi & mhi);                                 // C + T
+    const uint32_t high = __popcll((x.lo >> 1) & mlo) + __popcll((x.hi >> 1) & mhi);                  // G + T
+    t = __popcll(x.lo & (x.lo >> 1) & mlo) + __popcll(x.hi & (x.hi >> 1) & mhi);
+    c = low - t;
+    g = high - t;
+}
+
+// Same staging as kmc_make_bloom_kernel.  Real tables are dominated by count-1 k-mers that share a few hundred compositions, so the adds
+// are combined on chip before any global atomic: (1) the wavefront sorts its 64 bin keys in registers (bitonic network over __shfl_xor,
+// no LDS, no barrier) and only the head lane of each run of equal keys adds, with the run length; (2) that add goes to the workgroup's LDS
+// table when the bin owns a slot there (claimed once by the first key that hashes to an empty slot, for the life of the workgroup), else
+// straight to the histogram.  The table is flushed once at the end.  All adds are exact integer adds: the result does not depend on order.
+__global__ __launch_bounds__(BLOCK) void kmc_kmer_stats_kernel(KmcView v, const uint8_t *__restrict__ records, uint64_t first_record, uint64_t n,
+                                                               unsigned long long *__restrict__ hist, unsigned long long *__restrict__ over255) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[KMC_RECS * KMC_MAX_REC + 32];
+    __shared__ uint64_t block_prefix[2];
+    __shared__ uint32_t cache_key[KSTATS_CACHE];
+    __shared__ unsigned long long cache_cnt[KSTATS_CACHE];
+    for (unsigned j = threadIdx.x; j < KSTATS_CACHE; j += BLOCK) {
+        cache_key[j] = KSTATS_NONE;
+        cache_cnt[j] = 0;
+    }
+    const uint32_t ncomp = kstats_tet(v.k);
+    const unsigned lane = threadIdx.x & 63u;
+    const uint64_t num_chunks = (n + KMC_RECS - 1) / KMC_RECS;
+    for (uint64_t chunk = blockIdx.x; chunk < num_chunks; chunk += gridDim.x) {
+        const uint64_t rec0 = chunk * KMC_RECS;
+        const unsigned nrec = (unsigned)((n - rec0) < KMC_RECS ? (n - rec0) : KMC_RECS);
+        if (threadIdx.x < 2) block_prefix[threadIdx.x] = kmc_prefix_of(v, first_record + rec0 + (threadIdx.x ? nrec - 1 : 0));
+        const uint64_t byte0 = rec0 * v.rec_size;
+        const unsigned nbytes = nrec * v.rec_size;
+        const uint64_t a0 = byte0 & ~15ULL;
+        const unsigned lead = (unsigned)(byte0 - a0);
+        const unsigned nvec = (lead + nbytes + 15u) / 16u;
+        const uint64_t total_bytes = n * (uint64_t)v.rec_size;
+        for (unsigned j = threadIdx.x; j < nvec; j += BLOCK) {
+            const uint64_t off = a0 + (uint64_t)j * 16u;
+            if (off + 16u <= total_bytes) *reinterpret_cast<uint4 *>(&stage[j * 16u]) = *reinterpret_cast<const uint4 *>(records + off);
+            else
+                for (unsigned q = 0; q < 16u; ++q) stage[j * 16u + q] = (off + q < total_bytes) ? records[off + q] : 0;
+        }
+        __syncthreads();
+        uint32_t key = KSTATS_NONE;
+        bool over = false;
+        if (threadIdx.x < nrec) {
+            Kmer a;
+            uint32_t count;
+            kmc_decode(v, kmc_prefix_in(v, first_record + rec0 + threadIdx.x, block_prefix[0], block_prefix[1]), &stage[lead + threadIdx.x * v.rec_size], a, count);
+            if (count >= v.min_count && count <= v.max_count) {
+                if (count > 255u) over = true;   // the reference asserts count <= 255 (getKmerStats.cpp:113): counted, never binned
+                else {
+                    uint32_t c, g, t;
+                    kstats_composition(a, v.k, c, g, t);
+                    key = count * ncomp + kstats_comp_index(v.k, v.k - c - g - t, c, g);
+                }
+            }
+        }
+        __syncthreads();   // the stage is free for the next chunk; everything below is per wavefront
+        const uint64_t over_mask = __ballot(over);
+        if (over_mask && lane == (unsigned)(__ffsll((unsigned long long)over_mask) - 1)) atomicAdd(over255, (unsigned long long)__popcll(over_mask));
+        // bitonic sort of the wavefront's 64 keys, ascending (KSTATS_NONE last)
+        for (unsigned kk = 2; kk <= 64u; kk <<= 1)
+            for (unsigned j = kk >> 1; j > 0; j >>= 1) {
+                const uint32_t other = __shfl_xor(key, (int)j);
+                const bool keep_min = ((lane & j) == 0) == ((lane & kk) == 0);
+                key = keep_min ? min(key, other) : max(key, other);
+            }
+        const uint32_t prev = __shfl_up(key, 1u);
+        const bool head = key != KSTATS_NONE && (lane == 0 || prev != key);
+        const uint64_t heads = __ballot(head);
+        const uint32_t valid = (uint32_t)__popcll(__ballot(key != KSTATS_NONE));
+        if (head) {
+            const uint64_t later = heads & ~((2ULL << lane) - 1ULL);   // heads above this lane (lane 63: none)
+            const unsigned long long run = (later ? (uint32_t)(__ffsll((unsigned long long)later) - 1) : valid) - lane;
+            const uint32_t slot = (key * 2654435761u) >> (32 - 10);   // KSTATS_CACHE = 2^10 slots
+            const uint32_t owner = atomicCAS(&cache_key[slot], KSTATS_NONE, key);
+            if (owner == KSTATS_NONE || owner == key) atomicAdd(&cache_cnt[slot], run);
+            else atomicAdd(&hist[key], run);
+        }
+    }
+    __syncthreads();
+    for (unsigned j = threadIdx.x; j < KSTATS_CACHE; j += BLOCK)
+        if (cache_cnt[j]) atomicAdd(&hist[cache_key[j]], cache_cnt[j]);
+}
+static_assert(KSTATS_CACHE == 1024, "kmc_kmer_stats_kernel hashes into 2^10 slots");
+
 }  // namespace
 
 extern "C" {
@@ -1742,6 +1846,10 @@ static int parallel_pread(int fd, uint8_t *dst, uint64_t offset, size_t bytes) {
     return 0;
 }
 
+// launch(i, d_chunk, first, m): enqueue the work on chunk i (records [first, first + m), 16-byte aligned in device memory) on the context's stream
+using KmcChunkLaunch = std::function<int(uint64_t, const uint8_t *, uint64_t, uint64_t)>;
+static int kmc_stream_chunks(bt_kmc_scan *s, const char *what, const uint8_t *h_records, int fd, uint64_t file_offset, uint64_t first_record, uint64_t n,
+                             uint64_t chunk_records, const KmcChunkLaunch &launch, void (*progress)(uint64_t, void *) = nullptr, void *progress_user = nullptr);
 static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx, const uint8_t *h_records, int fd, uint64_t file_offset, uint64_t first_record,
                            uint64_t n, uint64_t chunk_records, uint64_t *h_hit_count);
 
@@ -1768,12 +1876,34 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
         if (h_hit_count) *h_hit_count = 0;
         return BT_OK;
     }
+    const char *what = fd >= 0 ? "bt_kmc_scan_run_file" : "bt_kmc_scan_run_host";
+    const int rc = kmc_stream_chunks(s, what, h_records, fd, file_offset, first_record, n, chunk_records, [&](uint64_t i, const uint8_t *d, uint64_t first, uint64_t m) {
+        if (i == 0 && hipMemsetAsync(s->d_host_hits, 0, 8, s->ctx->stream) != hipSuccess) return fail(std::string(what) + ": clearing the hit counter failed");
+        return bt_kmc_scan_run(s, path_bloom, table, sample_idx, d, first, m, reinterpret_cast<uint64_t *>(s->d_host_hits));
+    });
+    if (rc != BT_OK) return rc;
+    unsigned long long hits = 0;
+    hipError_t e = hipMemcpyAsync(&hits, s->d_host_hits, 8, hipMemcpyDeviceToHost, s->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+    if (e != hipSuccess) return fail(std::string(what) + ": " + hipGetErrorString(e));
+    int overflowed = 0;
+    if (bt_table_status(table, nullptr, nullptr, &overflowed) != BT_OK) return BT_ERR;
+    if (overflowed) return fail("bt_kmc_scan_run_host: the count table is full, matched k-mers were dropped (bt_table_reserve before the scan)");
+    if (h_hit_count) *h_hit_count = hits;
+    return BT_OK;
+}
+
+// The records [first_record, first_record + n) — from host memory (h_records) or from a file (fd, at file_offset) — through two staging slots: pinned
+// host buffer -> device buffer on a copy stream, launch(...) on the context's stream, events both ways.  Blocking: returns once every launch is done.
+static int kmc_stream_chunks(bt_kmc_scan *s, const char *what, const uint8_t *h_records, int fd, uint64_t file_offset, uint64_t first_record, uint64_t n,
+                             uint64_t chunk_records, const KmcChunkLaunch &launch, void (*progress)(uint64_t, void *), void *progress_user) {
+    if (first_record + n > s->total) return fail(std::string(what) + ": record range exceeds the database");
+    if (n == 0) return BT_OK;
     BT_HIP(hipSetDevice(s->ctx->device));
     const auto t_enter = std::chrono::steady_clock::now();
     const uint64_t rec = s->rec_size;
     chunk_records = std::max<uint64_t>(16, std::min<uint64_t>(chunk_records ? chunk_records : (1ull << 23), n + 15) / 16 * 16);   // chunk starts stay 16-byte aligned
     const size_t chunk_bytes = chunk_records * rec;
-    // two staging slots: pinned host buffer -> device buffer on a copy stream, scan on the context's stream, events both ways
     hipError_t e = hipSuccess;
     if (s->stage_bytes < chunk_bytes) {
         free_host_staging(s);
@@ -1794,7 +1924,7 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_host_hits), 8);
         if (e != hipSuccess) {
             free_host_staging(s);
-            return fail(std::string("bt_kmc_scan_run_host: staging buffers: ") + hipGetErrorString(e));
+            return fail(std::string(what) + ": staging buffers: " + hipGetErrorString(e));
         }
         s->stage_bytes = reuse ? s->ctx->kmc_stage_bytes : chunk_bytes;
         if (reuse) s->ctx->kmc_stage_bytes = 0;
@@ -1802,7 +1932,6 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
     const bool timing = getenv("BT_STAGE_TIMES") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     double read_s = 0, wait_s = 0;
-    e = hipMemsetAsync(s->d_host_hits, 0, 8, s->ctx->stream);
     int rc = BT_OK;
     uint64_t done = 0;
     for (uint64_t i = 0; e == hipSuccess && rc == BT_OK && done < n; ++i) {
@@ -1815,7 +1944,7 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
         wait_s += std::chrono::duration<double>(t_r - t_w).count();
         if (fd >= 0) {
             if (parallel_pread(fd, s->h_pin[b], file_offset + done * rec, m * rec) != 0) {
-                rc = fail("bt_kmc_scan_run_file: reading the records failed");
+                rc = fail(std::string(what) + ": reading the records failed");
                 break;
             }
         } else
@@ -1826,12 +1955,11 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
         if (e == hipSuccess) e = hipEventRecord(s->copied[b], s->copy_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(s->ctx->stream, s->copied[b], 0);
         if (e != hipSuccess) break;
-        rc = bt_kmc_scan_run(s, path_bloom, table, sample_idx, s->d_stage[b], first_record + done, m, reinterpret_cast<uint64_t *>(s->d_host_hits));
+        rc = launch(i, s->d_stage[b], first_record + done, m);
         if (rc == BT_OK) e = hipEventRecord(s->scanned[b], s->ctx->stream);
         done += m;
+        if (rc == BT_OK && e == hipSuccess && progress) progress(done, progress_user);
     }
-    unsigned long long hits = 0;
-    if (e == hipSuccess && rc == BT_OK) e = hipMemcpyAsync(&hits, s->d_host_hits, 8, hipMemcpyDeviceToHost, s->ctx->stream);
     const auto t_loop = std::chrono::steady_clock::now();
     hipError_t e2 = hipStreamSynchronize(s->ctx->stream);
     (void)hipStreamSynchronize(s->copy_stream);
@@ -1841,11 +1969,7 @@ static int kmc_scan_stream(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table
                 std::chrono::duration<double>(t_begin - t_enter).count());
     if (rc != BT_OK) return rc;
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(std::string("bt_kmc_scan_run_host: ") + hipGetErrorString(e));
-    int overflowed = 0;
-    if (bt_table_status(table, nullptr, nullptr, &overflowed) != BT_OK) return BT_ERR;
-    if (overflowed) return fail("bt_kmc_scan_run_host: the count table is full, matched k-mers were dropped (bt_table_reserve before the scan)");
-    if (h_hit_count) *h_hit_count = hits;
+    if (e != hipSuccess) return fail(std::string(what) + ": " + hipGetErrorString(e));
     return BT_OK;
 }
 
@@ -1859,6 +1983,56 @@ int bt_kmc_scan_make_bloom(bt_kmc_scan *s, bt_bloom *sample_bloom, const uint8_t
     unsigned grid = grid_for((n + KMC_RECS - 1) / KMC_RECS, 1, s->ctx->num_cu * 8);
     hipLaunchKernelGGL(kmc_make_bloom_kernel, dim3(grid), dim3(BLOCK), 0, s->ctx->stream, make_kmc_view(s), sample_bloom->view(), d_records, first_record, n);
     BT_CHECK_LAUNCH();
+    return BT_OK;
+}
+
+uint64_t bt_kmer_stats_num_bins(uint32_t k) { return k >= 1 && k <= 64 ? 256ull * kstats_tet(k) : 0; }
+
+static int kmer_stats_launch(bt_kmc_scan *s, const uint8_t *d_records, uint64_t first_record, uint64_t n, uint64_t *d_hist, uint64_t *d_over255) {
+    const unsigned grid = grid_for((n + KMC_RECS - 1) / KMC_RECS, 1, s->ctx->num_cu * 8);
+    hipLaunchKernelGGL(kmc_kmer_stats_kernel, dim3(grid), dim3(BLOCK), 0, s->ctx->stream, make_kmc_view(s), d_records, first_record, n,
+                       reinterpret_cast<unsigned long long *>(d_hist), reinterpret_cast<unsigned long long *>(d_over255));
+    BT_CHECK_LAUNCH();
+    return BT_OK;
+}
+
+int bt_kmc_scan_kmer_stats(bt_kmc_scan *s, const uint8_t *d_records, uint64_t first_record, uint64_t n, uint64_t *d_hist, uint64_t *d_over255) {
+    if (!s || !d_hist || !d_over255) return fail("bt_kmc_scan_kmer_stats: null argument");
+    if (first_record + n > s->total) return fail("bt_kmc_scan_kmer_stats: record range exceeds the database");
+    if ((reinterpret_cast<uintptr_t>(d_records) & 15u) != 0) return fail("bt_kmc_scan_kmer_stats: d_records must be 16-byte aligned");
+    if (n == 0) return BT_OK;
+    BT_HIP(hipSetDevice(s->ctx->device));
+    return kmer_stats_launch(s, d_records, first_record, n, d_hist, d_over255);
+}
+
+int bt_kmc_scan_kmer_stats_file(bt_kmc_scan *s, const char *suf_path, uint64_t payload_offset, uint64_t first_record, uint64_t n, uint64_t chunk_records,
+                                uint64_t *h_hist, uint64_t *h_binned, uint64_t *h_over255, void (*progress)(uint64_t, void *), void *progress_user) {
+    if (!s || !suf_path || !h_hist) return fail("bt_kmc_scan_kmer_stats_file: null argument");
+    if (first_record + n > s->total) return fail("bt_kmc_scan_kmer_stats_file: record range exceeds the database");
+    const uint64_t bins = bt_kmer_stats_num_bins(s->k);
+    BT_HIP(hipSetDevice(s->ctx->device));
+    uint64_t *d_hist = nullptr;   // bins, then the above-255 counter
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_hist), (bins + 1) * 8));
+    hipError_t e = hipMemsetAsync(d_hist, 0, (bins + 1) * 8, s->ctx->stream);
+    int rc = e == hipSuccess ? BT_OK : fail(std::string("bt_kmc_scan_kmer_stats_file: ") + hipGetErrorString(e));
+    const int fd = rc == BT_OK ? ::open(suf_path, O_RDONLY) : -1;
+    if (rc == BT_OK && fd < 0) rc = fail(std::string("bt_kmc_scan_kmer_stats_file: cannot open ") + suf_path);
+    if (rc == BT_OK)
+        rc = kmc_stream_chunks(s, "bt_kmc_scan_kmer_stats_file", nullptr, fd, payload_offset + first_record * s->rec_size, first_record, n, chunk_records,
+                               [&](uint64_t, const uint8_t *d, uint64_t first, uint64_t m) { return kmer_stats_launch(s, d, first, m, d_hist, d_hist + bins); }, progress, progress_user);
+    if (fd >= 0) ::close(fd);
+    uint64_t over = 0;
+    if (rc == BT_OK) {
+        e = hipMemcpyAsync(h_hist, d_hist, bins * 8, hipMemcpyDeviceToHost, s->ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&over, d_hist + bins, 8, hipMemcpyDeviceToHost, s->ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+        if (e != hipSuccess) rc = fail(std::string("bt_kmc_scan_kmer_stats_file: ") + hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(s->ctx->stream);
+    (void)hipFree(d_hist);
+    if (rc != BT_OK) return rc;
+    if (h_binned) *h_binned = std::accumulate(h_hist, h_hist + bins, (uint64_t)0);
+    if (h_over255) *h_over255 = over;
     return BT_OK;
 }
 

@@ -89,6 +89,11 @@ bt_kmc_scan_destroy = _sig("bt_kmc_scan_destroy", [vp])
 bt_kmc_scan_set_count_range = _sig("bt_kmc_scan_set_count_range", [vp, C.c_uint32, C.c_uint64])
 bt_kmc_scan_run = _sig("bt_kmc_scan_run", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, vp])
 bt_kmc_scan_decode = _sig("bt_kmc_scan_decode", [vp, vp, C.c_uint64, C.c_uint64, vp, vp])
+bt_kmer_stats_num_bins = _sig("bt_kmer_stats_num_bins", [C.c_uint32], C.c_uint64)
+bt_kmc_scan_kmer_stats = _sig("bt_kmc_scan_kmer_stats", [vp, vp, C.c_uint64, C.c_uint64, vp, vp])
+KMER_STATS_PROGRESS = C.CFUNCTYPE(None, C.c_uint64, vp)
+bt_kmc_scan_kmer_stats_file = _sig("bt_kmc_scan_kmer_stats_file", [vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, u64p,
+                                                                   KMER_STATS_PROGRESS, vp])
 
 
 
@@ -482,10 +487,41 @@ class KmcScan:
             b.free()
         return kmers, counts
 
+    def kmer_stats(self, d_records_ptr, first_record, n, d_hist_ptr, d_over255_ptr):
+        """getKmerStats on device-resident records: ADDS into a caller-zeroed device histogram (kmer_stats_bins(k) uint64) and the device
+        uint64 above-255 counter (asynchronous)"""
+        check(bt_kmc_scan_kmer_stats(self.h, d_records_ptr, first_record, n, d_hist_ptr, d_over255_ptr))
+
+    def kmer_stats_file(self, suf_path, first_record=0, n=None, chunk_records=0, payload_offset=4, progress=None):
+        """getKmerStats streamed from the .kmc_suf file -> (histogram, records binned, records in range above 255); progress(records_done)
+        is called after each chunk"""
+        n = self.total - first_record if n is None else n
+        hist = np.zeros(kmer_stats_bins(self.k), np.uint64)
+        binned, over = C.c_uint64(), C.c_uint64()
+        cb = KMER_STATS_PROGRESS((lambda done, _user: progress(done)) if progress else 0)
+        check(bt_kmc_scan_kmer_stats_file(self.h, suf_path.encode(), payload_offset, first_record, n, chunk_records, _np_ptr(hist), C.byref(binned),
+                                          C.byref(over), cb, None))
+        return hist, binned.value, over.value
+
     def close(self):
         if self.h:
             bt_kmc_scan_destroy(self.h)
             self.h = None
+
+
+def kmer_stats_bins(k):
+    """bins of the getKmerStats histogram: 256 counts x C(k+3,3) compositions (include/btgpu.h)"""
+    return int(bt_kmer_stats_num_bins(k))
+
+
+def kmer_stats_rows(hist, k):
+    """the non-zero bins of a getKmerStats histogram as rows (number, count, A, C, G, T), in bin order = sorted by (count, A, C, G, T)"""
+    comp = np.array([(a, c, g, k - a - c - g) for a in range(k + 1) for c in range(k + 1 - a) for g in range(k + 1 - a - c)], np.int64)
+    hist = np.asarray(hist, np.uint64)
+    assert len(hist) == 256 * len(comp)
+    nz = np.nonzero(hist)[0]
+    count, idx = np.divmod(nz, len(comp))
+    return np.column_stack([hist[nz].astype(np.int64), count, comp[idx]])
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -263,6 +263,26 @@ int bt_kmc_scan_run_file(bt_kmc_scan *s, bt_bloom *path_bloom, bt_table *table, 
  * are added to a sample's KmerBloom (created with bt_bloom_create(ctx, total_kmers, fpr, k, 0, ..), written with bt_bloom_save:
  * byte-identical .bloomMeta / .bloomData, insertion being an order-independent OR) */
 int bt_kmc_scan_make_bloom(bt_kmc_scan *s, bt_bloom *sample_bloom, const uint8_t *d_records, uint64_t first_record, uint64_t n);
+/* bayesTyperTools getKmerStats (src/bayesTyperTools/scripts/getKmerStats.cpp:87-127): a histogram over (k-mer count, #A, #C, #G, #T) of
+ * the records whose counter lies in the count range (bt_kmc_scan_set_count_range, as CKMCFile::ReadNextKmer skips the others).
+ * Bin layout: count * C(k+3,3) + comp(a, c, g) for count 0..255, where comp enumerates the compositions a + c + g <= k (t = k - a - c - g)
+ * in (a, c, g) lexicographic order:
+ *   comp(a, c, g) = [C(k+3,3) - C(k-a+3,3)] + [C(k-a+2,2) - C(k-a-c+2,2)] + g
+ * so increasing bin index is increasing (count, A, C, G, T).  bt_kmer_stats_num_bins(k) = 256 * C(k+3,3) (63 MB of uint64 at k = 55, 98 MB at
+ * k = 64); 0 for k outside 1..64.
+ * The reference asserts count <= 255 (line 113): a record in range with a larger count is not binned but counted in *d_over255.
+ * Adds are exact integer adds, so the histogram does not depend on the order records arrive in. */
+uint64_t bt_kmer_stats_num_bins(uint32_t k);
+/* Records [first_record, first_record + n) in device memory (d_records at record first_record, 16-byte aligned, as for
+ * bt_kmc_scan_make_bloom) are ADDED into the caller-zeroed device histogram d_hist (bt_kmer_stats_num_bins(k) uint64) and the device
+ * uint64 *d_over255.  Asynchronous on the context's stream. */
+int bt_kmc_scan_kmer_stats(bt_kmc_scan *s, const uint8_t *d_records, uint64_t first_record, uint64_t n, uint64_t *d_hist, uint64_t *d_over255);
+/* The same for records [first_record, first_record + n) of the .kmc_suf file at payload_offset (4: behind the "KMCS" marker), streamed through
+ * the staging slots of bt_kmc_scan_run_file (chunk_records: records per transfer, 0: default).  Blocking.  h_hist (host,
+ * bt_kmer_stats_num_bins(k) uint64) receives the histogram; *h_binned = records binned, *h_over255 = records in range above 255 (either may be
+ * NULL).  progress (may be NULL) is called with the number of records streamed so far after each chunk is handed to the device. */
+int bt_kmc_scan_kmer_stats_file(bt_kmc_scan *s, const char *suf_path, uint64_t payload_offset, uint64_t first_record, uint64_t n, uint64_t chunk_records,
+                                uint64_t *h_hist, uint64_t *h_binned, uint64_t *h_over255, void (*progress)(uint64_t records_done, void *user), void *progress_user);
 /* decode only (tests): d_kmers[2*i..] = packed k-mer of record i, d_counts[i] = its count */
 int bt_kmc_scan_decode(bt_kmc_scan *s, const uint8_t *d_records, uint64_t first_record, uint64_t n,
                        uint64_t *d_kmers, uint32_t *d_counts);
