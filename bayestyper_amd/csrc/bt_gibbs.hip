@@ -847,10 +847,12 @@ struct bt_gibbs_source {
     std::vector<void *> allocs;
     uint64_t device_bytes = 0, flat_bytes = 0;
     bool uploaded = false;
+    uint64_t count[21] = {0};      // elements of the flat device arrays, in BuildBatch's order (bt_gibbs_source_fetch)
 };
 
 // a malformed batch must not make the tile builder read out of bounds: offsets monotone, indices in range
-static int validate_batch(const bt_gibbs_batch *B) {
+// rows = false: the per-row arrays and index lists are absent (the library built them itself: bt_gibbs_source_create_from_paths); only the small arrays are checked
+static int validate_batch(const bt_gibbs_batch *B, bool rows = true) {
     const uint32_t G = B->num_groups, C = B->num_clusters;
     if (G == 0 || C == 0) return fail("bt_gibbs_create: empty batch");
     if (B->group_cluster_off[G] != C) return fail("bt_gibbs_create: group_cluster_off[G] != num_clusters");
@@ -861,7 +863,7 @@ static int validate_batch(const bt_gibbs_batch *B) {
             return true;
         };
         if (B->group_cluster_off[0] != 0 || !monotone(B->group_cluster_off, G) || !monotone(B->group_source_off, G) || !monotone(B->edge_off, C) || !monotone(B->kmer_off, C) ||
-            !monotone(B->unique_off, C) || !monotone(B->multi_off, C) || !monotone(B->nestdep_off, C) || !monotone(B->kv_off, B->kmer_off[C]) ||
+            !monotone(B->unique_off, C) || !monotone(B->multi_off, C) || !monotone(B->nestdep_off, C) || (rows && !monotone(B->kv_off, B->kmer_off[C])) ||
             !monotone(B->nestdep_var_off, B->nestdep_off[C]))
             return fail("bt_gibbs_create: an offset array of the batch is not monotone");
         uint64_t hap_at = 0, var_at = 0, hv_at = 0;
@@ -874,11 +876,11 @@ static int validate_batch(const bt_gibbs_batch *B) {
                 const uint32_t H = B->num_haplotypes[c], V = B->num_variants[c], K = B->kmer_off[c + 1] - B->kmer_off[c];
                 for (uint32_t i = B->edge_off[c]; i < B->edge_off[c + 1]; ++i)
                     if (B->edges[i] >= nv) return fail("bt_gibbs_create: edge target outside its group");
-                for (uint32_t i = B->unique_off[c]; i < B->unique_off[c + 1]; ++i)
+                for (uint32_t i = B->unique_off[c]; rows && i < B->unique_off[c + 1]; ++i)
                     if (B->unique_idx[i] >= K) return fail("bt_gibbs_create: unique k-mer index outside its cluster");
-                for (uint32_t i = B->multi_off[c]; i < B->multi_off[c + 1]; ++i)
+                for (uint32_t i = B->multi_off[c]; rows && i < B->multi_off[c + 1]; ++i)
                     if (B->multi_idx[i] >= K) return fail("bt_gibbs_create: multicluster k-mer index outside its cluster");
-                for (uint32_t r = B->kmer_off[c]; r < B->kmer_off[c + 1]; ++r) {
+                for (uint32_t r = B->kmer_off[c]; rows && r < B->kmer_off[c + 1]; ++r) {
                     if (B->kmer_shared[r] >= (int32_t)B->group_num_shared[gi]) return fail("bt_gibbs_create: shared k-mer record outside its group");
                     for (uint32_t e = B->kv_off[r]; e < B->kv_off[r + 1]; ++e)
                         if (B->kv_var[e] >= V) return fail("bt_gibbs_create: k-mer overlaps a variant outside its cluster");
@@ -896,7 +898,9 @@ static int validate_batch(const bt_gibbs_batch *B) {
 }
 
 // dimensions + slice starts of every cluster and group of a batch; upload: the flat arrays go to the device (they stay there until the source is destroyed)
-static int source_build(bt_ctx *ctx, uint32_t S, const bt_gibbs_batch *B, bool upload, bt_gibbs_source **out) {
+// pc != nullptr: the per-row arrays and index lists are device arrays already (pc's, and d_shared); B carries the small host arrays, its kmer_off / unique_off /
+// multi_off / group_num_shared are the library's own.  On success the caller hands their ownership to the source.
+static int source_build(bt_ctx *ctx, uint32_t S, const bt_gibbs_batch *B, bool upload, bt_gibbs_source **out, const bt::PathsCandidates *pc = nullptr, const int32_t *d_shared = nullptr) {
     const uint32_t G = B->num_groups, C = B->num_clusters;
     std::unique_ptr<bt_gibbs_source> src(new bt_gibbs_source());
     src->ctx = ctx;
@@ -914,7 +918,7 @@ static int source_build(bt_ctx *ctx, uint32_t S, const bt_gibbs_batch *B, bool u
         x.r0 = B->kmer_off[c];
         x.K = B->kmer_off[c + 1] - x.r0;
         if (x.H < 1 || x.H >= 65535 || x.V < 1) return fail("bt_gibbs_create: cluster with no haplotype / variant or too many haplotypes");
-        x.nnz = B->kv_off[B->kmer_off[c + 1]] - B->kv_off[B->kmer_off[c]];
+        x.nnz = pc ? pc->cluster_kv0[c + 1] - pc->cluster_kv0[c] : B->kv_off[B->kmer_off[c + 1]] - B->kv_off[B->kmer_off[c]];
         x.u0 = B->unique_off[c];
         x.nu = B->unique_off[c + 1] - x.u0;
         x.m0 = B->multi_off[c];
@@ -945,38 +949,47 @@ static int source_build(bt_ctx *ctx, uint32_t S, const bt_gibbs_batch *B, bool u
     for (uint32_t gi = 0; gi < G; ++gi)
         src->gd[gi] = GroupDims{B->group_cluster_off[gi], B->group_cluster_off[gi + 1] - B->group_cluster_off[gi], B->group_source_off[gi], B->group_source_off[gi + 1] - B->group_source_off[gi],
                                 B->group_num_shared[gi], B->group_index[gi], gi, 0};
-    const uint64_t R = B->kmer_off[C], NNZ = B->kv_off[R], ND = B->nestdep_off[C];
+    const uint64_t R = B->kmer_off[C], NNZ = pc ? pc->nnz : B->kv_off[R], ND = B->nestdep_off[C];
     src->flat_bytes = (uint64_t)G * S + (uint64_t)B->group_source_off[G] * 4 + (uint64_t)B->edge_off[C] * 4 + mult + R * (S + 11ull) + 4 + NNZ * 2 + kvb * 4 +
                       ((uint64_t)B->unique_off[C] + B->multi_off[C]) * 4 + hapvar * 2 + ((uint64_t)hap + 1) * 4 + (uint64_t)B->hapnest_off[hap] * 4 + (uint64_t)var * 3 + ND * 8 + 4 +
                       (uint64_t)B->nestdep_var_off[ND] * 2;
     if (upload) {
         BT_HIP(hipSetDevice(ctx->device));
         hipError_t e = hipSuccess;
-        auto up = [&](const void *h, size_t bytes, const void **d_out) -> hipError_t {
+        uint32_t field_at = 0;
+        // resident != nullptr: the array was built on the device (bt_gibbs_source_create_from_paths): nothing to allocate or copy; accounted like an uploaded one
+        auto up = [&](const void *h, size_t bytes, size_t elem, const void **d_out, const void *resident) -> hipError_t {
+            src->count[field_at++] = bytes / elem;
+            src->device_bytes += std::max<size_t>(bytes, 16);
+            if (resident) {
+                *d_out = resident;
+                return hipSuccess;
+            }
             void *d = nullptr;
             hipError_t er = hipMalloc(&d, std::max<size_t>(bytes, 16));
             if (er != hipSuccess) return er;
             src->allocs.push_back(d);
-            src->device_bytes += std::max<size_t>(bytes, 16);
             *d_out = d;
             return bytes ? hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
         };
         BuildBatch &bb = src->dev;
 #define BT_UP(field, ptr, bytes) \
-    if (e == hipSuccess) e = up(ptr, bytes, reinterpret_cast<const void **>(&bb.field))
+    if (e == hipSuccess) e = up(ptr, bytes, sizeof(*bb.field), reinterpret_cast<const void **>(&bb.field), nullptr)
+#define BT_UP_ROWS(field, ptr, bytes, dev) \
+    if (e == hipSuccess) e = up(ptr, bytes, sizeof(*bb.field), reinterpret_cast<const void **>(&bb.field), pc ? static_cast<const void *>(dev) : nullptr)
         BT_UP(group_ploidy, B->group_ploidy, (size_t)G * S);
         BT_UP(group_sources, B->group_sources, (size_t)B->group_source_off[G] * 4);
         BT_UP(edges, B->edges, (size_t)B->edge_off[C] * 4);
-        BT_UP(hap_kmer_mult, B->hap_kmer_mult, (size_t)mult);
-        BT_UP(kmer_has_counts, B->kmer_has_counts, (size_t)R);
-        BT_UP(kmer_counts, B->kmer_counts, (size_t)R * S);
-        BT_UP(kmer_ic_mult, B->kmer_ic_mult, (size_t)R * 2);
-        BT_UP(kmer_shared, B->kmer_shared, (size_t)R * 4);
-        BT_UP(kv_off, B->kv_off, (size_t)(R + 1) * 4);
-        BT_UP(kv_var, B->kv_var, (size_t)NNZ * 2);
-        BT_UP(kv_bits, B->kv_bits, (size_t)kvb * 4);
-        BT_UP(unique_idx, B->unique_idx, (size_t)B->unique_off[C] * 4);
-        BT_UP(multi_idx, B->multi_idx, (size_t)B->multi_off[C] * 4);
+        BT_UP_ROWS(hap_kmer_mult, B->hap_kmer_mult, (size_t)mult, pc->hap_kmer_mult);
+        BT_UP_ROWS(kmer_has_counts, B->kmer_has_counts, (size_t)R, pc->kmer_has_counts);
+        BT_UP_ROWS(kmer_counts, B->kmer_counts, (size_t)R * S, pc->kmer_counts);
+        BT_UP_ROWS(kmer_ic_mult, B->kmer_ic_mult, (size_t)R * 2, pc->kmer_ic_mult);
+        BT_UP_ROWS(kmer_shared, B->kmer_shared, (size_t)R * 4, d_shared);
+        BT_UP_ROWS(kv_off, B->kv_off, (size_t)(R + 1) * 4, pc->kv_off);
+        BT_UP_ROWS(kv_var, B->kv_var, (size_t)NNZ * 2, pc->kv_var);
+        BT_UP_ROWS(kv_bits, B->kv_bits, (size_t)kvb * 4, pc->kv_bits);
+        BT_UP_ROWS(unique_idx, B->unique_idx, (size_t)B->unique_off[C] * 4, pc->unique_idx);
+        BT_UP_ROWS(multi_idx, B->multi_idx, (size_t)B->multi_off[C] * 4, pc->multi_idx);
         BT_UP(hap_allele, B->hap_allele, (size_t)hapvar * 2);
         BT_UP(hapnest_off, B->hapnest_off, ((size_t)hap + 1) * 4);
         BT_UP(hapnest_idx, B->hapnest_idx, (size_t)B->hapnest_off[hap] * 4);
@@ -986,6 +999,7 @@ static int source_build(bt_ctx *ctx, uint32_t S, const bt_gibbs_batch *B, bool u
         BT_UP(nestdep_var_off, B->nestdep_var_off, (size_t)(ND + 1) * 4);
         BT_UP(nestdep_var, B->nestdep_var, (size_t)B->nestdep_var_off[ND] * 2);
 #undef BT_UP
+#undef BT_UP_ROWS
         const hipError_t e2 = hipStreamSynchronize(ctx->stream);   // (the caller's arrays may go away)
         if (e != hipSuccess || e2 != hipSuccess) {
             for (void *d : src->allocs) (void)hipFree(d);
@@ -1005,6 +1019,84 @@ int bt_gibbs_source_create(bt_ctx *ctx, uint32_t num_samples, const bt_gibbs_bat
     const int rc = validate_batch(B);
     if (rc != BT_OK) return rc;
     return source_build(ctx, num_samples, B, true, out);
+}
+
+int bt_gibbs_source_create_from_paths(bt_ctx *ctx, uint32_t num_samples, bt_paths *p, const bt_gibbs_batch *structure, bt_gibbs_source **out) {
+    if (!ctx || !p || !structure || !out) return fail("bt_gibbs_source_create_from_paths: null argument");
+    if (num_samples < 1 || num_samples > 30) return fail("bt_gibbs_source_create_from_paths: number of samples must be in 1..30");
+    bt::PathsCandidates pc{};
+    int rc = bt::paths_device_candidates(p, "bt_gibbs_source_create_from_paths", &pc);
+    if (rc != BT_OK) return rc;
+    const bt_gibbs_batch *B = structure;
+    if (pc.ctx->device != ctx->device) return fail("bt_gibbs_source_create_from_paths: the context is on another device than the paths handle");
+    if (pc.S != num_samples) return fail("bt_gibbs_source_create_from_paths: the number of samples differs from the count table's the candidates were built against");
+    if (B->hap_kmer_mult || B->kmer_has_counts || B->kmer_counts || B->kmer_ic_mult || B->kmer_shared || B->kv_off || B->kv_var || B->kv_bits || B->unique_idx || B->multi_idx ||
+        B->group_num_shared)
+        return fail("bt_gibbs_source_create_from_paths: the per-row pointers, the index lists, kmer_shared and group_num_shared of `structure` must be NULL (they come from the paths handle)");
+    if (B->num_clusters != pc.C) return fail("bt_gibbs_source_create_from_paths: `structure` has another number of clusters than the paths handle");
+    if (!B->group_index || !B->group_cluster_off || !B->group_ploidy || !B->group_source_off || !B->group_sources || !B->cluster_idx || !B->edge_off || !B->edges ||
+        !B->num_haplotypes || !B->num_variants || !B->hap_allele || !B->hapnest_off || !B->hapnest_idx || !B->var_num_alleles || !B->var_has_dependency || !B->nestdep_off ||
+        !B->nestdep_cluster || !B->nestdep_var_off || !B->nestdep_var)
+        return fail("bt_gibbs_source_create_from_paths: a per-group / per-cluster / haplotype / variant / nested-dependency array of `structure` is missing");
+    for (uint32_t c = 0; c < pc.C; ++c)
+        if (B->num_haplotypes[c] != pc.num_paths[c]) return fail("bt_gibbs_source_create_from_paths: num_haplotypes of `structure` differs from the paths handle's number of paths");
+    if (B->num_groups == 0 || B->group_cluster_off[0] != 0 || B->group_cluster_off[B->num_groups] != pc.C)
+        return fail("bt_gibbs_source_create_from_paths: group_cluster_off does not cover the clusters");
+    for (uint32_t g = 0; g < B->num_groups; ++g)
+        if (B->group_cluster_off[g + 1] <= B->group_cluster_off[g]) return fail("bt_gibbs_source_create_from_paths: group without clusters");
+    // the batch as the source builder sees it: the caller's small arrays + the library's own offsets
+    bt_gibbs_batch Bp = *B;
+    std::vector<uint32_t> num_shared(B->num_groups, 0);
+    Bp.kmer_off = pc.kmer_off;
+    Bp.unique_off = pc.unique_off;
+    Bp.multi_off = pc.multi_off;
+    Bp.group_num_shared = num_shared.data();
+    rc = validate_batch(&Bp, false);
+    if (rc != BT_OK) return rc;
+    int32_t *d_shared = nullptr;
+    rc = bt::paths_number_shared(p, B->group_cluster_off, B->num_groups, &d_shared, num_shared.data());
+    if (rc != BT_OK) return rc;
+    bt_gibbs_source *src = nullptr;
+    rc = source_build(ctx, num_samples, &Bp, true, &src, &pc, d_shared);
+    if (rc != BT_OK) {
+        (void)hipFree(d_shared);
+        return rc;   // (the paths handle keeps its candidates)
+    }
+    src->allocs.push_back(d_shared);
+    bt::paths_release_candidates(p, src->allocs);
+    *out = src;
+    return BT_OK;
+}
+
+int bt_gibbs_source_fetch(bt_gibbs_source *src, uint64_t *h_counts, const bt_gibbs_source_arrays *out) {
+    if (!src || !h_counts) return fail("bt_gibbs_source_fetch: null argument");
+    if (!src->uploaded) return fail("bt_gibbs_source_fetch: the source holds no device arrays");
+    for (int i = 0; i < 21; ++i) h_counts[i] = src->count[i];
+    h_counts[21] = src->G;
+    h_counts[22] = h_counts[23] = h_counts[24] = (uint64_t)src->C + 1;
+    if (!out) return BT_OK;
+    BT_HIP(hipSetDevice(src->ctx->device));
+    BT_HIP(hipStreamSynchronize(src->ctx->stream));
+    const BuildBatch &bb = src->dev;
+    const void *dev[21] = {bb.group_ploidy, bb.group_sources, bb.edges, bb.hap_kmer_mult, bb.kmer_has_counts, bb.kmer_counts, bb.kmer_ic_mult, bb.kmer_shared, bb.kv_off, bb.kv_var, bb.kv_bits,
+                           bb.unique_idx, bb.multi_idx, bb.hap_allele, bb.hapnest_off, bb.hapnest_idx, bb.var_num_alleles, bb.var_has_dependency, bb.nestdep_cluster, bb.nestdep_var_off,
+                           bb.nestdep_var};
+    void *const host[21] = {out->group_ploidy, out->group_sources, out->edges, out->hap_kmer_mult, out->kmer_has_counts, out->kmer_counts, out->kmer_ic_mult, out->kmer_shared, out->kv_off,
+                            out->kv_var, out->kv_bits, out->unique_idx, out->multi_idx, out->hap_allele, out->hapnest_off, out->hapnest_idx, out->var_num_alleles, out->var_has_dependency,
+                            out->nestdep_cluster, out->nestdep_var_off, out->nestdep_var};
+    static const uint8_t elem[21] = {1, 4, 4, 1, 1, 1, 1, 4, 4, 2, 4, 4, 4, 2, 4, 4, 2, 1, 4, 4, 2};
+    for (int i = 0; i < 21; ++i)
+        if (host[i] && src->count[i]) BT_HIP(hipMemcpy(host[i], dev[i], src->count[i] * elem[i], hipMemcpyDeviceToHost));
+    if (out->group_num_shared)
+        for (uint32_t g = 0; g < src->G; ++g) out->group_num_shared[g] = src->gd[g].num_shared;
+    const uint32_t C = src->C;
+    for (uint32_t c = 0; c < C; ++c) {
+        const ClusterDims &x = src->cd[c];
+        if (out->kmer_off) out->kmer_off[c] = x.r0, out->kmer_off[c + 1] = x.r0 + x.K;
+        if (out->unique_off) out->unique_off[c] = x.u0, out->unique_off[c + 1] = x.u0 + x.nu;
+        if (out->multi_off) out->multi_off[c] = x.m0, out->multi_off[c + 1] = x.m0 + x.nm;
+    }
+    return BT_OK;
 }
 
 int bt_gibbs_source_destroy(bt_gibbs_source *src) {

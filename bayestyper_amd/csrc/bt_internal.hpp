@@ -100,6 +100,26 @@ inline void ctx_host_give(bt_ctx *ctx, void *p, size_t bytes, unsigned flags) {
 }
 }  // namespace bt
 
+namespace bt {
+// The seam between bt_paths.hip and bt_gibbs.hip (bt_gibbs_source_create_from_paths): what bt_paths_candidates_device left in a paths handle.
+// Lower-case pointers are DEVICE arrays (bt_gibbs_batch's fields of the same names), the rest host arrays that live as long as the handle.
+struct PathsCandidates {
+    bt_ctx *ctx;
+    uint32_t C, S;
+    uint64_t R, nnz, kv_words, mult_bytes, num_unique, num_multi;
+    const uint32_t *num_paths, *kmer_off, *unique_off, *multi_off, *cluster_kv0;   // host: [C], [C+1] x 4 (cluster_kv0: first incidence entry of the cluster)
+    const uint8_t *hap_kmer_mult, *kmer_has_counts, *kmer_counts, *kmer_ic_mult;
+    const uint32_t *kv_off, *kv_bits, *unique_idx, *multi_idx;
+    const uint16_t *kv_var;
+};
+// a view of the handle's device candidates (an error, named after `who`, when it holds none)
+int paths_device_candidates(bt_paths *p, const char *who, PathsCandidates *out);
+// kmer_shared [R] (a device array the caller owns) and group_num_shared [G] (host) for groups given as ranges of the handle's clusters
+int paths_number_shared(bt_paths *p, const uint32_t *group_cluster_off, uint32_t G, int32_t **d_kmer_shared, uint32_t *h_group_num_shared);
+// the device arrays change owner (appended to allocs; the row keys are released): the handle reports "no candidates" afterwards
+void paths_release_candidates(bt_paths *p, std::vector<void *> &allocs);
+}  // namespace bt
+
 struct bt_timer {
     bt_ctx *ctx = nullptr;
     hipEvent_t start = nullptr, stop = nullptr;

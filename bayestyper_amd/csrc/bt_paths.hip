@@ -15,8 +15,6 @@
 
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
 #include <exception>
 #include <cstring>
@@ -532,9 +530,10 @@ __global__ __launch_bounds__(BLOCK) void scan_add_kernel(uint32_t *__restrict__ 
 // per row: key, table record
 __global__ __launch_bounds__(BLOCK) void rows_kernel(IndexA A, TableView t, const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pos_slot_a,
                                                       const uint32_t *__restrict__ flag, const uint32_t *__restrict__ row_of_pos, const int64_t *__restrict__ slots,
-                                                      const uint8_t *__restrict__ list_flags, uint64_t L, uint32_t S, uint32_t *__restrict__ a_row,
+                                                      const uint8_t *__restrict__ list_flags, const uint32_t *__restrict__ pos_path,
+                                                      const uint32_t *__restrict__ path_cluster, uint64_t L, uint32_t S, uint32_t *__restrict__ a_row,
                                                       uint64_t *__restrict__ row_key, uint8_t *__restrict__ row_flags, uint8_t *__restrict__ row_counts,
-                                                      uint8_t *__restrict__ row_ic) {
+                                                      uint8_t *__restrict__ row_ic, uint32_t *__restrict__ row_cluster) {
     for (uint64_t pos = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; pos < L; pos += (uint64_t)gridDim.x * BLOCK) {
         if (!flag[pos]) continue;
         const uint32_t a = pos_slot_a[pos], row = row_of_pos[pos], j = A.list_id[a];
@@ -542,6 +541,7 @@ __global__ __launch_bounds__(BLOCK) void rows_kernel(IndexA A, TableView t, cons
         row_key[2 * (uint64_t)row] = A.lo[a];
         row_key[2 * (uint64_t)row + 1] = A.hi[a];
         row_flags[row] = list_flags[j];
+        row_cluster[row] = path_cluster[pos_path[pos]];
         const int64_t slot = slots[j];
         for (uint32_t s = 0; s < S; ++s) row_counts[(uint64_t)row * S + s] = slot >= 0 ? t.count_bytes((uint64_t)slot)[s] : (uint8_t)0;
         const uint32_t meta = slot >= 0 ? *t.meta((uint64_t)slot) : 0u;
@@ -573,19 +573,235 @@ __global__ __launch_bounds__(BLOCK) void triples_kernel(IndexA A, const uint8_t 
                                                          const uint8_t *__restrict__ list_flags, const uint32_t *__restrict__ a_row, const uint32_t *__restrict__ pos_path,
                                                          const uint32_t *__restrict__ pos_nt, const uint32_t *__restrict__ path_local,
                                                          const uint32_t *__restrict__ iv_off, const Interval *__restrict__ iv, uint64_t L,
-                                                         unsigned long long *__restrict__ cursor, uint64_t *__restrict__ out /* null: count only */) {
+                                                         unsigned long long *__restrict__ cursor, const uint32_t *__restrict__ row_off, uint32_t *__restrict__ row_cnt,
+                                                         uint32_t *__restrict__ out /* null: count pass */) {
+    // count pass: row_cnt[row] = triples of the row, *cursor = triples of the batch (64 bits: the caller refuses 2^32 or more before any 32-bit count is used).
+    // write pass: a triple goes to the next free place of ITS ROW's segment [row_off[row], row_off[row + 1]) as (variant << 16 | path); the order inside a
+    // segment is the arrival order, and nothing downstream depends on it (row_entries_*: distinct variants ascending, OR over the paths).
     for (uint64_t pos = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; pos < L; pos += (uint64_t)gridDim.x * BLOCK) {
         if (!valid[pos]) continue;
         const uint32_t a = pos_slot_a[pos];
         if (list_flags[A.list_id[a]] & 2) continue;
-        const uint32_t gp = pos_path[pos], nt = pos_nt[pos];
+        const uint32_t gp = pos_path[pos], nt = pos_nt[pos], row = a_row[a];
+        uint32_t n = 0;
         for (uint32_t e = iv_off[gp]; e < iv_off[gp + 1]; ++e) {
             if (iv[e].first <= nt && nt < iv[e].second) {
-                const unsigned long long j = atomicAdd(cursor, 1ULL);
-                if (out) out[j] = ((uint64_t)a_row[a] << 32) | ((uint64_t)iv[e].variant << 16) | path_local[gp];
+                if (out) {
+                    const uint32_t j = row_off[row] + atomicAdd(&row_cnt[row], 1u);
+                    if (j < row_off[row + 1]) out[j] = ((uint32_t)iv[e].variant << 16) | (path_local[gp] & 0xffffu);
+                }
+                ++n;
             }
         }
+        if (!out && n) {
+            atomicAdd(&row_cnt[row], n);
+            atomicAdd(cursor, (unsigned long long)n);
+        }
     }
+}
+
+// ---- variant_haplotype_indices of a row from its triples, without a global sort ----
+// A row's entries are its DISTINCT variants in ascending order, an entry's bitset the OR over the entry's paths.  Rows are independent, so every row is
+// handled by the smallest unit that holds it: a lane (a sorting network over registers), a wavefront (register bitonic over __shfl_xor) or a workgroup.
+// The workgroup path does not sort: the variant index is 16 bits wide, so the set of a row's variants is a 65536-bit map in LDS, an entry's rank the number
+// of set bits below it; it holds for a row of any length.  Each path runs twice: count (row_nnz[row] = entries) and, after the scan that makes kv_off, write.
+constexpr uint32_t ROW_LANE_MAX = 8, ROW_WAVE_MAX = 64, ROW_MAP_WORDS = 2048;
+struct RowJob {
+    const uint32_t *trip, *row_off;        // triples, [R+1] segments
+    uint32_t *row_nnz;                     // count pass: entries per row
+    const uint32_t *kv_off;                // write pass: [R+1]
+    const uint32_t *row_cluster;           // [R]
+    const uint32_t *cluster_h, *cluster_kv0;   // [C] haplotypes, first entry of the cluster
+    const uint64_t *cluster_kvb;           // [C] first bitset word of the cluster
+    uint16_t *kv_var;
+    uint32_t *kv_bits;
+    uint32_t write;
+    __device__ inline uint32_t *bits_of(uint32_t row, uint32_t &hw) const {
+        const uint32_t c = row_cluster[row];
+        hw = (cluster_h[c] + 31u) / 32u;
+        return kv_bits + cluster_kvb[c] + (uint64_t)(kv_off[row] - cluster_kv0[c]) * hw;
+    }
+};
+// one lane per row of at most ROW_LANE_MAX (<= 8) triples; longer rows are handed to the wavefront / workgroup lists (count pass only)
+__global__ __launch_bounds__(BLOCK) void row_entries_lane_kernel(RowJob J, uint64_t R, uint32_t lane_max, uint32_t wave_max, uint32_t *__restrict__ wave_list,
+                                                                  uint32_t wave_cap, uint32_t *__restrict__ block_list, uint32_t block_cap,
+                                                                  uint32_t *__restrict__ list_n /* [0] wave, [1] block */) {
+    for (uint64_t row = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; row < R; row += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t t0 = J.row_off[row], n = J.row_off[row + 1] - t0;
+        if (n > lane_max) {
+            if (!J.write) {
+                if (n <= wave_max) {
+                    const uint32_t j = atomicAdd(&list_n[0], 1u);
+                    if (j < wave_cap) wave_list[j] = (uint32_t)row;
+                } else {
+                    const uint32_t j = atomicAdd(&list_n[1], 1u);
+                    if (j < block_cap) block_list[j] = (uint32_t)row;
+                }
+            }
+            continue;
+        }
+        uint32_t v[ROW_LANE_MAX];
+#pragma unroll
+        for (uint32_t i = 0; i < ROW_LANE_MAX; ++i) v[i] = i < n ? J.trip[t0 + i] : 0xFFFFFFFFu;
+#pragma unroll
+        for (uint32_t round = 0; round < ROW_LANE_MAX; ++round)   // odd-even transposition network, fully unrolled: v stays in registers
+#pragma unroll
+            for (uint32_t i = round & 1u; i + 1 < ROW_LANE_MAX; i += 2) {
+                const uint32_t lo = min(v[i], v[i + 1]), hi = max(v[i], v[i + 1]);
+                v[i] = lo;
+                v[i + 1] = hi;
+            }
+        uint32_t hw = 0, e = 0;
+        uint32_t *bits = J.write && n ? J.bits_of((uint32_t)row, hw) : nullptr;
+        uint16_t *var = J.kv_var + (J.write ? J.kv_off[row] : 0u);
+#pragma unroll
+        for (uint32_t i = 0; i < ROW_LANE_MAX; ++i) {
+            if (i >= n) continue;
+            if (i == 0 || (v[i] >> 16) != (v[i - (i ? 1 : 0)] >> 16)) {
+                if (J.write) var[e] = (uint16_t)(v[i] >> 16);
+                ++e;
+            }
+            if (J.write) bits[(uint64_t)(e - 1) * hw + ((v[i] & 0xffffu) >> 5)] |= 1u << (v[i] & 31u);   // this lane owns the row's words (zeroed before)
+        }
+        if (!J.write) J.row_nnz[row] = e;
+    }
+}
+// one wavefront per listed row of at most 64 triples: bitonic sort of (variant, path) across the lanes, heads of equal-variant runs are the entries
+__global__ __launch_bounds__(BLOCK) void row_entries_wave_kernel(RowJob J, const uint32_t *__restrict__ list, uint32_t nlist) {
+    const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (BLOCK / 64);
+    for (uint32_t item = blockIdx.x * (BLOCK / 64) + threadIdx.x / 64; item < nlist; item += waves) {
+        const uint32_t row = list[item], t0 = J.row_off[row], n = min(J.row_off[row + 1] - t0, 64u);
+        uint32_t x = lane < n ? J.trip[t0 + lane] : 0xFFFFFFFFu;
+#pragma unroll
+        for (uint32_t k = 2; k <= 64; k <<= 1)
+#pragma unroll
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                const uint32_t y = (uint32_t)__shfl_xor((int)x, (int)j, 64);
+                const bool keep_min = ((lane & k) == 0) == ((lane & j) == 0);
+                x = keep_min ? min(x, y) : max(x, y);
+            }
+        const uint32_t prev = (uint32_t)__shfl_up((int)x, 1, 64);
+        const bool head = lane < n && (lane == 0 || (prev >> 16) != (x >> 16));
+        const unsigned long long heads = __ballot(head);
+        if (!J.write) {
+            if (lane == 0) J.row_nnz[row] = (uint32_t)__popcll(heads);
+            continue;
+        }
+        const uint32_t e = (uint32_t)__popcll(heads & (lane == 63 ? ~0ULL : ((2ULL << lane) - 1ULL))) - 1u;   // heads at or before this lane, minus one
+        uint32_t hw = 0;
+        uint32_t *bits = J.bits_of(row, hw);
+        if (head) J.kv_var[J.kv_off[row] + e] = (uint16_t)(x >> 16);
+        if (lane < n) atomicOr(&bits[(uint64_t)e * hw + ((x & 0xffffu) >> 5)], 1u << (x & 31u));
+    }
+}
+// one workgroup per listed row, any number of triples: the row's variants as a bit map over the 16-bit variant index, ranks by a prefix sum of popcounts
+__global__ __launch_bounds__(BLOCK) void row_entries_block_kernel(RowJob J, const uint32_t *__restrict__ list, uint32_t nlist) {
+    __shared__ uint32_t map[ROW_MAP_WORDS], before[ROW_MAP_WORDS], part[BLOCK];
+    constexpr uint32_t PER = ROW_MAP_WORDS / BLOCK;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t item = blockIdx.x; item < nlist; item += gridDim.x) {
+        const uint32_t row = list[item], t0 = J.row_off[row], n = J.row_off[row + 1] - t0;
+        for (uint32_t i = tid; i < ROW_MAP_WORDS; i += BLOCK) map[i] = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += BLOCK) {
+            const uint32_t var = J.trip[t0 + i] >> 16;
+            atomicOr(&map[var >> 5], 1u << (var & 31u));
+        }
+        __syncthreads();
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < PER; ++q) {
+            before[tid * PER + q] = s;
+            s += (uint32_t)__popc(map[tid * PER + q]);
+        }
+        part[tid] = s;
+        __syncthreads();
+        for (uint32_t off = 1; off < BLOCK; off <<= 1) {
+            const uint32_t add = tid >= off ? part[tid - off] : 0u;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        const uint32_t base = part[tid] - s;
+#pragma unroll
+        for (uint32_t q = 0; q < PER; ++q) before[tid * PER + q] += base;
+        __syncthreads();
+        if (!J.write) {
+            if (tid == 0) J.row_nnz[row] = part[BLOCK - 1];
+        } else {
+            uint32_t hw = 0;
+            uint32_t *bits = J.bits_of(row, hw);
+            uint16_t *var_out = J.kv_var + J.kv_off[row];
+            for (uint32_t w = tid; w < ROW_MAP_WORDS; w += BLOCK) {
+                uint32_t m = map[w], e = before[w];
+                while (m) {
+                    var_out[e++] = (uint16_t)(w * 32u + (uint32_t)__ffs((int)m) - 1u);
+                    m &= m - 1u;
+                }
+            }
+            for (uint32_t i = tid; i < n; i += BLOCK) {
+                const uint32_t t = J.trip[t0 + i], var = t >> 16;
+                const uint32_t e = before[var >> 5] + (uint32_t)__popc(map[var >> 5] & ((1u << (var & 31u)) - 1u));
+                atomicOr(&bits[(uint64_t)e * hw + ((t & 0xffffu) >> 5)], 1u << (t & 31u));
+            }
+        }
+        __syncthreads();   // (the next row clears the map)
+    }
+}
+
+// ---- row lists: kmer_has_counts, and the stable split of a cluster's rows into unique / multicluster (first-seen = row order) ----
+__global__ __launch_bounds__(BLOCK) void row_flags_kernel(const uint8_t *__restrict__ row_flags, uint64_t R, uint32_t *__restrict__ is_multi, uint8_t *__restrict__ has_counts) {
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < R; r += (uint64_t)gridDim.x * BLOCK) {
+        is_multi[r] = (row_flags[r] >> 2) & 1u;
+        has_counts[r] = row_flags[r] & 1u;
+    }
+}
+// multi_before[r] = multicluster rows before row r in the batch: the row's place in multi_idx, or r - multi_before[r] in unique_idx (ids local to the cluster)
+__global__ __launch_bounds__(BLOCK) void row_lists_kernel(const uint8_t *__restrict__ row_flags, const uint32_t *__restrict__ multi_before, const uint32_t *__restrict__ row_cluster,
+                                                           const uint32_t *__restrict__ kmer_off, uint64_t R, uint32_t *__restrict__ unique_idx, uint32_t *__restrict__ multi_idx) {
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < R; r += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t local = (uint32_t)r - kmer_off[row_cluster[r]];
+        if (row_flags[r] & 4) multi_idx[multi_before[r]] = local;
+        else unique_idx[(uint32_t)r - multi_before[r]] = local;
+    }
+}
+
+// ---- shared records of multicluster k-mers (KmerCounter.cpp:607-616): inside a group, walking its clusters in vertex order and each cluster's multi_idx in
+// order, distinct keys are numbered by first occurrence.  The multicluster rows of a group are a contiguous range of multi_idx (its clusters are), in exactly
+// that order, so with m = a row's place in multi_idx: first(m) = the smallest m of the same (group, key) (atomicMin over an open-addressing index: the SLOT an
+// entry gets depends on arrival, the minimum does not), number(m) = first occurrences before first(m) in the group (a prefix sum). ----
+__global__ __launch_bounds__(BLOCK) void shared_index_kernel(const uint32_t *__restrict__ multi_idx, const uint32_t *__restrict__ multi_off, const uint32_t *__restrict__ kmer_off,
+                                                              const uint32_t *__restrict__ cluster_group, uint32_t C, const uint64_t *__restrict__ row_key, uint32_t M,
+                                                              uint64_t *__restrict__ klo, uint64_t *__restrict__ khi, uint32_t *__restrict__ ktag, uint32_t *__restrict__ kstate,
+                                                              uint32_t *__restrict__ kfirst, uint64_t mask, uint32_t *__restrict__ item_slot, uint32_t *__restrict__ item_row) {
+    for (uint32_t m = blockIdx.x * BLOCK + threadIdx.x; m < M; m += gridDim.x * BLOCK) {
+        uint32_t lo = 0, hi = C;   // last cluster with multi_off[c] <= m (empty clusters repeat an offset: the last one is the owner)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (multi_off[mid] <= m) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t row = kmer_off[lo] + multi_idx[m];
+        const uint64_t slot = index_insert(klo, khi, ktag, kstate, mask, row_key[2 * (uint64_t)row], row_key[2 * (uint64_t)row + 1], cluster_group[lo]);
+        atomicMin(&kfirst[slot], m);
+        item_slot[m] = (uint32_t)slot;
+        item_row[m] = row;
+    }
+}
+__global__ __launch_bounds__(BLOCK) void shared_first_kernel(const uint32_t *__restrict__ item_slot, const uint32_t *__restrict__ kfirst, uint32_t M, uint32_t *__restrict__ is_first) {
+    for (uint32_t m = blockIdx.x * BLOCK + threadIdx.x; m < M; m += gridDim.x * BLOCK) is_first[m] = kfirst[item_slot[m]] == m ? 1u : 0u;
+}
+__global__ __launch_bounds__(BLOCK) void shared_number_kernel(const uint32_t *__restrict__ item_slot, const uint32_t *__restrict__ item_row, const uint32_t *__restrict__ kfirst,
+                                                               const uint32_t *__restrict__ ktag, const uint32_t *__restrict__ firsts_before,
+                                                               const uint32_t *__restrict__ group_m0, uint32_t M, int32_t *__restrict__ kmer_shared) {
+    for (uint32_t m = blockIdx.x * BLOCK + threadIdx.x; m < M; m += gridDim.x * BLOCK) {
+        const uint32_t slot = item_slot[m];
+        kmer_shared[item_row[m]] = (int32_t)(firsts_before[kfirst[slot]] - firsts_before[group_m0[ktag[slot]]]);
+    }
+}
+__global__ __launch_bounds__(BLOCK) void gather_u32_idx32_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ idx, uint32_t n, uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) out[i] = in[idx[i]];
 }
 
 __global__ __launch_bounds__(BLOCK) void gather_u32_kernel(const uint32_t *__restrict__ in, const uint64_t *__restrict__ idx, uint32_t n, uint32_t *__restrict__ out) {
@@ -645,6 +861,24 @@ struct bt_paths {
     std::vector<uint8_t> mult, has_counts, counts, ic;
     std::vector<uint64_t> key;
     std::vector<uint16_t> kv_var, hap_allele, nestdep_var;
+    // candidates result (device): the per-row / per-entry arrays of bt_paths_candidates_device, until a source takes them or the handle goes
+    bool cand_on_device = false;
+    std::vector<void *> cand_owned;
+    uint64_t R = 0, nnz = 0, kv_words = 0, mult_bytes = 0, num_unique = 0, num_multi = 0;
+    std::vector<uint32_t> cluster_kv0;   // [C+1] first incidence entry of each cluster
+    uint8_t *d_mult = nullptr, *d_has_counts = nullptr, *d_counts = nullptr, *d_ic = nullptr;
+    uint64_t *d_key = nullptr;
+    uint32_t *d_kv_off = nullptr, *d_kv_bits = nullptr, *d_unique_idx = nullptr, *d_multi_idx = nullptr;
+    uint16_t *d_kv_var = nullptr;
+    void drop_device_candidates() {
+        for (void *q : cand_owned) (void)hipFree(q);
+        cand_owned.clear();
+        cand_on_device = false;
+        d_mult = d_has_counts = d_counts = d_ic = nullptr;
+        d_key = nullptr;
+        d_kv_off = d_kv_bits = d_unique_idx = d_multi_idx = nullptr;
+        d_kv_var = nullptr;
+    }
 };
 
 namespace {
@@ -920,6 +1154,7 @@ int bt_paths_destroy(bt_paths *p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void *q : p->owned) (void)hipFree(q);
+    p->drop_device_candidates();
     delete p;
     return BT_OK;
 }
@@ -1128,195 +1363,74 @@ int bt_paths_classify(bt_paths *p, bt_table *table, bt_bloom *multigroup_bloom, 
     return BT_OK;
 }
 
-int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes) {
+}  // extern "C"
+
+namespace {
+
+// exclusive prefix sum of n words on the context's stream: d_out[0 .. n], d_out[n] = *total.  The totals of the 1024-element blocks pass through the host
+// (n / 1024 words).  An error when the total does not fit 32 bits: every offset of the batch layout is a uint32_t.
+int exclusive_scan(bt_ctx *ctx, const uint32_t *d_in, uint64_t n, uint32_t *d_out, uint64_t *total, const char *what, std::vector<void *> &tmp) {
+    hipStream_t st = ctx->stream;
+    const uint64_t nblk = (n + BLOCK * 4 - 1) / (BLOCK * 4);
+    uint64_t sum = 0;
+    if (nblk) {
+        uint32_t *d_sums = nullptr;
+        const int rc = dev_alloc(&d_sums, nblk, tmp);
+        if (rc != BT_OK) return rc;
+        hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nblk), dim3(BLOCK), 0, st, d_in, n, d_out, d_sums);
+        BT_CHECK_LAUNCH();
+        std::vector<uint32_t> sums(nblk);
+        BT_HIP(hipMemcpyAsync(sums.data(), d_sums, nblk * 4, hipMemcpyDeviceToHost, st));
+        BT_HIP(hipStreamSynchronize(st));
+        for (uint64_t i = 0; i < nblk; ++i) {
+            const uint32_t v = sums[i];
+            sums[i] = (uint32_t)sum;
+            sum += v;
+        }
+        if (sum >= (1ull << 32)) return fail(std::string("bt_paths_candidates: more than 2^32 ") + what + " in one batch: a 32-bit offset of the batch layout would overflow (split the unit)");
+        BT_HIP(hipMemcpyAsync(d_sums, sums.data(), nblk * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblk), dim3(BLOCK), 0, st, d_out, n, d_sums);
+        BT_CHECK_LAUNCH();
+    }
+    const uint32_t last = (uint32_t)sum;
+    BT_HIP(hipMemcpyAsync(d_out + n, &last, 4, hipMemcpyHostToDevice, st));
+    BT_HIP(hipStreamSynchronize(st));
+    *total = sum;
+    return BT_OK;
+}
+
+uint32_t env_threshold(const char *name, uint32_t dflt) {
+    const char *e = getenv(name);
+    if (!e) return dflt;
+    const long v = atol(e);
+    return (uint32_t)std::min<long>(std::max<long>(v, 0), dflt);   // (tests lower the thresholds so that small units reach every path; never above the kernels' limits)
+}
+
+// getHaplotypeCandidates for every cluster: the per-row / per-entry arrays are built and LEFT on the device (p->d_*), the O(C) arrays and what the host graph
+// walk gives (haplotype alleles, nested clusters) in p's host vectors
+int candidates_build(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes) {
     if (!p || !table || !sizes) return fail("bt_paths_candidates: null argument");
     if (table->k != p->k) return fail("bt_paths_candidates: k mismatch");
     BT_HIP(hipSetDevice(p->ctx->device));
+    p->have_candidates = false;
+    p->drop_device_candidates();
     int rc = build_index(p);
     if (rc != BT_OK) return rc;
     hipStream_t st = p->ctx->stream;
     const unsigned maxb = p->ctx->num_cu * 16;
     const uint32_t C = p->C, S = table->num_samples;
     p->S = S;
-    std::vector<void *> tmp;
-    auto cleanup = [&]() {
-        for (void *q : tmp) (void)hipFree(q);
-    };
-#define TRYC(x)                  \
-    do {                         \
-        const int _rc = (x);     \
-        if (_rc != BT_OK) {      \
-            cleanup();           \
-            return _rc;          \
-        }                        \
-    } while (0)
-#define HIPC(call)                                                                      \
-    do {                                                                                \
-        hipError_t _e = (call);                                                         \
-        if (_e != hipSuccess) {                                                         \
-            cleanup();                                                                  \
-            return bt::fail(std::string(#call) + ": " + hipGetErrorString(_e));         \
-        }                                                                               \
-    } while (0)
-    // 1. table records of the distinct (cluster, k-mer) entries
-    TRYC(bt_table_find_batch(table, p->d_list_kmers, p->n_list, p->d_list_slots));
-    hipLaunchKernelGGL(record_kernel, dim3(grid_for(p->n_list, BLOCK, maxb)), dim3(BLOCK), 0, st, table->v, p->d_list_slots, p->n_list, p->d_list_flags);
-    // 2. row numbering = prefix sum over first-occurrence flags in text order
-    uint32_t *d_flag = nullptr, *d_rowpos = nullptr, *d_sums = nullptr, *d_a_row = nullptr;
-    const uint64_t nblk = (p->L + BLOCK * 4 - 1) / (BLOCK * 4);
-    TRYC(dev_alloc(&d_flag, p->L, tmp));
-    TRYC(dev_alloc(&d_rowpos, p->L + 1, tmp));
-    TRYC(dev_alloc(&d_sums, nblk, tmp));
-    TRYC(dev_alloc(&d_a_row, p->A.mask + 1, tmp));
-    hipLaunchKernelGGL(first_flag_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, p->L, d_flag);
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nblk), dim3(BLOCK), 0, st, d_flag, p->L, d_rowpos, d_sums);
-    std::vector<uint32_t> sums(nblk);
-    HIPC(hipMemcpyAsync(sums.data(), d_sums, nblk * 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    uint64_t total_rows = 0;
-    for (uint64_t i = 0; i < nblk; ++i) {
-        const uint32_t v = sums[i];
-        sums[i] = (uint32_t)total_rows;
-        total_rows += v;
-    }
-    if (total_rows >= (1ull << 32)) {
-        cleanup();
-        return fail("bt_paths_candidates: more than 2^32 k-mer rows in one batch");
-    }
-    HIPC(hipMemcpyAsync(d_sums, sums.data(), nblk * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblk), dim3(BLOCK), 0, st, d_rowpos, p->L, d_sums);
-    // kmer_off[c] = rows before the cluster's first text position
-    p->kmer_off.assign(C + 1, 0);
-    {
-        // rows before the first text position of every cluster (d_rowpos has L + 1 entries: the last one is the total)
-        uint64_t *d_idx = nullptr;
-        uint32_t *d_out = nullptr;
-        TRYC(dev_alloc(&d_idx, C, tmp));
-        TRYC(dev_alloc(&d_out, C, tmp));
-        HIPC(hipMemcpyAsync(d_rowpos + p->L, &total_rows, 4, hipMemcpyHostToDevice, st));
-        HIPC(hipMemcpyAsync(d_idx, p->cluster_text0.data(), (size_t)C * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(gather_u32_kernel, dim3((C + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d_rowpos, d_idx, C, d_out);
-        HIPC(hipMemcpyAsync(p->kmer_off.data(), d_out, (size_t)C * 4, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    p->kmer_off[C] = (uint32_t)total_rows;
-    const uint64_t R = total_rows;
-    // 3. per row: key + table record
-    uint64_t *d_row_key = nullptr;
-    uint8_t *d_row_flags = nullptr, *d_row_counts = nullptr, *d_row_ic = nullptr;
-    TRYC(dev_alloc(&d_row_key, 2 * R, tmp));
-    TRYC(dev_alloc(&d_row_flags, R, tmp));
-    TRYC(dev_alloc(&d_row_counts, R * S, tmp));
-    TRYC(dev_alloc(&d_row_ic, 2 * R, tmp));
-    hipLaunchKernelGGL(rows_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, table->v, p->d_valid, p->d_pos_slot_a, d_flag, d_rowpos, p->d_list_slots,
-                       p->d_list_flags, p->L, S, d_a_row, d_row_key, d_row_flags, d_row_counts, d_row_ic);
-    // 4. multiplicity matrix
-    std::vector<uint64_t> mult0(C + 1, 0);
-    for (uint32_t c = 0; c < C; ++c) mult0[c + 1] = mult0[c] + (uint64_t)(p->kmer_off[c + 1] - p->kmer_off[c]) * p->num_paths[c];
-    uint8_t *d_mult = nullptr;
-    uint32_t *d_row0 = nullptr, *d_h = nullptr, *d_over = nullptr;
-    uint64_t *d_mult0 = nullptr;
-    TRYC(dev_alloc(&d_mult, mult0[C], tmp));
-    TRYC(dev_alloc(&d_row0, C + 1, tmp));
-    TRYC(dev_alloc(&d_h, C, tmp));
-    TRYC(dev_alloc(&d_mult0, C + 1, tmp));
-    TRYC(dev_alloc(&d_over, 1, tmp));
-    HIPC(hipMemsetAsync(d_mult, 0, std::max<uint64_t>(mult0[C], 1), st));
-    HIPC(hipMemsetAsync(d_over, 0, 4, st));
-    HIPC(hipMemcpyAsync(d_row0, p->kmer_off.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_h, p->num_paths.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(d_mult0, mult0.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(mult_kernel, dim3(grid_for(p->B.mask + 1, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->B, p->d_list_flags, d_a_row, p->d_path_cluster,
-                       p->d_path_local, d_row0, d_mult0, d_h, d_mult, d_over);
-    // 5. (row, variant, path) triples
-    unsigned long long *d_cursor = nullptr;
-    TRYC(dev_alloc(&d_cursor, 1, tmp));
-    HIPC(hipMemsetAsync(d_cursor, 0, 8, st));
-    hipLaunchKernelGGL(triples_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, d_a_row, p->d_pos_path,
-                       p->d_pos_nt, p->d_path_local, p->d_iv_off, p->d_iv, p->L, d_cursor, (uint64_t *)nullptr);
-    unsigned long long ntrip = 0;
-    HIPC(hipMemcpyAsync(&ntrip, d_cursor, 8, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    uint64_t *d_trip = nullptr;
-    TRYC(dev_alloc(&d_trip, ntrip, tmp));
-    HIPC(hipMemsetAsync(d_cursor, 0, 8, st));
-    hipLaunchKernelGGL(triples_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, d_a_row, p->d_pos_path,
-                       p->d_pos_nt, p->d_path_local, p->d_iv_off, p->d_iv, p->L, d_cursor, d_trip);
-    HIPC(hipGetLastError());
-    // sort the triples by (row, variant, path) on the device (rocPRIM radix sort over the 64-bit keys)
-    if (ntrip > 1) {
-        uint64_t *d_sorted = nullptr;
-        TRYC(dev_alloc(&d_sorted, ntrip, tmp));
-        size_t tmp_bytes = 0;
-        HIPC(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_trip, d_sorted, (size_t)ntrip, 0, 64, st));
-        uint8_t *d_tmp = nullptr;
-        TRYC(dev_alloc(&d_tmp, tmp_bytes, tmp));
-        HIPC(rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_trip, d_sorted, (size_t)ntrip, 0, 64, st));
-        d_trip = d_sorted;
-    }
-    // 6. fetch and assemble on the host
-    std::vector<uint64_t> trip(ntrip);
-    std::vector<uint8_t> row_flags(R);
-    uint32_t over = 0;
-    p->key.resize(2 * R);
-    p->counts.resize(R * S);
-    p->ic.resize(2 * R);
-    p->mult.resize(mult0[C]);
-    HIPC(hipStreamSynchronize(st));
-    if (ntrip) HIPC(hipMemcpy(trip.data(), d_trip, ntrip * 8, hipMemcpyDeviceToHost));
-    if (R) {
-        HIPC(hipMemcpy(row_flags.data(), d_row_flags, R, hipMemcpyDeviceToHost));
-        HIPC(hipMemcpy(p->key.data(), d_row_key, 2 * R * 8, hipMemcpyDeviceToHost));
-        HIPC(hipMemcpy(p->counts.data(), d_row_counts, R * S, hipMemcpyDeviceToHost));
-        HIPC(hipMemcpy(p->ic.data(), d_row_ic, 2 * R, hipMemcpyDeviceToHost));
-    }
-    if (mult0[C]) HIPC(hipMemcpy(p->mult.data(), d_mult, mult0[C], hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost));
-    cleanup();
-#undef TRYC
-#undef HIPC
-    if (over) return fail("bt_paths_candidates: a path k-mer occurs more than 127 times on one haplotype (the reference asserts <= 127)");
-    // ---- assembly on the host, on several threads: every thread takes a range of clusters (their rows are a contiguous range of rows, their triples a
-    // contiguous range of the sorted triples), builds its pieces of the lists with offsets relative to the piece, and the pieces are concatenated in
-    // cluster order with the offsets rebased.  (One thread did all of this in rounds 1-3: 0.37 s for 175 000 clusters, more than the unit's sampling launch.)
+    // ---- the host half (haplotype alleles, nested clusters, nested dependency map: O(paths x vertices), reads no k-mer data) on host threads of its own
+    // while the device kernels are in flight; every thread takes a range of clusters and the pieces are concatenated in cluster order afterwards
     struct Piece {
-        std::vector<uint32_t> unique_off, unique_idx, multi_off, multi_idx, kv_off, kv_bits, hapnest_off, hapnest_idx, nestdep_off, nestdep_cluster, nestdep_var_off;
-        std::vector<uint16_t> kv_var, hap_allele, nestdep_var;
+        std::vector<uint32_t> hapnest_off, hapnest_idx, nestdep_off, nestdep_cluster, nestdep_var_off;
+        std::vector<uint16_t> hap_allele, nestdep_var;
     };
     const unsigned T = host_threads(C);
     std::vector<Piece> piece(T);
-    p->has_counts.resize(R);
     auto work = [&](unsigned t) {
         Piece &q = piece[t];
         const uint32_t c0 = (uint32_t)((uint64_t)C * t / T), c1 = (uint32_t)((uint64_t)C * (t + 1) / T);
-        const uint64_t r0 = p->kmer_off[c0], r1 = p->kmer_off[c1];
-        for (uint64_t r = r0; r < r1; ++r) p->has_counts[r] = row_flags[r] & 1;
-        // unique / multicluster row lists, in row (= first-seen) order
-        for (uint32_t c = c0; c < c1; ++c) {
-            for (uint32_t r = p->kmer_off[c]; r < p->kmer_off[c + 1]; ++r) (row_flags[r] & 4 ? q.multi_idx : q.unique_idx).push_back(r - p->kmer_off[c]);
-            q.unique_off.push_back((uint32_t)q.unique_idx.size());
-            q.multi_off.push_back((uint32_t)q.multi_idx.size());
-        }
-        // variant_haplotype_indices: the triples arrive sorted by (row, variant, path); entries of a row ordered by variant
-        uint64_t ti = (uint64_t)(std::lower_bound(trip.begin(), trip.end(), r0 << 32) - trip.begin());
-        for (uint32_t c = c0; c < c1; ++c) {
-            const uint32_t HW = (p->num_paths[c] + 31) / 32;
-            for (uint64_t r = p->kmer_off[c]; r < p->kmer_off[c + 1]; ++r) {
-                while (ti < ntrip && (trip[ti] >> 32) == r) {
-                    const uint16_t var = (uint16_t)((trip[ti] >> 16) & 0xffff);
-                    q.kv_var.push_back(var);
-                    const size_t w0 = q.kv_bits.size();
-                    q.kv_bits.resize(w0 + HW, 0);
-                    while (ti < ntrip && (trip[ti] >> 32) == r && (uint16_t)((trip[ti] >> 16) & 0xffff) == var) {
-                        const uint32_t path = (uint32_t)(trip[ti] & 0xffff);
-                        q.kv_bits[w0 + (path >> 5)] |= 1u << (path & 31);
-                        ++ti;
-                    }
-                }
-                q.kv_off.push_back((uint32_t)q.kv_var.size());
-            }
-        }
-        // haplotypes and the nested dependency map (O(paths x vertices))
         std::vector<Interval> iv_dummy;
         std::vector<uint16_t> alleles;
         std::vector<uint32_t> nested;
@@ -1344,12 +1458,242 @@ int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes 
             q.nestdep_off.push_back((uint32_t)q.nestdep_cluster.size());
         }
     };
+    std::exception_ptr walk_error;
+    std::thread walker;
+    struct Joiner {
+        std::thread &t;
+        ~Joiner() {
+            if (t.joinable()) t.join();
+        }
+    } joiner{walker};
+    auto walk_all = [&]() {
+        try {
+            if (C) run_on_threads(T, work);
+        } catch (...) {
+            walk_error = std::current_exception();
+        }
+    };
     try {
-        if (C) run_on_threads(T, work);
-    } catch (const std::exception &e) {   // (a worker ran out of memory on its pieces: an error of the call, not of the process)
-        return fail(std::string("bt_paths_candidates: ") + e.what());
+        walker = std::thread(walk_all);
+    } catch (...) {   // (no thread could be started: the walk runs here, before the device work)
+        walk_all();
     }
-    // concatenation: `idx` lists appended as they are, `off` lists (cumulative ends, relative to the piece) rebased on what precedes the piece
+
+    std::vector<void *> tmp, keep;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(st);
+        for (void *q : tmp) (void)hipFree(q);
+        for (void *q : keep) (void)hipFree(q);
+        tmp.clear();
+        keep.clear();
+        p->drop_device_candidates();   // (nothing owned yet: forgets the pointers)
+    };
+#define TRYC(x)                  \
+    do {                         \
+        const int _rc = (x);     \
+        if (_rc != BT_OK) {      \
+            cleanup();           \
+            return _rc;          \
+        }                        \
+    } while (0)
+#define HIPC(call)                                                                      \
+    do {                                                                                \
+        hipError_t _e = (call);                                                         \
+        if (_e != hipSuccess) {                                                         \
+            cleanup();                                                                  \
+            return bt::fail(std::string(#call) + ": " + hipGetErrorString(_e));         \
+        }                                                                               \
+    } while (0)
+    // 1. table records of the distinct (cluster, k-mer) entries
+    TRYC(bt_table_find_batch(table, p->d_list_kmers, p->n_list, p->d_list_slots));
+    hipLaunchKernelGGL(record_kernel, dim3(grid_for(p->n_list, BLOCK, maxb)), dim3(BLOCK), 0, st, table->v, p->d_list_slots, p->n_list, p->d_list_flags);
+    // 2. row numbering = prefix sum over first-occurrence flags in text order
+    uint32_t *d_flag = nullptr, *d_rowpos = nullptr, *d_a_row = nullptr;
+    TRYC(dev_alloc(&d_flag, p->L, tmp));
+    TRYC(dev_alloc(&d_rowpos, p->L + 1, tmp));
+    TRYC(dev_alloc(&d_a_row, p->A.mask + 1, tmp));
+    hipLaunchKernelGGL(first_flag_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, p->L, d_flag);
+    uint64_t total_rows = 0;
+    TRYC(exclusive_scan(p->ctx, d_flag, p->L, d_rowpos, &total_rows, "k-mer rows", tmp));
+    // kmer_off[c] = rows before the cluster's first text position (d_rowpos has L + 1 entries: the last one is the total)
+    p->kmer_off.assign(C + 1, 0);
+    uint32_t *d_c32 = nullptr;   // [C+1] gather results
+    {
+        uint64_t *d_idx = nullptr;
+        TRYC(dev_alloc(&d_idx, C, tmp));
+        TRYC(dev_alloc(&d_c32, C + 1, tmp));
+        HIPC(hipMemcpyAsync(d_idx, p->cluster_text0.data(), (size_t)C * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(gather_u32_kernel, dim3((C + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d_rowpos, d_idx, C, d_c32);
+        HIPC(hipMemcpyAsync(p->kmer_off.data(), d_c32, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    p->kmer_off[C] = (uint32_t)total_rows;
+    const uint64_t R = total_rows;
+    // 3. per row: key + table record + its cluster
+    uint8_t *d_row_flags = nullptr;
+    uint32_t *d_row_cluster = nullptr;
+    TRYC(dev_alloc(&p->d_key, 2 * R, keep));
+    TRYC(dev_alloc(&p->d_counts, R * S, keep));
+    TRYC(dev_alloc(&p->d_ic, 2 * R, keep));
+    TRYC(dev_alloc(&p->d_has_counts, R, keep));
+    TRYC(dev_alloc(&d_row_flags, R, tmp));
+    TRYC(dev_alloc(&d_row_cluster, R, tmp));
+    hipLaunchKernelGGL(rows_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, table->v, p->d_valid, p->d_pos_slot_a, d_flag, d_rowpos, p->d_list_slots,
+                       p->d_list_flags, p->d_pos_path, p->d_path_cluster, p->L, S, d_a_row, p->d_key, d_row_flags, p->d_counts, p->d_ic, d_row_cluster);
+    // 4. multiplicity matrix
+    std::vector<uint64_t> mult0(C + 1, 0);
+    for (uint32_t c = 0; c < C; ++c) mult0[c + 1] = mult0[c] + (uint64_t)(p->kmer_off[c + 1] - p->kmer_off[c]) * p->num_paths[c];
+    uint32_t *d_row0 = nullptr, *d_h = nullptr, *d_over = nullptr;
+    uint64_t *d_mult0 = nullptr;
+    TRYC(dev_alloc(&p->d_mult, mult0[C], keep));
+    TRYC(dev_alloc(&d_row0, C + 1, tmp));
+    TRYC(dev_alloc(&d_h, C, tmp));
+    TRYC(dev_alloc(&d_mult0, C + 1, tmp));
+    TRYC(dev_alloc(&d_over, 1, tmp));
+    HIPC(hipMemsetAsync(p->d_mult, 0, std::max<uint64_t>(mult0[C], 1), st));
+    HIPC(hipMemsetAsync(d_over, 0, 4, st));
+    HIPC(hipMemcpyAsync(d_row0, p->kmer_off.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_h, p->num_paths.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_mult0, mult0.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mult_kernel, dim3(grid_for(p->B.mask + 1, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->B, p->d_list_flags, d_a_row, p->d_path_cluster,
+                       p->d_path_local, d_row0, d_mult0, d_h, p->d_mult, d_over);
+    // 5. (row, variant, path) triples, each scattered into its row's segment: count per row, scan, write
+    unsigned long long *d_cursor = nullptr;
+    uint32_t *d_row_cnt = nullptr, *d_row_off = nullptr, *d_trip = nullptr;
+    TRYC(dev_alloc(&d_cursor, 1, tmp));
+    TRYC(dev_alloc(&d_row_cnt, R, tmp));
+    TRYC(dev_alloc(&d_row_off, R + 1, tmp));
+    HIPC(hipMemsetAsync(d_cursor, 0, 8, st));
+    HIPC(hipMemsetAsync(d_row_cnt, 0, std::max<uint64_t>(R, 1) * 4, st));
+    hipLaunchKernelGGL(triples_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, d_a_row, p->d_pos_path,
+                       p->d_pos_nt, p->d_path_local, p->d_iv_off, p->d_iv, p->L, d_cursor, (const uint32_t *)nullptr, d_row_cnt, (uint32_t *)nullptr);
+    unsigned long long ntrip = 0;
+    HIPC(hipMemcpyAsync(&ntrip, d_cursor, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (ntrip >= (1ull << 32)) {
+        cleanup();
+        return fail("bt_paths_candidates: more than 2^32 (k-mer, variant, haplotype) incidences in one batch: a 32-bit offset of the batch layout would overflow (split the unit)");
+    }
+    uint64_t ntrip2 = 0;
+    TRYC(exclusive_scan(p->ctx, d_row_cnt, R, d_row_off, &ntrip2, "incidences", tmp));
+    TRYC(dev_alloc(&d_trip, ntrip, tmp));
+    HIPC(hipMemsetAsync(d_row_cnt, 0, std::max<uint64_t>(R, 1) * 4, st));
+    hipLaunchKernelGGL(triples_kernel, dim3(grid_for(p->L, BLOCK, maxb)), dim3(BLOCK), 0, st, p->A, p->d_valid, p->d_pos_slot_a, p->d_list_flags, d_a_row, p->d_pos_path,
+                       p->d_pos_nt, p->d_path_local, p->d_iv_off, p->d_iv, p->L, d_cursor, d_row_off, d_row_cnt, d_trip);
+    HIPC(hipGetLastError());
+    // 6. entries per row (distinct variants), rows longer than a lane's share listed for the wavefront / workgroup kernels
+    const uint32_t lane_max = env_threshold("BT_PATHS_ROW_LANE_MAX", ROW_LANE_MAX), wave_max = std::max(lane_max, env_threshold("BT_PATHS_ROW_WAVE_MAX", ROW_WAVE_MAX));
+    const uint32_t wave_cap = (uint32_t)(ntrip / (lane_max + 1ull)) + 1u, block_cap = (uint32_t)(ntrip / (wave_max + 1ull)) + 1u;   // a listed row has more triples than the threshold
+    uint32_t *d_row_nnz = nullptr, *d_wave_list = nullptr, *d_block_list = nullptr, *d_list_n = nullptr;
+    TRYC(dev_alloc(&d_row_nnz, R, tmp));
+    TRYC(dev_alloc(&d_wave_list, wave_cap, tmp));
+    TRYC(dev_alloc(&d_block_list, block_cap, tmp));
+    TRYC(dev_alloc(&d_list_n, 2, tmp));
+    TRYC(dev_alloc(&p->d_kv_off, R + 1, keep));
+    HIPC(hipMemsetAsync(d_list_n, 0, 8, st));
+    RowJob J{};
+    J.trip = d_trip;
+    J.row_off = d_row_off;
+    J.row_nnz = d_row_nnz;
+    J.row_cluster = d_row_cluster;
+    J.cluster_h = d_h;
+    J.write = 0;
+    hipLaunchKernelGGL(row_entries_lane_kernel, dim3(grid_for(R, BLOCK, maxb)), dim3(BLOCK), 0, st, J, R, lane_max, wave_max, d_wave_list, wave_cap, d_block_list, block_cap, d_list_n);
+    uint32_t list_n[2] = {0, 0};
+    HIPC(hipMemcpyAsync(list_n, d_list_n, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (list_n[0] > wave_cap || list_n[1] > block_cap) {
+        cleanup();
+        return fail("bt_paths_candidates: internal error: more long rows than their triples allow");
+    }
+    auto long_rows = [&]() {
+        if (list_n[0]) hipLaunchKernelGGL(row_entries_wave_kernel, dim3(grid_for(list_n[0], BLOCK / 64, maxb)), dim3(BLOCK), 0, st, J, d_wave_list, list_n[0]);
+        if (list_n[1]) hipLaunchKernelGGL(row_entries_block_kernel, dim3(grid_for(list_n[1], 1, maxb)), dim3(BLOCK), 0, st, J, d_block_list, list_n[1]);
+    };
+    long_rows();
+    HIPC(hipGetLastError());
+    uint64_t nnz = 0;
+    TRYC(exclusive_scan(p->ctx, d_row_nnz, R, p->d_kv_off, &nnz, "incidence entries", tmp));
+    // 7. where each cluster's entries and bitset words start (O(C), host), then the write pass
+    uint32_t *d_ckv0 = nullptr;
+    uint64_t *d_ckvb = nullptr;
+    TRYC(dev_alloc(&d_ckv0, C + 1, tmp));
+    TRYC(dev_alloc(&d_ckvb, C + 1, tmp));
+    p->cluster_kv0.assign(C + 1, 0);
+    hipLaunchKernelGGL(gather_u32_idx32_kernel, dim3((C + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, p->d_kv_off, d_row0, C + 1, d_ckv0);
+    HIPC(hipMemcpyAsync(p->cluster_kv0.data(), d_ckv0, (size_t)(C + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    std::vector<uint64_t> kvb(C + 1, 0);
+    for (uint32_t c = 0; c < C; ++c) kvb[c + 1] = kvb[c] + (uint64_t)(p->cluster_kv0[c + 1] - p->cluster_kv0[c]) * ((p->num_paths[c] + 31) / 32);
+    HIPC(hipMemcpyAsync(d_ckvb, kvb.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, st));
+    TRYC(dev_alloc(&p->d_kv_var, nnz, keep));
+    TRYC(dev_alloc(&p->d_kv_bits, kvb[C], keep));
+    HIPC(hipMemsetAsync(p->d_kv_bits, 0, std::max<uint64_t>(kvb[C], 1) * 4, st));
+    J.kv_off = p->d_kv_off;
+    J.cluster_kv0 = d_ckv0;
+    J.cluster_kvb = d_ckvb;
+    J.kv_var = p->d_kv_var;
+    J.kv_bits = p->d_kv_bits;
+    J.write = 1;
+    hipLaunchKernelGGL(row_entries_lane_kernel, dim3(grid_for(R, BLOCK, maxb)), dim3(BLOCK), 0, st, J, R, lane_max, wave_max, d_wave_list, wave_cap, d_block_list, block_cap, d_list_n);
+    long_rows();
+    HIPC(hipGetLastError());
+    // 8. kmer_has_counts and the unique / multicluster row lists (stable: a row's place is the number of rows of its kind before it)
+    uint32_t *d_is_multi = d_row_nnz, *d_mbefore = nullptr;
+    TRYC(dev_alloc(&d_mbefore, R + 1, tmp));
+    hipLaunchKernelGGL(row_flags_kernel, dim3(grid_for(R, BLOCK, maxb)), dim3(BLOCK), 0, st, d_row_flags, R, d_is_multi, p->d_has_counts);
+    uint64_t num_multi = 0;
+    TRYC(exclusive_scan(p->ctx, d_is_multi, R, d_mbefore, &num_multi, "multicluster rows", tmp));
+    p->multi_off.assign(C + 1, 0);
+    p->unique_off.assign(C + 1, 0);
+    hipLaunchKernelGGL(gather_u32_idx32_kernel, dim3((C + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d_mbefore, d_row0, C + 1, d_c32);
+    HIPC(hipMemcpyAsync(p->multi_off.data(), d_c32, (size_t)(C + 1) * 4, hipMemcpyDeviceToHost, st));
+    TRYC(dev_alloc(&p->d_unique_idx, R - num_multi, keep));
+    TRYC(dev_alloc(&p->d_multi_idx, num_multi, keep));
+    hipLaunchKernelGGL(row_lists_kernel, dim3(grid_for(R, BLOCK, maxb)), dim3(BLOCK), 0, st, d_row_flags, d_mbefore, d_row_cluster, d_row0, R, p->d_unique_idx, p->d_multi_idx);
+    HIPC(hipGetLastError());
+    uint32_t over = 0;
+    HIPC(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    for (uint32_t c = 0; c <= C; ++c) p->unique_off[c] = p->kmer_off[c] - p->multi_off[c];
+    if (getenv("BT_PATHS_DEBUG")) {   // which kernel took how many rows, and the triples-per-row distribution (bin b: rows with 2^(b-1) < triples <= 2^b; bin 0: none or one)
+        std::vector<uint32_t> off(R + 1, 0);
+        HIPC(hipMemcpy(off.data(), d_row_off, (R + 1) * 4, hipMemcpyDeviceToHost));
+        uint64_t hist[33] = {0};
+        uint32_t longest = 0;
+        for (uint64_t r = 0; r < R; ++r) {
+            const uint32_t n = off[r + 1] - off[r];
+            longest = std::max(longest, n);
+            unsigned b = 0;
+            while ((1ull << b) < n) ++b;
+            ++hist[b];
+        }
+        std::string h;
+        for (unsigned b = 0; b < 33; ++b)
+            if (hist[b]) h += " 2^" + std::to_string(b) + ":" + std::to_string(hist[b]);
+        fprintf(stderr, "bt_paths_candidates: rows=%llu triples=%llu entries=%llu lane_rows=%llu wave_rows=%u block_rows=%u lane_max=%u wave_max=%u longest_row=%u triples_per_row%s\n",
+                (unsigned long long)R, ntrip, (unsigned long long)nnz, (unsigned long long)(R - list_n[0] - list_n[1]), list_n[0], list_n[1], lane_max, wave_max, longest, h.c_str());
+    }
+    for (void *q : tmp) (void)hipFree(q);
+    tmp.clear();
+    if (over) {
+        cleanup();
+        return fail("bt_paths_candidates: a path k-mer occurs more than 127 times on one haplotype (the reference asserts <= 127)");
+    }
+    // ---- the host half: join, concatenate the pieces in cluster order (`off` lists hold cumulative ends relative to the piece: rebased on what precedes it)
+    if (walker.joinable()) walker.join();
+    if (walk_error) {
+        cleanup();
+        try {
+            std::rethrow_exception(walk_error);
+        } catch (const std::exception &e) {   // (a worker ran out of memory on its pieces: an error of the call, not of the process)
+            return fail(std::string("bt_paths_candidates: ") + e.what());
+        } catch (...) {
+            return fail("bt_paths_candidates: host walk failed");
+        }
+    }
+#undef TRYC
+#undef HIPC
     auto cat = [&](auto &dst, auto Piece::*m) {
         size_t n = 0;
         for (auto &q : piece) n += (q.*m).size();
@@ -1369,28 +1713,38 @@ int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes 
             base += (uint32_t)(q.*idx).size();
         }
     };
-    cat_off(p->unique_off, &Piece::unique_off, &Piece::unique_idx);
-    cat_off(p->multi_off, &Piece::multi_off, &Piece::multi_idx);
-    cat_off(p->kv_off, &Piece::kv_off, &Piece::kv_var);
-    cat_off(p->hapnest_off, &Piece::hapnest_off, &Piece::hapnest_idx);
-    cat_off(p->nestdep_off, &Piece::nestdep_off, &Piece::nestdep_cluster);
-    cat_off(p->nestdep_var_off, &Piece::nestdep_var_off, &Piece::nestdep_var);
-    cat(p->unique_idx, &Piece::unique_idx);
-    cat(p->multi_idx, &Piece::multi_idx);
-    cat(p->kv_var, &Piece::kv_var);
-    cat(p->kv_bits, &Piece::kv_bits);
-    cat(p->hap_allele, &Piece::hap_allele);
-    cat(p->hapnest_idx, &Piece::hapnest_idx);
-    cat(p->nestdep_cluster, &Piece::nestdep_cluster);
-    cat(p->nestdep_var, &Piece::nestdep_var);
+    try {
+        cat_off(p->hapnest_off, &Piece::hapnest_off, &Piece::hapnest_idx);
+        cat_off(p->nestdep_off, &Piece::nestdep_off, &Piece::nestdep_cluster);
+        cat_off(p->nestdep_var_off, &Piece::nestdep_var_off, &Piece::nestdep_var);
+        cat(p->hap_allele, &Piece::hap_allele);
+        cat(p->hapnest_idx, &Piece::hapnest_idx);
+        cat(p->nestdep_cluster, &Piece::nestdep_cluster);
+        cat(p->nestdep_var, &Piece::nestdep_var);
+    } catch (const std::exception &e) {
+        cleanup();
+        return fail(std::string("bt_paths_candidates: ") + e.what());
+    }
     piece.clear();
+    for (auto *v : {&p->kv_off, &p->unique_idx, &p->multi_idx, &p->kv_bits}) std::vector<uint32_t>().swap(*v);   // (host copies of an earlier bt_paths_candidates)
+    for (auto *v : {&p->mult, &p->has_counts, &p->counts, &p->ic}) std::vector<uint8_t>().swap(*v);
+    std::vector<uint64_t>().swap(p->key);
+    std::vector<uint16_t>().swap(p->kv_var);
+    p->cand_owned = std::move(keep);
+    p->cand_on_device = true;
     p->have_candidates = true;
+    p->R = R;
+    p->nnz = nnz;
+    p->kv_words = kvb[C];
+    p->mult_bytes = mult0[C];
+    p->num_multi = num_multi;
+    p->num_unique = R - num_multi;
     sizes->rows = R;
-    sizes->mult_bytes = p->mult.size();
-    sizes->nnz = p->kv_var.size();
-    sizes->kv_words = p->kv_bits.size();
-    sizes->num_unique = p->unique_idx.size();
-    sizes->num_multi = p->multi_idx.size();
+    sizes->mult_bytes = p->mult_bytes;
+    sizes->nnz = nnz;
+    sizes->kv_words = p->kv_words;
+    sizes->num_unique = p->num_unique;
+    sizes->num_multi = num_multi;
     sizes->hap_allele = p->hap_allele.size();
     sizes->num_haplotypes = p->num_gpaths;
     sizes->hapnest = p->hapnest_idx.size();
@@ -1399,9 +1753,203 @@ int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes 
     return BT_OK;
 }
 
+}  // namespace
+
+namespace bt {
+
+int paths_device_candidates(bt_paths *p, const char *who, PathsCandidates *out) {
+    if (!p->have_candidates || !p->cand_on_device)
+        return fail(std::string(who) + ": the paths handle holds no candidates on the device (bt_paths_candidates_device has not run, or a source took them)");
+    out->ctx = p->ctx;
+    out->C = p->C;
+    out->S = p->S;
+    out->R = p->R;
+    out->nnz = p->nnz;
+    out->kv_words = p->kv_words;
+    out->mult_bytes = p->mult_bytes;
+    out->num_unique = p->num_unique;
+    out->num_multi = p->num_multi;
+    out->num_paths = p->num_paths.data();
+    out->kmer_off = p->kmer_off.data();
+    out->unique_off = p->unique_off.data();
+    out->multi_off = p->multi_off.data();
+    out->cluster_kv0 = p->cluster_kv0.data();
+    out->hap_kmer_mult = p->d_mult;
+    out->kmer_has_counts = p->d_has_counts;
+    out->kmer_counts = p->d_counts;
+    out->kmer_ic_mult = p->d_ic;
+    out->kv_off = p->d_kv_off;
+    out->kv_var = p->d_kv_var;
+    out->kv_bits = p->d_kv_bits;
+    out->unique_idx = p->d_unique_idx;
+    out->multi_idx = p->d_multi_idx;
+    return BT_OK;
+}
+
+int paths_number_shared(bt_paths *p, const uint32_t *group_cluster_off, uint32_t G, int32_t **d_kmer_shared, uint32_t *h_group_num_shared) {
+    BT_HIP(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const unsigned maxb = p->ctx->num_cu * 16;
+    const uint32_t C = p->C;
+    const uint64_t R = p->R, M = p->num_multi;
+    std::vector<void *> tmp;
+    int32_t *d_shared = nullptr;
+    auto cleanup = [&](bool all) {
+        (void)hipStreamSynchronize(st);
+        for (void *q : tmp) (void)hipFree(q);
+        if (all && d_shared) (void)hipFree(d_shared);
+    };
+#define TRYC(x)                  \
+    do {                         \
+        const int _rc = (x);     \
+        if (_rc != BT_OK) {      \
+            cleanup(true);       \
+            return _rc;          \
+        }                        \
+    } while (0)
+#define HIPC(call)                                                                      \
+    do {                                                                                \
+        hipError_t _e = (call);                                                         \
+        if (_e != hipSuccess) {                                                         \
+            cleanup(true);                                                              \
+            return bt::fail(std::string(#call) + ": " + hipGetErrorString(_e));         \
+        }                                                                               \
+    } while (0)
+    {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_shared), std::max<uint64_t>(R * 4, 16));
+        if (e != hipSuccess) return fail(std::string("bt_gibbs_source_create_from_paths: device allocation: ") + hipGetErrorString(e));
+    }
+    HIPC(hipMemsetAsync(d_shared, 0xFF, std::max<uint64_t>(R * 4, 16), st));   // -1: not a multicluster row
+    for (uint32_t g = 0; g < G; ++g) h_group_num_shared[g] = 0;
+    if (M) {
+        std::vector<uint32_t> cluster_group(C), group_m0(G);
+        for (uint32_t g = 0; g < G; ++g) {
+            group_m0[g] = p->multi_off[group_cluster_off[g]];
+            for (uint32_t c = group_cluster_off[g]; c < group_cluster_off[g + 1]; ++c) cluster_group[c] = g;
+        }
+        const uint64_t cap = pow2_at_least(2 * M);
+        uint64_t *klo = nullptr, *khi = nullptr;
+        uint32_t *ktag = nullptr, *kstate = nullptr, *kfirst = nullptr, *item_slot = nullptr, *item_row = nullptr, *is_first = nullptr, *before = nullptr;
+        uint32_t *d_multi_off = nullptr, *d_kmer_off = nullptr, *d_cluster_group = nullptr, *d_group_m0 = nullptr, *d_group_end = nullptr, *d_group_n = nullptr;
+        TRYC(dev_alloc(&klo, cap, tmp));
+        TRYC(dev_alloc(&khi, cap, tmp));
+        TRYC(dev_alloc(&ktag, cap, tmp));
+        TRYC(dev_alloc(&kstate, cap, tmp));
+        TRYC(dev_alloc(&kfirst, cap, tmp));
+        TRYC(dev_alloc(&item_slot, M, tmp));
+        TRYC(dev_alloc(&item_row, M, tmp));
+        TRYC(dev_alloc(&is_first, M, tmp));
+        TRYC(dev_alloc(&before, M + 1, tmp));
+        TRYC(dev_alloc(&d_multi_off, C + 1, tmp));
+        TRYC(dev_alloc(&d_kmer_off, C + 1, tmp));
+        TRYC(dev_alloc(&d_cluster_group, C, tmp));
+        TRYC(dev_alloc(&d_group_m0, G + 1, tmp));
+        TRYC(dev_alloc(&d_group_n, G + 1, tmp));
+        (void)d_group_end;
+        HIPC(hipMemsetAsync(kstate, 0, cap * 4, st));
+        HIPC(hipMemsetAsync(kfirst, 0xFF, cap * 4, st));
+        HIPC(hipMemcpy(d_multi_off, p->multi_off.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(d_kmer_off, p->kmer_off.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(d_cluster_group, cluster_group.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+        group_m0.push_back((uint32_t)M);
+        HIPC(hipMemcpy(d_group_m0, group_m0.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(shared_index_kernel, dim3(grid_for(M, BLOCK, maxb)), dim3(BLOCK), 0, st, p->d_multi_idx, d_multi_off, d_kmer_off, d_cluster_group, C, p->d_key, (uint32_t)M, klo,
+                           khi, ktag, kstate, kfirst, cap - 1, item_slot, item_row);
+        hipLaunchKernelGGL(shared_first_kernel, dim3(grid_for(M, BLOCK, maxb)), dim3(BLOCK), 0, st, item_slot, kfirst, (uint32_t)M, is_first);
+        HIPC(hipGetLastError());
+        uint64_t firsts = 0;
+        TRYC(exclusive_scan(p->ctx, is_first, M, before, &firsts, "shared k-mer records", tmp));
+        hipLaunchKernelGGL(shared_number_kernel, dim3(grid_for(M, BLOCK, maxb)), dim3(BLOCK), 0, st, item_slot, item_row, kfirst, ktag, before, d_group_m0, (uint32_t)M, d_shared);
+        hipLaunchKernelGGL(gather_u32_idx32_kernel, dim3((G + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, before, d_group_m0, G + 1, d_group_n);
+        HIPC(hipGetLastError());
+        std::vector<uint32_t> at(G + 1);
+        HIPC(hipMemcpyAsync(at.data(), d_group_n, (size_t)(G + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        // (groups are in cluster order, so group g's rows end where group g + 1's begin; the last one ends at M)
+        for (uint32_t g = 0; g < G; ++g) h_group_num_shared[g] = at[g + 1] - at[g];
+    }
+    cleanup(false);
+#undef TRYC
+#undef HIPC
+    *d_kmer_shared = d_shared;
+    return BT_OK;
+}
+
+void paths_release_candidates(bt_paths *p, std::vector<void *> &allocs) {
+    for (void *q : p->cand_owned) {
+        if (q == p->d_key) (void)hipFree(q);   // (the keys only serve the numbering of the shared records)
+        else allocs.push_back(q);
+    }
+    p->cand_owned.clear();
+    p->drop_device_candidates();
+    p->have_candidates = false;
+}
+
+}  // namespace bt
+
+extern "C" {
+
+int bt_paths_candidates_device(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes) { return candidates_build(p, table, sizes); }
+
+// "device build + copies to the host": the per-row arrays come back into host vectors (what bt_paths_candidates_fetch hands out) and leave the device
+int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes) {
+    const int rc = candidates_build(p, table, sizes);
+    if (rc != BT_OK) return rc;
+    hipError_t e = hipSuccess;
+    auto down = [&](auto &v, const auto *d, uint64_t n) {
+        if (e != hipSuccess) return;
+        v.resize(n);
+        if (n) e = hipMemcpy(v.data(), d, n * sizeof(v[0]), hipMemcpyDeviceToHost);
+    };
+    try {
+        down(p->mult, p->d_mult, p->mult_bytes);
+        down(p->key, p->d_key, 2 * p->R);
+        down(p->has_counts, p->d_has_counts, p->R);
+        down(p->counts, p->d_counts, p->R * p->S);
+        down(p->ic, p->d_ic, 2 * p->R);
+        down(p->kv_off, p->d_kv_off, p->R + 1);
+        down(p->kv_var, p->d_kv_var, p->nnz);
+        down(p->kv_bits, p->d_kv_bits, p->kv_words);
+        down(p->unique_idx, p->d_unique_idx, p->num_unique);
+        down(p->multi_idx, p->d_multi_idx, p->num_multi);
+    } catch (const std::exception &ex) {
+        p->drop_device_candidates();
+        p->have_candidates = false;
+        return fail(std::string("bt_paths_candidates: ") + ex.what());
+    }
+    p->drop_device_candidates();
+    if (e != hipSuccess) {
+        p->have_candidates = false;
+        return fail(std::string("bt_paths_candidates: copying the bundle to the host: ") + hipGetErrorString(e));
+    }
+    return BT_OK;
+}
+
+int bt_paths_candidates_fetch_small(bt_paths *p, bt_paths_candidates_out *o) {
+    if (!p || !o) return fail("bt_paths_candidates_fetch_small: null argument");
+    if (!p->have_candidates) return fail("bt_paths_candidates_fetch_small: no candidates (bt_paths_candidates / bt_paths_candidates_device has not run, or a source took them)");
+    if (o->hap_kmer_mult || o->kmer_key || o->kmer_has_counts || o->kmer_counts || o->kmer_ic_mult || o->kv_off || o->kv_var || o->kv_bits || o->unique_idx || o->multi_idx)
+        return fail("bt_paths_candidates_fetch_small: the per-row pointers must be NULL");
+    auto cp = [](const auto &v, auto *dst) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+    };
+    cp(p->kmer_off, o->kmer_off);
+    cp(p->unique_off, o->unique_off);
+    cp(p->multi_off, o->multi_off);
+    cp(p->hap_allele, o->hap_allele);
+    cp(p->hapnest_off, o->hapnest_off);
+    cp(p->hapnest_idx, o->hapnest_idx);
+    cp(p->nestdep_off, o->nestdep_off);
+    cp(p->nestdep_cluster, o->nestdep_cluster);
+    cp(p->nestdep_var_off, o->nestdep_var_off);
+    cp(p->nestdep_var, o->nestdep_var);
+    return BT_OK;
+}
+
 int bt_paths_candidates_fetch(bt_paths *p, bt_paths_candidates_out *o) {
     if (!p || !o) return fail("bt_paths_candidates_fetch: null argument");
     if (!p->have_candidates) return fail("bt_paths_candidates_fetch: bt_paths_candidates has not run");
+    if (p->cand_on_device) return fail("bt_paths_candidates_fetch: the per-row arrays are on the device (bt_paths_candidates_device): use bt_paths_candidates_fetch_small");
     auto cp = [](const auto &v, auto *dst) {   // (the large arrays on several threads: one core's memcpy into fresh pages is the slow part)
         if (!dst || v.empty()) return;
         const size_t bytes = v.size() * sizeof(v[0]);

@@ -175,6 +175,8 @@ struct GpuSampler : GibbsSampler {
 std::unique_ptr<GibbsSampler> InferenceEngine::newSampler(uint32_t noise_seeding, const GibbsBatchData &batch, bt_ctx *on_ctx) {
     const bt_gibbs_params p = params(noise_seeding);
     if (make_sampler) return make_sampler(p, batch);
+    // a position-only batch: its rows are on the device already, in the unit's source
+    if (batch.onDevice()) return std::unique_ptr<GibbsSampler>(new GpuSampler(on_ctx ? on_ctx : ctx, p, batch.source.get(), batch.source_pos));
     return std::unique_ptr<GibbsSampler>(new GpuSampler(on_ctx ? on_ctx : ctx, p, batch));
 }
 
@@ -313,18 +315,29 @@ void InferenceEngine::estimateNoise(CountDistribution *cd, const GibbsBatchData 
     // (bt_gibbs_create_from_source) — no per-chain subset copy on the host, no per-chain upload.
     struct Source {
         bt_gibbs_source *s = nullptr;
+        bool owned = true;
         ~Source() {
-            if (s) bt_gibbs_source_destroy(s);
+            if (s && owned) bt_gibbs_source_destroy(s);
         }
     } source;
-    if (!make_sampler && ctx && unit.numGroups() && !getenv("BT_NOISE_NO_SOURCE")) {
+    if (!make_sampler && ctx && unit.numGroups() && unit.onDevice()) {   // the unit's source exists already: classifyPathKmers built it on the device
+        source.s = unit.source.get();
+        source.owned = false;
+    } else if (!make_sampler && ctx && unit.numGroups() && !getenv("BT_NOISE_NO_SOURCE")) {
         StageScope stage("  noise chains: the unit's clusters to the device (once)");
         const bt_gibbs_batch view = unit.view();
         check(bt_gibbs_source_create(ctx, (uint32_t)S, &view, &source.s), "bt_gibbs_source_create");
     }
     const bt_gibbs_params noise_params = params(1);
-    auto sampler_over = [this, &unit, &source, &noise_params](const std::vector<uint32_t> &ids, bt_ctx *on_ctx) -> std::unique_ptr<Sampler> {
-        if (source.s) return std::unique_ptr<Sampler>(new GpuSampler(on_ctx ? on_ctx : ctx, noise_params, source.s, ids));
+    // positions in the source of the groups `ids` of this batch (an attached source holds the whole unit, the batch maybe a rank's share of it)
+    auto in_source = [&unit](const std::vector<uint32_t> &ids) {
+        if (!unit.onDevice()) return ids;
+        std::vector<uint32_t> pos(ids.size());
+        for (size_t i = 0; i < ids.size(); i++) pos[i] = unit.source_pos[ids[i]];
+        return pos;
+    };
+    auto sampler_over = [this, &unit, &source, &noise_params, &in_source](const std::vector<uint32_t> &ids, bt_ctx *on_ctx) -> std::unique_ptr<Sampler> {
+        if (source.s) return std::unique_ptr<Sampler>(new GpuSampler(on_ctx ? on_ctx : ctx, noise_params, source.s, in_source(ids)));
         return newSampler(1, unit.take(ids), on_ctx);
     };
     std::unique_ptr<Sampler> sampler;
@@ -383,7 +396,7 @@ void InferenceEngine::estimateNoise(CountDistribution *cd, const GibbsBatchData 
             bt_ctx *helper_ctx = alt.c ? (sampler_ctx == ctx ? alt.c : ctx) : nullptr;
             const uint64_t like = sampler ? sampler->deviceBytes() : 0;   // the next chain's sampler is over as many groups of the same unit: about as large
             // (the selector is touched by one thread at a time: this one before the first chain, then the helper of each chain, whose result is taken before the next is started)
-            prepared = std::async(std::launch::async, [this, &source, &noise_params, &sampler_over, &select, current = sampler_groups, helper_ctx, like]() {
+            prepared = std::async(std::launch::async, [this, &source, &noise_params, &sampler_over, &select, &in_source, current = sampler_groups, helper_ctx, like]() {
                 Prepared r;
                 r.groups = select();
                 const std::vector<uint32_t> &next = r.groups;
@@ -393,7 +406,7 @@ void InferenceEngine::estimateNoise(CountDistribution *cd, const GibbsBatchData 
                     uint64_t need = 0, total = 0, free_bytes = 0;
                     int num_cu = 0;
                     need = like + like / 4;
-                    if (source.s && ((need == 0 && bt_gibbs_state_bytes_from_source(source.s, &noise_params, next.data(), (uint32_t)next.size(), &need) != BT_OK) ||
+                    if (source.s && ((need == 0 && bt_gibbs_state_bytes_from_source(source.s, &noise_params, in_source(next).data(), (uint32_t)next.size(), &need) != BT_OK) ||
                                      bt_ctx_info(helper_ctx, &num_cu, &total, &free_bytes, nullptr, 0) != BT_OK))
                         r.why_not = bt_last_error();
                     else if (source.s && (double)need > 0.7 * (double)free_bytes) r.why_not = "sampler state does not fit next to the running chain's";
@@ -444,7 +457,8 @@ void InferenceEngine::runDefault(const GibbsBatchData &batch, const CountDistrib
         const bt_gibbs_batch view = batch.view();
         uint64_t need = 0, total = 0, free_bytes = 0;
         int num_cu = 0;
-        int have = bt_gibbs_state_bytes(ctx, &p, &view, &need) == BT_OK && bt_ctx_info(ctx, &num_cu, &total, &free_bytes, nullptr, 0) == BT_OK;
+        int have = (batch.onDevice() ? bt_gibbs_state_bytes_from_source(batch.source.get(), &p, batch.source_pos.data(), (uint32_t)batch.source_pos.size(), &need)
+                                     : bt_gibbs_state_bytes(ctx, &p, &view, &need)) == BT_OK && bt_ctx_info(ctx, &num_cu, &total, &free_bytes, nullptr, 0) == BT_OK;
         if (const char *e = getenv("BT_GIBBS_FREE_BYTES")) free_bytes = strtoull(e, nullptr, 0);   // (tests: pretend a smaller GPU)
         if (have && free_bytes && (double)need > 0.9 * (double)free_bytes) {
             const uint32_t parts = (uint32_t)std::min<uint64_t>(batch.numGroups(), (uint64_t)((double)need / (0.75 * (double)free_bytes)) + 1);

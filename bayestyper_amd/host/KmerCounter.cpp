@@ -110,6 +110,22 @@ bt_gibbs_batch GibbsBatchData::view() const {
     return b;
 }
 
+bt_gibbs_batch GibbsBatchData::structureView() const {
+    bt_gibbs_batch b = view();
+    b.hap_kmer_mult = b.kmer_has_counts = b.kmer_counts = b.kmer_ic_mult = nullptr;
+    b.kmer_shared = nullptr;
+    b.kv_off = b.kv_bits = b.unique_idx = b.multi_idx = b.group_num_shared = nullptr;
+    b.kv_var = nullptr;
+    return b;
+}
+
+void GibbsBatchData::dropRows() {
+    for (auto *v : {&hap_kmer_mult, &kmer_has_counts, &kmer_counts, &kmer_ic_mult}) std::vector<uint8_t>().swap(*v);
+    for (auto *v : {&kv_off, &kv_bits, &unique_idx, &multi_idx}) std::vector<uint32_t>().swap(*v);
+    std::vector<int32_t>().swap(kmer_shared);
+    std::vector<uint16_t>().swap(kv_var);
+}
+
 namespace {
 // appends the slice [off[i], off[i+1]) * width of `src` to `dst` and extends the offsets `dst_off`
 template <typename T>
@@ -173,6 +189,10 @@ GibbsBatchData GibbsBatchData::fromView(const bt_gibbs_batch &b, uint32_t S) {
 GibbsBatchData GibbsBatchData::take(const std::vector<uint32_t> &ids) const {
     GibbsBatchData o;
     o.S = S;
+    const bool rows = !kv_off.empty();   // (a position-only batch, or one whose rows were dropped: small arrays only)
+    o.source = source;
+    if (source)
+        for (uint32_t g : ids) o.source_pos.push_back(source_pos[g]);
     // prefix sums over the per-cluster quantities that have no explicit offsets
     const uint32_t C = numClusters();
     std::vector<uint64_t> mult_off(C + 1, 0), hapvar_off(C + 1, 0), hap_base(C + 1, 0), var_base(C + 1, 0), kvb_off(C + 1, 0);
@@ -182,9 +202,9 @@ GibbsBatchData GibbsBatchData::take(const std::vector<uint32_t> &ids) const {
         hapvar_off[c + 1] = hapvar_off[c] + H * V;
         hap_base[c + 1] = hap_base[c] + H;
         var_base[c + 1] = var_base[c] + V;
-        kvb_off[c + 1] = kvb_off[c] + (uint64_t)(kv_off[kmer_off[c + 1]] - kv_off[kmer_off[c]]) * ((H + 31) / 32);
+        if (rows) kvb_off[c + 1] = kvb_off[c] + (uint64_t)(kv_off[kmer_off[c + 1]] - kv_off[kmer_off[c]]) * ((H + 31) / 32);
     }
-    {   // the large arrays get their final capacity up front (appending slice by slice reallocated — and re-touched — them a dozen times over)
+    if (rows) {   // the large arrays get their final capacity up front (appending slice by slice reallocated — and re-touched — them a dozen times over)
         uint64_t rows = 0, mult = 0, kv = 0, kvb = 0, uniq = 0, multi = 0, nclus = 0;
         for (uint32_t g : ids)
             for (uint32_t c = group_cluster_off[g]; c < group_cluster_off[g + 1]; c++) {
@@ -215,7 +235,7 @@ GibbsBatchData GibbsBatchData::take(const std::vector<uint32_t> &ids) const {
     o.group_source_off.push_back(0);
     o.edge_off.push_back(0);
     o.kmer_off.push_back(0);
-    o.kv_off.push_back(0);
+    if (rows) o.kv_off.push_back(0);
     o.unique_off.push_back(0);
     o.multi_off.push_back(0);
     o.hapnest_off.push_back(0);
@@ -226,7 +246,7 @@ GibbsBatchData GibbsBatchData::take(const std::vector<uint32_t> &ids) const {
         appendSlice(o.group_ploidy, group_ploidy, (uint64_t)g * S, (uint64_t)(g + 1) * S);
         appendSlice(o.group_sources, group_sources, group_source_off[g], group_source_off[g + 1]);
         o.group_source_off.push_back((uint32_t)o.group_sources.size());
-        o.group_num_shared.push_back(group_num_shared[g]);
+        if (!group_num_shared.empty()) o.group_num_shared.push_back(group_num_shared[g]);
         for (uint32_t c = group_cluster_off[g]; c < group_cluster_off[g + 1]; c++) {
             o.cluster_idx.push_back(cluster_idx[c]);
             appendSlice(o.edges, edges, edge_off[c], edge_off[c + 1]);
@@ -234,20 +254,22 @@ GibbsBatchData GibbsBatchData::take(const std::vector<uint32_t> &ids) const {
             o.num_haplotypes.push_back(num_haplotypes[c]);
             o.num_variants.push_back(num_variants[c]);
             const uint32_t r0 = kmer_off[c], r1 = kmer_off[c + 1];
-            appendSlice(o.hap_kmer_mult, hap_kmer_mult, mult_off[c], mult_off[c + 1]);
-            appendSlice(o.kmer_has_counts, kmer_has_counts, r0, r1);
-            appendSlice(o.kmer_counts, kmer_counts, (uint64_t)r0 * S, (uint64_t)r1 * S);
-            appendSlice(o.kmer_ic_mult, kmer_ic_mult, (uint64_t)r0 * 2, (uint64_t)r1 * 2);
-            appendSlice(o.kmer_shared, kmer_shared, r0, r1);
-            const uint32_t e0 = kv_off[r0], base = o.kv_off.back();
-            for (uint32_t r = r0; r < r1; r++) o.kv_off.push_back(base + (kv_off[r + 1] - e0));
-            appendSlice(o.kv_var, kv_var, e0, kv_off[r1]);
-            appendSlice(o.kv_bits, kv_bits, kvb_off[c], kvb_off[c + 1]);
+            if (rows) {
+                appendSlice(o.hap_kmer_mult, hap_kmer_mult, mult_off[c], mult_off[c + 1]);
+                appendSlice(o.kmer_has_counts, kmer_has_counts, r0, r1);
+                appendSlice(o.kmer_counts, kmer_counts, (uint64_t)r0 * S, (uint64_t)r1 * S);
+                appendSlice(o.kmer_ic_mult, kmer_ic_mult, (uint64_t)r0 * 2, (uint64_t)r1 * 2);
+                appendSlice(o.kmer_shared, kmer_shared, r0, r1);
+                const uint32_t e0 = kv_off[r0], base = o.kv_off.back();
+                for (uint32_t r = r0; r < r1; r++) o.kv_off.push_back(base + (kv_off[r + 1] - e0));
+                appendSlice(o.kv_var, kv_var, e0, kv_off[r1]);
+                appendSlice(o.kv_bits, kv_bits, kvb_off[c], kvb_off[c + 1]);
+                appendSlice(o.unique_idx, unique_idx, unique_off[c], unique_off[c + 1]);
+                appendSlice(o.multi_idx, multi_idx, multi_off[c], multi_off[c + 1]);
+            }
             o.kmer_off.push_back(o.kmer_off.back() + (r1 - r0));
-            appendSlice(o.unique_idx, unique_idx, unique_off[c], unique_off[c + 1]);
-            o.unique_off.push_back((uint32_t)o.unique_idx.size());
-            appendSlice(o.multi_idx, multi_idx, multi_off[c], multi_off[c + 1]);
-            o.multi_off.push_back((uint32_t)o.multi_idx.size());
+            o.unique_off.push_back(o.unique_off.back() + (unique_off[c + 1] - unique_off[c]));
+            o.multi_off.push_back(o.multi_off.back() + (multi_off[c + 1] - multi_off[c]));
             appendSlice(o.hap_allele, hap_allele, hapvar_off[c], hapvar_off[c + 1]);
             const uint32_t hn0 = hapnest_off[hap_base[c]], hbase = o.hapnest_off.back();
             for (uint64_t h = hap_base[c]; h < hap_base[c + 1]; h++) o.hapnest_off.push_back(hbase + (hapnest_off[h + 1] - hn0));
@@ -524,76 +546,110 @@ GibbsBatchData KmerCounter::classifyPathKmers(bt_table *table, const InferenceUn
     st.reset(new StageScope("  candidates (bt_paths_candidates)"));
 
     // ---- getHaplotypeCandidates of every cluster (VariantClusterGraph.cpp:941-1135) ----
+    // Default: the bundle is built and KEPT on the device and becomes the unit's sampler source there (bt_gibbs_source_create_from_paths); only the O(C) arrays
+    // and the host graph walk's come back.  BT_CANDIDATES_ON_HOST=1: the bundle crosses the host (fetched, assembled, uploaded again by the engine).
+    const bool on_host = getenv("BT_CANDIDATES_ON_HOST") && atoi(getenv("BT_CANDIDATES_ON_HOST")) != 0;
     bt_paths_candidates_sizes sz{};
-    check(bt_paths_candidates(unit_paths->h, table, &sz), "bt_paths_candidates");
-    st.reset(new StageScope("  candidates: host arrays + fetch"));
     GibbsBatchData b;
     b.S = S;
-    // (the arrays are sized — i.e. zero-filled, page by page — on several threads: one thread took 0.17 s for the 0.4 GB of a chr20-sized unit)
     std::vector<uint64_t> kmer_key;
-    {
-        const std::vector<std::function<void()>> sizing = {
-            [&]() { kmer_key.resize(std::max<uint64_t>(sz.rows * 2, 1)); },
-            [&]() { b.kmer_off.resize(C + 1); b.unique_off.resize(C + 1); b.multi_off.resize(C + 1); b.nestdep_off.resize(C + 1); },
-            [&]() { b.hap_kmer_mult.resize(std::max<uint64_t>(sz.mult_bytes, 1)); },
-            [&]() { b.kmer_has_counts.resize(std::max<uint64_t>(sz.rows, 1)); b.kmer_counts.resize(std::max<uint64_t>(sz.rows * S, 1)); },
-            [&]() { b.kmer_ic_mult.resize(std::max<uint64_t>(sz.rows * 2, 1)); },
-            [&]() { b.kv_off.resize(sz.rows + 1); },
-            [&]() { b.kv_var.resize(std::max<uint64_t>(sz.nnz, 1)); },
-            [&]() { b.kv_bits.resize(std::max<uint64_t>(sz.kv_words, 1)); },
-            [&]() { b.unique_idx.resize(std::max<uint64_t>(sz.num_unique, 1)); b.multi_idx.resize(std::max<uint64_t>(sz.num_multi, 1)); },
-            [&]() {
-                b.hap_allele.resize(std::max<uint64_t>(sz.hap_allele, 1));
-                b.hapnest_off.resize(sz.num_haplotypes + 1);
-                b.hapnest_idx.resize(std::max<uint64_t>(sz.hapnest, 1));
-                b.nestdep_cluster.resize(std::max<uint64_t>(sz.nestdep, 1));
-                b.nestdep_var_off.resize(sz.nestdep + 1);
-                b.nestdep_var.resize(std::max<uint64_t>(sz.nestdep_var, 1));
-            }};
-        parallelFor(sizing.size(), (unsigned)sizing.size(), [&](size_t a, size_t e, unsigned) {
-            for (size_t i = a; i < e; i++) sizing[i]();
-        });
+    if (!on_host) {
+        check(bt_paths_candidates_device(unit_paths->h, table, &sz), "bt_paths_candidates_device");
+        st.reset(new StageScope("  candidates: small arrays to the host (the bundle stays on the device)"));
+        b.kmer_off.resize(C + 1);
+        b.unique_off.resize(C + 1);
+        b.multi_off.resize(C + 1);
+        b.nestdep_off.resize(C + 1);
+        b.hap_allele.resize(std::max<uint64_t>(sz.hap_allele, 1));
+        b.hapnest_off.resize(sz.num_haplotypes + 1);
+        b.hapnest_idx.resize(std::max<uint64_t>(sz.hapnest, 1));
+        b.nestdep_cluster.resize(std::max<uint64_t>(sz.nestdep, 1));
+        b.nestdep_var_off.resize(sz.nestdep + 1);
+        b.nestdep_var.resize(std::max<uint64_t>(sz.nestdep_var, 1));
+        bt_paths_candidates_out out{};
+        out.kmer_off = b.kmer_off.data();
+        out.unique_off = b.unique_off.data();
+        out.multi_off = b.multi_off.data();
+        out.hap_allele = b.hap_allele.data();
+        out.hapnest_off = b.hapnest_off.data();
+        out.hapnest_idx = b.hapnest_idx.data();
+        out.nestdep_off = b.nestdep_off.data();
+        out.nestdep_cluster = b.nestdep_cluster.data();
+        out.nestdep_var_off = b.nestdep_var_off.data();
+        out.nestdep_var = b.nestdep_var.data();
+        check(bt_paths_candidates_fetch_small(unit_paths->h, &out), "bt_paths_candidates_fetch_small");
+        b.hap_allele.resize(sz.hap_allele);
+        b.hapnest_idx.resize(sz.hapnest);
+        b.nestdep_cluster.resize(sz.nestdep);
+        b.nestdep_var.resize(sz.nestdep_var);
+    } else {
+        check(bt_paths_candidates(unit_paths->h, table, &sz), "bt_paths_candidates");
+        st.reset(new StageScope("  candidates: host arrays + fetch"));
+        // (the arrays are sized — i.e. zero-filled, page by page — on several threads: one thread took 0.17 s for the 0.4 GB of a chr20-sized unit)
+        {
+            const std::vector<std::function<void()>> sizing = {
+                [&]() { kmer_key.resize(std::max<uint64_t>(sz.rows * 2, 1)); },
+                [&]() { b.kmer_off.resize(C + 1); b.unique_off.resize(C + 1); b.multi_off.resize(C + 1); b.nestdep_off.resize(C + 1); },
+                [&]() { b.hap_kmer_mult.resize(std::max<uint64_t>(sz.mult_bytes, 1)); },
+                [&]() { b.kmer_has_counts.resize(std::max<uint64_t>(sz.rows, 1)); b.kmer_counts.resize(std::max<uint64_t>(sz.rows * S, 1)); },
+                [&]() { b.kmer_ic_mult.resize(std::max<uint64_t>(sz.rows * 2, 1)); },
+                [&]() { b.kv_off.resize(sz.rows + 1); },
+                [&]() { b.kv_var.resize(std::max<uint64_t>(sz.nnz, 1)); },
+                [&]() { b.kv_bits.resize(std::max<uint64_t>(sz.kv_words, 1)); },
+                [&]() { b.unique_idx.resize(std::max<uint64_t>(sz.num_unique, 1)); b.multi_idx.resize(std::max<uint64_t>(sz.num_multi, 1)); },
+                [&]() {
+                    b.hap_allele.resize(std::max<uint64_t>(sz.hap_allele, 1));
+                    b.hapnest_off.resize(sz.num_haplotypes + 1);
+                    b.hapnest_idx.resize(std::max<uint64_t>(sz.hapnest, 1));
+                    b.nestdep_cluster.resize(std::max<uint64_t>(sz.nestdep, 1));
+                    b.nestdep_var_off.resize(sz.nestdep + 1);
+                    b.nestdep_var.resize(std::max<uint64_t>(sz.nestdep_var, 1));
+                }};
+            parallelFor(sizing.size(), (unsigned)sizing.size(), [&](size_t a, size_t e, unsigned) {
+                for (size_t i = a; i < e; i++) sizing[i]();
+            });
+        }
+        bt_paths_candidates_out out{};
+        out.kmer_off = b.kmer_off.data();
+        out.hap_kmer_mult = b.hap_kmer_mult.data();
+        out.kmer_key = kmer_key.data();
+        out.kmer_has_counts = b.kmer_has_counts.data();
+        out.kmer_counts = b.kmer_counts.data();
+        out.kmer_ic_mult = b.kmer_ic_mult.data();
+        out.kv_off = b.kv_off.data();
+        out.kv_var = b.kv_var.data();
+        out.kv_bits = b.kv_bits.data();
+        out.unique_off = b.unique_off.data();
+        out.unique_idx = b.unique_idx.data();
+        out.multi_off = b.multi_off.data();
+        out.multi_idx = b.multi_idx.data();
+        out.hap_allele = b.hap_allele.data();
+        out.hapnest_off = b.hapnest_off.data();
+        out.hapnest_idx = b.hapnest_idx.data();
+        out.nestdep_off = b.nestdep_off.data();
+        out.nestdep_cluster = b.nestdep_cluster.data();
+        out.nestdep_var_off = b.nestdep_var_off.data();
+        out.nestdep_var = b.nestdep_var.data();
+        check(bt_paths_candidates_fetch(unit_paths->h, &out), "bt_paths_candidates_fetch");
+        unit_paths.reset();   // the enumerated paths are no longer needed (device route: once the source has taken the bundle)
+        b.hap_kmer_mult.resize(sz.mult_bytes);
+        b.kmer_has_counts.resize(sz.rows);
+        b.kmer_counts.resize(sz.rows * S);
+        b.kmer_ic_mult.resize(sz.rows * 2);
+        b.kv_var.resize(sz.nnz);
+        b.kv_bits.resize(sz.kv_words);
+        b.unique_idx.resize(sz.num_unique);
+        b.multi_idx.resize(sz.num_multi);
+        b.hap_allele.resize(sz.hap_allele);
+        b.hapnest_idx.resize(sz.hapnest);
+        b.nestdep_cluster.resize(sz.nestdep);
+        b.nestdep_var.resize(sz.nestdep_var);
     }
-    bt_paths_candidates_out out{};
-    out.kmer_off = b.kmer_off.data();
-    out.hap_kmer_mult = b.hap_kmer_mult.data();
-    out.kmer_key = kmer_key.data();
-    out.kmer_has_counts = b.kmer_has_counts.data();
-    out.kmer_counts = b.kmer_counts.data();
-    out.kmer_ic_mult = b.kmer_ic_mult.data();
-    out.kv_off = b.kv_off.data();
-    out.kv_var = b.kv_var.data();
-    out.kv_bits = b.kv_bits.data();
-    out.unique_off = b.unique_off.data();
-    out.unique_idx = b.unique_idx.data();
-    out.multi_off = b.multi_off.data();
-    out.multi_idx = b.multi_idx.data();
-    out.hap_allele = b.hap_allele.data();
-    out.hapnest_off = b.hapnest_off.data();
-    out.hapnest_idx = b.hapnest_idx.data();
-    out.nestdep_off = b.nestdep_off.data();
-    out.nestdep_cluster = b.nestdep_cluster.data();
-    out.nestdep_var_off = b.nestdep_var_off.data();
-    out.nestdep_var = b.nestdep_var.data();
-    check(bt_paths_candidates_fetch(unit_paths->h, &out), "bt_paths_candidates_fetch");
-    unit_paths.reset();   // the enumerated paths are no longer needed
-    b.hap_kmer_mult.resize(sz.mult_bytes);
-    b.kmer_has_counts.resize(sz.rows);
-    b.kmer_counts.resize(sz.rows * S);
-    b.kmer_ic_mult.resize(sz.rows * 2);
-    b.kv_var.resize(sz.nnz);
-    b.kv_bits.resize(sz.kv_words);
-    b.unique_idx.resize(sz.num_unique);
-    b.multi_idx.resize(sz.num_multi);
-    b.hap_allele.resize(sz.hap_allele);
-    b.hapnest_idx.resize(sz.hapnest);
-    b.nestdep_cluster.resize(sz.nestdep);
-    b.nestdep_var.resize(sz.nestdep_var);
 
     // ---- the group structure (VariantClusterGroup.hpp:60-89) around the bundles ----
     st.reset(new StageScope("  group structure (host)"));
     const uint32_t G = (uint32_t)unit.variant_cluster_groups.size();
-    b.kmer_shared.assign(sz.rows, -1);
+    if (on_host) b.kmer_shared.assign(sz.rows, -1);
     b.group_cluster_off.push_back(0);
     b.group_source_off.push_back(0);
     b.edge_off.push_back(0);
@@ -609,7 +665,7 @@ GibbsBatchData KmerCounter::classifyPathKmers(bt_table *table, const InferenceUn
         for (uint32_t v = 0; v < grp.clusters.size(); v++) {
             const uint32_t c = ug.group_first[g] + v;
             const uint32_t r0 = b.kmer_off[c];
-            for (uint32_t i = b.multi_off[c]; i < b.multi_off[c + 1]; i++) {
+            for (uint32_t i = b.multi_off[c]; on_host && i < b.multi_off[c + 1]; i++) {   // (device route: numbered on the device)
                 const uint64_t r = (uint64_t)r0 + b.multi_idx[i];
                 auto ins = keys.emplace(std::make_pair(kmer_key[2 * r], kmer_key[2 * r + 1]), (int32_t)keys.size());
                 b.kmer_shared[r] = ins.first->second;
@@ -622,8 +678,18 @@ GibbsBatchData KmerCounter::classifyPathKmers(bt_table *table, const InferenceUn
             b.var_num_alleles.insert(b.var_num_alleles.end(), ug.graphs[c].var_num_alleles.begin(), ug.graphs[c].var_num_alleles.end());
             b.var_has_dependency.insert(b.var_has_dependency.end(), ug.graphs[c].var_has_dependency.begin(), ug.graphs[c].var_has_dependency.end());
         }
-        b.group_num_shared.push_back((uint32_t)keys.size());
+        if (on_host) b.group_num_shared.push_back((uint32_t)keys.size());
         b.group_cluster_off.push_back((uint32_t)b.cluster_idx.size());
+    }
+    if (!on_host) {
+        st.reset(new StageScope("  candidates: sampler source from the device arrays (bt_gibbs_source_create_from_paths)"));
+        const bt_gibbs_batch structure = b.structureView();
+        bt_gibbs_source *src = nullptr;
+        check(bt_gibbs_source_create_from_paths(ctx, S, unit_paths->h, &structure, &src), "bt_gibbs_source_create_from_paths");
+        b.source.reset(src, [](bt_gibbs_source *x) { bt_gibbs_source_destroy(x); });
+        b.source_pos.resize(G);
+        for (uint32_t g = 0; g < G; g++) b.source_pos[g] = g;
+        unit_paths.reset();
     }
     return b;
 }

@@ -47,10 +47,20 @@ struct GibbsBatchData {
     std::vector<uint8_t> group_ploidy, hap_kmer_mult, kmer_has_counts, kmer_counts, kmer_ic_mult, var_has_dependency;
     std::vector<int32_t> kmer_shared;
     std::vector<uint16_t> kv_var, hap_allele, var_num_alleles, nestdep_var;
+    // A POSITION-ONLY batch (classifyPathKmers' default): the per-row arrays (hap_kmer_mult, kmer_*, kv_*, unique_idx, multi_idx) were built on the device and
+    // live in `source` (bt_gibbs_source_create_from_paths), shared by the unit's batch and every batch taken from it; those vectors are empty here, the
+    // small arrays are as in a full batch, and source_pos[g] is the position of group g in the source.  Samplers over such a batch come from
+    // bt_gibbs_create_from_source(source, ..., source_pos); view() of it must not be handed to bt_gibbs_create (structureView() is what the source was made of).
+    std::shared_ptr<bt_gibbs_source> source;
+    std::vector<uint32_t> source_pos;
+    bool onDevice() const { return (bool)source; }
+    bt_gibbs_batch structureView() const;   // view() with the per-row pointers, the index lists, kmer_shared and group_num_shared NULL
     bt_gibbs_batch view() const;
     static GibbsBatchData fromView(const bt_gibbs_batch &b, uint32_t S);   // a deep copy of a batch handed in as plain arrays (include/btgpu.h: bt_gibbs_batch)
-    // the groups `ids` (ascending) as a batch of their own; group_index keeps the unit-wide index
+    // the groups `ids` (ascending) as a batch of their own; group_index keeps the unit-wide index.  Of a position-only batch: the small arrays and the composed
+    // positions (no per-row copying) — exactly take() of the full batch with the per-row arrays dropped
     GibbsBatchData take(const std::vector<uint32_t> &ids) const;
+    void dropRows();   // the per-row arrays released (the small arrays stay)
     uint32_t numGroups() const { return (uint32_t)group_index.size(); }
     uint32_t numClusters() const { return (uint32_t)cluster_idx.size(); }
 };

@@ -822,6 +822,54 @@ unsigned long long bth_unit_roundtrip(void *stage, const char *filename, uint32_
         return 0;
     }
 }
+// GibbsBatchData::take as text, every array on a line of its own ("name: values"; per-row arrays by their sizes): of the batch as it is (position_only = 0:
+// take, then the per-row arrays dropped), or of the same batch made position-only first (its rows dropped, group g at position source_pos[g] of a source
+// that is never touched here: take must compose positions and small arrays without it).  Returns the text's size.
+unsigned long long bth_batch_take_dump(const bt_gibbs_batch *batch, unsigned S, const uint32_t *ids, uint32_t num_ids, int position_only, const uint32_t *source_pos, char *buf,
+                                       unsigned long long cap) {
+    GibbsBatchData b = GibbsBatchData::fromView(*batch, S);
+    static char never_dereferenced;
+    if (position_only) {
+        b.dropRows();
+        b.source = std::shared_ptr<bt_gibbs_source>(reinterpret_cast<bt_gibbs_source *>(&never_dereferenced), [](bt_gibbs_source *) {});
+        b.source_pos.assign(source_pos, source_pos + b.numGroups());
+    }
+    GibbsBatchData t = b.take(std::vector<uint32_t>(ids, ids + num_ids));
+    if (!position_only) t.dropRows();
+    std::ostringstream os;
+    auto line = [&os](const char *name, const auto &v) {
+        os << name << ":";
+        for (auto x : v) os << " " << (long long)x;
+        os << "\n";
+    };
+    line("group_index", t.group_index);
+    line("group_cluster_off", t.group_cluster_off);
+    line("group_ploidy", t.group_ploidy);
+    line("group_source_off", t.group_source_off);
+    line("group_sources", t.group_sources);
+    line("group_num_shared", t.group_num_shared);
+    line("cluster_idx", t.cluster_idx);
+    line("edge_off", t.edge_off);
+    line("edges", t.edges);
+    line("num_haplotypes", t.num_haplotypes);
+    line("num_variants", t.num_variants);
+    line("kmer_off", t.kmer_off);
+    line("unique_off", t.unique_off);
+    line("multi_off", t.multi_off);
+    line("hap_allele", t.hap_allele);
+    line("hapnest_off", t.hapnest_off);
+    line("hapnest_idx", t.hapnest_idx);
+    line("var_num_alleles", t.var_num_alleles);
+    line("var_has_dependency", t.var_has_dependency);
+    line("nestdep_off", t.nestdep_off);
+    line("nestdep_cluster", t.nestdep_cluster);
+    line("nestdep_var_off", t.nestdep_var_off);
+    line("nestdep_var", t.nestdep_var);
+    os << "rows: " << t.hap_kmer_mult.size() << " " << t.kmer_has_counts.size() << " " << t.kmer_counts.size() << " " << t.kmer_ic_mult.size() << " " << t.kmer_shared.size() << " "
+       << t.kv_off.size() << " " << t.kv_var.size() << " " << t.kv_bits.size() << " " << t.unique_idx.size() << " " << t.multi_idx.size() << "\n";
+    if (t.onDevice()) line("source_pos", t.source_pos);
+    return copy_out(os.str(), buf, cap);
+}
 // ChromosomePloidy of the stage's genome for samples given as a gender string ("FM.."): rows "<chromosome>\t<female>\t<male>\t<per-sample ploidies>"
 unsigned long long bth_chromosome_ploidy(void *stage, const char *ploidy_filename, const char *genders, char *buf, unsigned long long cap, char *err, unsigned err_len) {
     auto *st = (ClusterStage *)stage;

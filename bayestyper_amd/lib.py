@@ -78,6 +78,8 @@ bt_paths_count_multigroup = _sig("bt_paths_count_multigroup", [vp, vp, vp, vp, u
 bt_paths_classify = _sig("bt_paths_classify", [vp, vp, vp, vp, vp])
 bt_paths_candidates = _sig("bt_paths_candidates", [vp, vp, vp])
 bt_paths_candidates_fetch = _sig("bt_paths_candidates_fetch", [vp, vp])
+bt_paths_candidates_device = _sig("bt_paths_candidates_device", [vp, vp, vp])
+bt_paths_candidates_fetch_small = _sig("bt_paths_candidates_fetch_small", [vp, vp])
 bt_table_count_parameter_kmers = _sig("bt_table_count_parameter_kmers", [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_float])
 bt_table_kmer_stats = _sig("bt_table_kmer_stats", [vp, vp, vp, vp, vp, vp, vp])
 bt_table_count_intercluster = _sig("bt_table_count_intercluster", [vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32])
@@ -414,6 +416,29 @@ class Paths:
         check(bt_paths_candidates_fetch(self.h, C.byref(out)))
         return {name: arrs[name][: int(n[name])] for name, _ in CAND_FIELDS}
 
+    _SMALL = ("kmer_off", "unique_off", "multi_off", "hap_allele", "hapnest_off", "hapnest_idx", "nestdep_off", "nestdep_cluster", "nestdep_var_off", "nestdep_var")
+
+    def candidates_device(self, table):
+        """bt_paths_candidates_device + bt_paths_candidates_fetch_small: the per-row arrays stay in device memory (GibbsSource.from_paths takes them);
+        -> (sizes as a dict, the small host arrays as a dict)"""
+        sz = _CandSizes()
+        check(bt_paths_candidates_device(self.h, table.h, C.byref(sz)))
+        self.num_samples = table.num_samples
+        sizes = {n: int(getattr(sz, n)) for n, _ in _CandSizes._fields_}
+        return sizes, self.fetch_small(sizes)
+
+    def fetch_small(self, sizes):
+        n = {"kmer_off": self.C + 1, "unique_off": self.C + 1, "multi_off": self.C + 1, "hap_allele": sizes["hap_allele"], "hapnest_off": sizes["num_haplotypes"] + 1,
+             "hapnest_idx": sizes["hapnest"], "nestdep_off": self.C + 1, "nestdep_cluster": sizes["nestdep"], "nestdep_var_off": sizes["nestdep"] + 1,
+             "nestdep_var": sizes["nestdep_var"]}
+        dt = dict(CAND_FIELDS)
+        arrs = {name: np.zeros(max(int(n[name]), 1), dt[name]) for name in self._SMALL}
+        out = _CandOut()
+        for name in self._SMALL:
+            setattr(out, name, arrs[name].ctypes.data)
+        check(bt_paths_candidates_fetch_small(self.h, C.byref(out)))
+        return {name: arrs[name][: int(n[name])] for name in self._SMALL}
+
     def close(self):
         if self.h:
             bt_paths_destroy(self.h)
@@ -548,6 +573,13 @@ bt_gibbs_trace_enable = _sig("bt_gibbs_trace_enable", [vp, C.c_uint32])
 bt_gibbs_trace_fetch = _sig("bt_gibbs_trace_fetch", [vp, vp, C.c_uint64, u64p])
 bt_gibbs_posterior_summary = _sig("bt_gibbs_posterior_summary", [vp, vp])
 bt_gibbs_device_bytes = _sig("bt_gibbs_device_bytes", [vp, u64p])
+bt_gibbs_source_create = _sig("bt_gibbs_source_create", [vp, C.c_uint32, vp, C.POINTER(vp)])
+bt_gibbs_source_create_from_paths = _sig("bt_gibbs_source_create_from_paths", [vp, C.c_uint32, vp, vp, C.POINTER(vp)])
+bt_gibbs_source_fetch = _sig("bt_gibbs_source_fetch", [vp, vp, vp])
+bt_gibbs_source_destroy = _sig("bt_gibbs_source_destroy", [vp])
+bt_gibbs_source_device_bytes = _sig("bt_gibbs_source_device_bytes", [vp, u64p])
+bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)])
+bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
 bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
@@ -642,6 +674,15 @@ class Gibbs:
         self.h = h.value
         if lut_g is not None:
             self.set_lut(lut_g, lut_n)
+
+    @classmethod
+    def _from_handle(cls, ctx, h, flat, params, keep):
+        """a sampler the library built from a source (GibbsSource.sampler); `flat` holds S, num_groups, num_clusters, group_cluster_off of ITS groups"""
+        g = cls.__new__(cls)
+        g.ctx, g.flat, g.h = ctx, flat, h
+        g.S, g.C, g.G = flat["S"], flat["num_clusters"], flat["num_groups"]
+        g.params, g.batch, g._keep = params, None, keep
+        return g
 
     def set_lut(self, lut_g, lut_n):
         lut_g, lut_n = np.ascontiguousarray(lut_g, np.float64), np.ascontiguousarray(lut_n, np.float64)
@@ -757,4 +798,101 @@ class Gibbs:
     def close(self):
         if self.h:
             bt_gibbs_destroy(self.h)
+            self.h = None
+
+
+SOURCE_FIELDS = [("group_ploidy", np.uint8), ("group_sources", np.uint32), ("edges", np.uint32), ("hap_kmer_mult", np.uint8), ("kmer_has_counts", np.uint8),
+                 ("kmer_counts", np.uint8), ("kmer_ic_mult", np.uint8), ("kmer_shared", np.int32), ("kv_off", np.uint32), ("kv_var", np.uint16), ("kv_bits", np.uint32),
+                 ("unique_idx", np.uint32), ("multi_idx", np.uint32), ("hap_allele", np.uint16), ("hapnest_off", np.uint32), ("hapnest_idx", np.uint32),
+                 ("var_num_alleles", np.uint16), ("var_has_dependency", np.uint8), ("nestdep_cluster", np.uint32), ("nestdep_var_off", np.uint32), ("nestdep_var", np.uint16),
+                 ("group_num_shared", np.uint32), ("kmer_off", np.uint32), ("unique_off", np.uint32), ("multi_off", np.uint32)]   # include/btgpu.h: bt_gibbs_source_arrays
+
+
+class _SourceArrays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _ in SOURCE_FIELDS]
+
+
+class GibbsSource:
+    """A unit's flat batch arrays resident on the device (bt_gibbs_source_*), and samplers over any selection of its groups.
+    `flat`: the batch's dict (synth.flatten layout); from_paths needs only its per-group / per-cluster / haplotype / variant / nested-dependency fields."""
+
+    def __init__(self, ctx, h, flat):
+        self.ctx, self.h, self.flat = ctx, h, flat
+        self.S, self.G = flat["S"], flat["num_groups"]
+
+    @classmethod
+    def from_batch(cls, ctx, flat):
+        from . import synth
+
+        _, batch, keep = synth.to_ctypes(flat)
+        h = vp()
+        check(bt_gibbs_source_create(ctx.h, flat["S"], C.addressof(batch), C.byref(h)))
+        del keep
+        return cls(ctx, h.value, flat)
+
+    @classmethod
+    def from_paths(cls, ctx, paths, structure):
+        """bt_gibbs_source_create_from_paths: takes the device candidates out of `paths` (Paths.candidates_device); `structure`: synth_graphs.gibbs_structure's dict"""
+        from . import synth
+
+        batch, keep = synth.GibbsBatch(), []
+        batch.num_groups, batch.num_clusters = structure["num_groups"], structure["num_clusters"]
+        for n in synth._BATCH_PTRS:
+            a = structure.get(n)
+            if a is None:
+                continue   # NULL: comes from the paths handle
+            a = np.ascontiguousarray(a if a.size else np.zeros(1, a.dtype))
+            keep.append(a)
+            setattr(batch, n, a.ctypes.data)
+        h = vp()
+        check(bt_gibbs_source_create_from_paths(ctx.h, structure["S"], paths.h, C.addressof(batch), C.byref(h)))
+        return cls(ctx, h.value, structure)
+
+    def fetch(self):
+        """bt_gibbs_source_fetch -> dict of the source's arrays (bt_gibbs_batch's names)"""
+        counts = np.zeros(25, np.uint64)
+        check(bt_gibbs_source_fetch(self.h, _np_ptr(counts), None))
+        arrs = {name: np.zeros(max(int(counts[i]), 1), dt) for i, (name, dt) in enumerate(SOURCE_FIELDS)}
+        out = _SourceArrays()
+        for name, _ in SOURCE_FIELDS:
+            setattr(out, name, arrs[name].ctypes.data)
+        check(bt_gibbs_source_fetch(self.h, _np_ptr(counts), C.byref(out)))
+        return {name: arrs[name][: int(counts[i])] for i, (name, _) in enumerate(SOURCE_FIELDS)}
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(bt_gibbs_source_device_bytes(self.h, C.byref(b)))
+        return b.value
+
+    def _params(self, **kw):
+        from . import synth
+
+        p, _, keep = synth.to_ctypes({"S": self.S, "gender": self.flat["gender"], "num_groups": 0, "num_clusters": 0, **{n: np.zeros(1, np.uint8) for n in synth._BATCH_PTRS}}, **kw)
+        return p, keep
+
+    def state_bytes(self, ids=None, **kw):
+        p, keep = self._params(**kw)
+        ids_a = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+        b = C.c_uint64()
+        check(bt_gibbs_state_bytes_from_source(self.h, C.addressof(p), None if ids_a is None else _np_ptr(ids_a), 0 if ids_a is None else len(ids_a), C.byref(b)))
+        return b.value
+
+    def sampler(self, params, ids=None, lut_g=None, lut_n=None):
+        """bt_gibbs_create_from_source over the groups at positions `ids` of the source (None: all); params: keyword arguments of synth.to_ctypes"""
+        p, keep = self._params(**params)
+        goff = np.asarray(self.flat["group_cluster_off"], np.int64)
+        sel = np.arange(self.G) if ids is None else np.asarray(ids, np.int64)
+        nv = goff[sel + 1] - goff[sel]
+        flat = {"S": self.S, "num_groups": len(sel), "num_clusters": int(nv.sum()), "group_cluster_off": np.concatenate([[0], np.cumsum(nv)]).astype(np.uint32)}
+        ids_a = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+        h = vp()
+        check(bt_gibbs_create_from_source(self.h, self.ctx.h, C.addressof(p), None if ids_a is None else _np_ptr(ids_a), 0 if ids_a is None else len(ids_a), C.byref(h)))
+        g = Gibbs._from_handle(self.ctx, h.value, flat, p, keep)
+        if lut_g is not None:
+            g.set_lut(lut_g, lut_n)
+        return g
+
+    def close(self):
+        if self.h:
+            bt_gibbs_source_destroy(self.h)
             self.h = None

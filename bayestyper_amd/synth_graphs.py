@@ -303,3 +303,19 @@ def gibbs_batch_from_candidates(cand, f, groups, S, gender=None, ploidy=None, cl
                  "multi_off", "multi_idx", "hap_allele", "hapnest_off", "hapnest_idx", "nestdep_off", "nestdep_cluster", "nestdep_var_off", "nestdep_var"):
         out[name] = cand[name]
     return out
+
+
+def gibbs_structure(small, f, groups, S, gender=None, ploidy=None, cluster_ids=None, sources=None, out_edges=None):
+    """The same hand-over with the candidates left on the device (bt_paths_candidates_device): `small` = bt_paths_candidates_fetch_small's arrays; -> the
+    `structure` of bt_gibbs_source_create_from_paths: bt_gibbs_batch's per-group / per-cluster / haplotype / variant / nested-dependency fields, the per-row
+    arrays, index lists, kmer_shared and group_num_shared None (they come from the paths handle)."""
+    rows = ("hap_kmer_mult", "kmer_has_counts", "kmer_counts", "kmer_ic_mult", "kv_off", "kv_var", "kv_bits", "unique_idx", "multi_idx")
+    cand = dict(small)
+    cand.update({n: np.zeros(0, np.uint32) for n in rows})
+    cand["kmer_key"] = np.zeros(0, np.uint64)
+    cand["multi_off"] = np.zeros(f["num_clusters"] + 1, np.uint32)   # (no rows to number here: the device does it)
+    out = gibbs_batch_from_candidates(cand, f, groups, S, gender, ploidy, cluster_ids, sources, out_edges)
+    for n in rows + ("kmer_shared", "group_num_shared"):
+        out[n] = None
+    out["multi_off"] = small["multi_off"]
+    return out

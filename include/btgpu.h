@@ -377,6 +377,16 @@ typedef struct bt_paths_candidates_sizes {
  * table: computes the bundle on the device + host and reports its sizes; bt_paths_candidates_fetch copies it out. */
 int bt_paths_candidates(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes);
 int bt_paths_candidates_fetch(bt_paths *p, bt_paths_candidates_out *out);
+/* The same bundle with every per-row / per-entry array LEFT IN DEVICE MEMORY, owned by `p`: hap_kmer_mult, kmer_key, kmer_has_counts, kmer_counts,
+ * kmer_ic_mult, kv_off, kv_var, kv_bits, unique_idx, multi_idx.  The reference builds the bundle inside the genotyper and hands it over in memory
+ * (VariantClusterGenotyper.cpp:59-106 <- VariantClusterGraph.cpp:941-1135); here bt_gibbs_source_create_from_paths takes these arrays over without a pass
+ * through the host.  Only the [C+1] offset arrays and what the host graph walk gives (hap_allele, hapnest_*, nestdep_*: VariantClusterGraph.cpp:984-1017,
+ * 1093-1132) exist on the host: bt_paths_candidates_fetch_small copies them out (the per-row pointers of `out` must be NULL); it also works after
+ * bt_paths_candidates.  bt_paths_candidates = this call + copies to the host.  The incidence lists (updateVariantPathIndices, :1137-1184) are built per
+ * row without a global sort: with BT_PATHS_DEBUG set, a line on stderr tells how many rows each of the three row kernels took (BT_PATHS_ROW_LANE_MAX /
+ * BT_PATHS_ROW_WAVE_MAX lower their thresholds of 8 / 64 triples for tests). */
+int bt_paths_candidates_device(bt_paths *p, bt_table *table, bt_paths_candidates_sizes *sizes);
+int bt_paths_candidates_fetch_small(bt_paths *p, bt_paths_candidates_out *out);
 
 /* ------------------------------------------------------------------------------------------
  * Best-path search per sample: VariantClusterGraph::{findSamplePaths, mergePaths, isPathsRedundant, filterPaths, addPathIndices}
@@ -487,6 +497,33 @@ int bt_gibbs_destroy(bt_gibbs *g);
  * bt_gibbs_create(batch) = source + sampler over all groups + source released. */
 typedef struct bt_gibbs_source bt_gibbs_source;
 int bt_gibbs_source_create(bt_ctx *ctx, uint32_t num_samples, const bt_gibbs_batch *batch, bt_gibbs_source **out);
+/* The source of a unit whose candidates are on the device already (bt_paths_candidates_device): what VariantClusterGroup::initGenotyper does when it hands
+ * getHaplotypeCandidates' bundle to the genotyper (VariantClusterGenotyper.cpp:59-106), with no host copy in between.  `structure` carries the per-group,
+ * per-cluster, haplotype, variant and nested-dependency fields of bt_gibbs_batch (host memory; hap_allele / hapnest_* / nestdep_* as
+ * bt_paths_candidates_fetch_small gives them); its per-row pointers, index lists, kmer_shared and group_num_shared must be NULL and come
+ * from `p`, as kmer_off / unique_off / multi_off do (ignored here).  Cluster c of `structure` is cluster c of `p`.  The source TAKES the device arrays out of `p` (`p`
+ * afterwards holds no candidates).  kmer_shared / group_num_shared are computed on the device: inside a group, walking its clusters in vertex order and
+ * each cluster's multi_idx in order, distinct k-mers are numbered by first occurrence (KmerCounter.cpp:607-616).  On an error `p` keeps its candidates. */
+int bt_gibbs_source_create_from_paths(bt_ctx *ctx, uint32_t num_samples, bt_paths *p, const bt_gibbs_batch *structure, bt_gibbs_source **out);
+/* host arrays receiving a source's flat device arrays (NULL: skipped), in bt_gibbs_batch's layout, followed by the [G] / [C+1] arrays the source keeps on the host */
+typedef struct bt_gibbs_source_arrays {
+    uint8_t *group_ploidy;
+    uint32_t *group_sources, *edges;
+    uint8_t *hap_kmer_mult, *kmer_has_counts, *kmer_counts, *kmer_ic_mult;
+    int32_t *kmer_shared;
+    uint32_t *kv_off;
+    uint16_t *kv_var;
+    uint32_t *kv_bits, *unique_idx, *multi_idx;
+    uint16_t *hap_allele;
+    uint32_t *hapnest_off, *hapnest_idx;
+    uint16_t *var_num_alleles;
+    uint8_t *var_has_dependency;
+    uint32_t *nestdep_cluster, *nestdep_var_off;
+    uint16_t *nestdep_var;
+    uint32_t *group_num_shared, *kmer_off, *unique_off, *multi_off;
+} bt_gibbs_source_arrays;
+/* diagnostic: h_counts[25] = number of elements of each of the 25 arrays above, in that order; out != NULL: the arrays are copied to the host (any source) */
+int bt_gibbs_source_fetch(bt_gibbs_source *src, uint64_t *h_counts, const bt_gibbs_source_arrays *out);
 int bt_gibbs_source_destroy(bt_gibbs_source *src);
 int bt_gibbs_source_device_bytes(bt_gibbs_source *src, uint64_t *bytes);
 int bt_gibbs_create_from_source(bt_gibbs_source *src, bt_ctx *ctx, const bt_gibbs_params *params, const uint32_t *group_ids, uint32_t num_groups, bt_gibbs **out);
