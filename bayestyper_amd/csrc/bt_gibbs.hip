@@ -13,6 +13,7 @@
 #ifndef BT_SWEEP_OUTLINE
 #define BT_SWEEP_INLINE   // the per-visit sweep functions are part of the kernel body (bt_rng_device.hpp: BT_SWEEPFN)
 #endif
+#include "bt_genotypes.hpp"
 #include "bt_gibbs_kernel.hpp"
 #include "bt_internal.hpp"
 
@@ -204,6 +205,100 @@ __global__ __launch_bounds__(64) void wire_sizes_kernel(const uint64_t *__restri
     if (c >= num_clusters) return;
     sizes[2 * c] = (uint32_t)(dip_off[c + 1] - dip_off[c]);
     sizes[2 * c + 1] = (uint32_t)(cell_off[c + 1] - cell_off[c]);
+}
+
+// ---- genotype posteriors of a launch computed ON THE DEVICE (bt_gibbs_genotypes; the summary code is bt_genotypes.hpp, shared with the host) ----
+// Lane mapping: one lane per (variant, sample) CELL of the launch, a flat index over all clusters — not one wavefront per cluster, which leaves 61 of 64
+// lanes idle on the two-haplotype, one-variant clusters at S = 3 that are 88 % of a unit.  Each lane walks its own cluster's diplotype table where the
+// sampler left it (dip_keys / dip_freq, nothing is packed first) and accumulates straight into its sample record of the output string; the lanes of a
+// cluster's cells read the same table words (one request).  A second kernel, one lane per variant, derives the variant statistics from the records.
+// per cluster: record sizes of its variants, the variant -> cluster map, and the flags [0] a table overflowed, [1] something was collected
+__global__ __launch_bounds__(256) void geno_sizes_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const ClusterLoc *__restrict__ loc, uint32_t num_clusters,
+                                                         uint32_t S, const uint32_t *__restrict__ cluster_var_off, uint32_t *__restrict__ var_cluster,
+                                                         unsigned long long *__restrict__ sizes, uint32_t *__restrict__ flags, unsigned long long *__restrict__ num_entries) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= num_clusters) return;
+    const Vx x = result_vx(tiles, pool, loc[c]);
+    SPtrF<uint32_t, LANES> sc = x.sc();
+    if (sc[SC_DIP_OVERFLOW]) atomicOr(&flags[0], 1u);
+    if (sc[SC_DIP_ENTRIES]) atomicOr(&flags[1], 1u);
+    if (num_entries) atomicAdd(num_entries, (unsigned long long)sc[SC_DIP_ENTRIES]);   // (BT_GIBBS_DEBUG: the size bt_gibbs_result_words' string would have)
+    TPtr<uint8_t> gp = x.t.arr<uint8_t>(A_PLOIDY);
+    const uint32_t v0 = cluster_var_off[c], V = cluster_var_off[c + 1] - v0;
+    for (uint32_t v = 0; v < V; ++v) {
+        const uint32_t A = x.var_na(v);
+        unsigned long long n = btgeno::variant_head_words(A);
+        for (uint32_t s = 0; s < S; ++s) n += btgeno::sample_words(A, gp[s]);
+        sizes[v0 + v] = n;
+        var_cluster[v0 + v] = c;
+    }
+}
+// one lane per (variant, sample) cell.  A cell whose sample collected fewer than `ordered_from` sweeps (btgeno::kOrderFreeBelow unless lowered for tests)
+// visits the table's slots as they lie: all genotype sums are then integers that never compare equal unless they are equal, and the result does not
+// depend on the order.  Any other cell visits the entries in the order bt_gibbs_result_fetch hands them out — ascending (h1, h2), 0xFFFF last, as
+// result_pack_kernel ranks them — by selection (next larger key; no memory), so the running maximum sees what the host's sees.
+__global__ __launch_bounds__(256) void geno_cell_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const ClusterLoc *__restrict__ loc, uint32_t num_variants, uint32_t S,
+                                                        const uint32_t *__restrict__ cluster_var_off, const uint32_t *__restrict__ var_cluster, const uint32_t *__restrict__ var_off,
+                                                        uint32_t *__restrict__ words, float min_gpp, float min_kmers, const float *__restrict__ min_fraction, uint32_t ordered_from,
+                                                        uint32_t *__restrict__ num_ordered) {
+    const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (idx >= (uint64_t)num_variants * S) return;
+    const uint32_t gv = (uint32_t)(idx / S), s = (uint32_t)(idx - (uint64_t)gv * S);
+    const uint32_t c = var_cluster[gv], v = gv - cluster_var_off[c];
+    const Vx x = result_vx(tiles, pool, loc[c]);
+    const uint32_t A = x.var_na(v);
+    TPtr<uint8_t> gp = x.t.arr<uint8_t>(A_PLOIDY);
+    uint64_t at = btgeno::variant_head_words(A);
+    for (uint32_t s2 = 0; s2 < s; ++s2) at += btgeno::sample_words(A, gp[s2]);
+    TPtr<uint32_t> keys = x.dip_keys(), freq = x.dip_freq();
+    const uint32_t cap = x.d().dip_cap;
+    uint32_t collected = 0;
+    for (uint32_t slot = 0; slot < cap; ++slot)
+        if (keys[slot]) collected += freq[slot * S + s];
+    const bool ordered = collected >= ordered_from;
+    if (ordered) atomicAdd(num_ordered, 1u);
+    auto entries = [&](auto add) {
+        if (!ordered) {
+            for (uint32_t slot = 0; slot < cap; ++slot) {
+                const uint32_t tag = keys[slot];
+                if (!tag) continue;
+                const uint32_t key = tag == 0xFFFFFFFFu ? 0xFFFFFFFFu : tag - 1u;
+                add((uint16_t)(key & 0xFFFFu), (uint16_t)(key >> 16), freq[slot * S + s]);
+            }
+            return;
+        }
+        long long prev = -1;
+        for (;;) {
+            long long next = 1ll << 32;
+            uint32_t at_slot = 0;
+            for (uint32_t slot = 0; slot < cap; ++slot) {
+                const uint32_t tag = keys[slot];
+                if (!tag) continue;
+                const uint32_t key = tag == 0xFFFFFFFFu ? 0xFFFFFFFFu : tag - 1u;
+                const long long ok = (long long)((key << 16) | (key >> 16));   // (h1, h2) lexicographic: h1 in the upper half
+                if (ok > prev && ok < next) {
+                    next = ok;
+                    at_slot = slot;
+                }
+            }
+            if (next == (1ll << 32)) break;
+            add((uint16_t)((uint32_t)next >> 16), (uint16_t)((uint32_t)next & 0xFFFFu), freq[at_slot * S + s]);
+            prev = next;
+        }
+    };
+    auto allele_of = [&](uint16_t h) -> uint16_t { return h != btgeno::NONE ? x.hap_allele(h, v) : (uint16_t)(A - 1u); };
+    auto stat = [&](uint32_t a, uint32_t i) -> double { return x.astats(s, v, a)[i]; };
+    btgeno::sample_record(words + var_off[gv] + at, A, gp[s], entries, allele_of, stat, min_gpp, min_kmers, min_fraction[s]);
+}
+// one lane per variant, after geno_cell_kernel: the variant's statistics and non-covered alleles
+__global__ __launch_bounds__(256) void geno_variant_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const ClusterLoc *__restrict__ loc, uint32_t num_variants, uint32_t S,
+                                                           const uint32_t *__restrict__ cluster_var_off, const uint32_t *__restrict__ var_cluster, const uint32_t *__restrict__ var_off,
+                                                           uint32_t *__restrict__ words) {
+    const uint32_t gv = blockIdx.x * 256u + threadIdx.x;
+    if (gv >= num_variants) return;
+    const uint32_t c = var_cluster[gv], v = gv - cluster_var_off[c];
+    const Vx x = result_vx(tiles, pool, loc[c]);
+    btgeno::variant_record(words + var_off[gv], x.var_na(v), x.var_dep(v) != 0, S, x.H, [&](uint32_t h) { return x.hap_allele(h, v); });
 }
 
 // ---- the noise model's update of one iteration (bt_gibbs_noise_chain) ----------------------------------------------------------------
@@ -555,6 +650,9 @@ struct bt_gibbs {
     uint32_t *d_trace = nullptr, *d_trace_counter = nullptr;
     uint32_t *d_wire = nullptr;   // bt_gibbs_result_words' string
     uint64_t wire_cap = 0;
+    uint32_t *d_geno = nullptr;   // bt_gibbs_genotypes' string
+    uint64_t geno_cap = 0;
+    std::vector<uint32_t> h_var_off;   // [C+1] first variant of every cluster among the launch's variants
     uint64_t trace_words = 0;
     // bt_gibbs_noise_iteration: pinned staging of the histogram (device -> host) and of the noise table (host -> device), device histogram
     uint64_t *h_pin_hist = nullptr, *d_iter_hist = nullptr;
@@ -1226,6 +1324,8 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
     } while (0)
 
     g->h_A.assign(C, 0);
+    g->h_var_off.assign((size_t)C + 1, 0);
+    for (uint32_t c = 0; c < C; ++c) g->h_var_off[c + 1] = g->h_var_off[c] + cd[c].V;
     uint64_t flat_sel = 0;   // bytes of the selected groups' slices of the flat arrays (bt_gibbs_state_bytes: what a create from a host batch uploads next to the pool)
     for (uint32_t c = 0; c < C; ++c) {
         g->h_A[c] = cd[c].A;
@@ -2241,6 +2341,7 @@ int bt_gibbs_destroy(bt_gibbs *g) {
     if (g->d_trace) (void)hipFree(g->d_trace);
     if (g->d_trace_counter) (void)hipFree(g->d_trace_counter);
     if (g->d_wire) (void)hipFree(g->d_wire);
+    if (g->d_geno) (void)hipFree(g->d_geno);
     {
         const size_t nh = (size_t)g->S * 256;
         if (g->recycles) {
@@ -3002,6 +3103,102 @@ int bt_gibbs_result_words(bt_gibbs *g, const uint32_t **d_words, uint64_t *num_w
     return BT_OK;
 }
 
+// The genotype summaries of the launch as ONE word string in device memory (layout: include/btgpu.h; records: bt_genotypes.hpp).  Uploaded: the filters and the
+// offset tables; everything else is read where the sampler keeps it.  The sampler's state is not touched.
+int bt_gibbs_genotypes(bt_gibbs *g, const bt_genotype_filters *f, const uint32_t **d_words, uint64_t *num_words) {
+    if (!g || !f || !f->min_fraction_observed_kmers || !d_words || !num_words) return fail("bt_gibbs_genotypes: null argument");
+    if (chain_in_flight(g)) return fail("bt_gibbs_genotypes: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
+    BT_HIP(hipSetDevice(g->ctx->device));
+    hipStream_t st = g->ctx->stream;
+    const uint32_t C = g->C, S = g->S, NV = g->h_var_off[C];
+    if (C == 0) return fail("bt_gibbs_genotypes: nothing was collected yet (no collected sweep has run)");
+    // one temporary block: record sizes u64 [NV] + the diplotype entries of all clusters u64 | cluster_var_off [C+1] | var_cluster [NV] | flags [4] | min_fraction f32 [S]
+    void *d_tmp = nullptr;
+    struct Free {
+        void *&p;
+        ~Free() {
+            if (p) (void)hipFree(p);
+        }
+    } fr{d_tmp};
+    const bool debug = getenv("BT_GIBBS_DEBUG") != nullptr;
+    const size_t tmp_words = 2 * ((size_t)NV + 1) + ((size_t)C + 1) + NV + 4 + S;
+    BT_HIP(hipMalloc(&d_tmp, tmp_words * 4));
+    unsigned long long *d_sizes = (unsigned long long *)d_tmp;
+    uint32_t *d_cvo = (uint32_t *)(d_sizes + NV + 1), *d_var_cluster = d_cvo + C + 1, *d_flags = d_var_cluster + NV;
+    float *d_minfrac = (float *)(d_flags + 4);
+    BT_HIP(hipMemcpyAsync(d_cvo, g->h_var_off.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, st));
+    BT_HIP(hipMemcpyAsync(d_minfrac, f->min_fraction_observed_kmers, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    BT_HIP(hipMemsetAsync(d_flags, 0, 16, st));
+    BT_HIP(hipMemsetAsync(d_sizes + NV, 0, 8, st));
+    hipLaunchKernelGGL(geno_sizes_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const TileDesc *)g->d_tiles, g->d_pool, (const ClusterLoc *)g->d_loc, C, S, (const uint32_t *)d_cvo,
+                       d_var_cluster, d_sizes, d_flags, debug ? d_sizes + NV : (unsigned long long *)nullptr);
+    BT_CHECK_LAUNCH();
+    std::vector<unsigned long long> sizes((size_t)NV + 1);
+    uint32_t flags[4] = {0, 0, 0, 0};
+    BT_HIP(hipMemcpyAsync(sizes.data(), d_sizes, ((size_t)NV + 1) * 8, hipMemcpyDeviceToHost, st));
+    BT_HIP(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, st));
+    BT_HIP(hipStreamSynchronize(st));
+    if (flags[0]) return fail("bt_gibbs_genotypes: diplotype frequency table overflowed");
+    if (!flags[1]) return fail("bt_gibbs_genotypes: nothing was collected yet (no collected sweep has run)");
+    // [C, variants, S, 0]  cluster_var_off [C+1]  var_off [variants+1]  (one pad word if odd)  records
+    const uint64_t at_cvo = 4, at_voff = at_cvo + C + 1, at_rec = (at_voff + NV + 1 + 1) & ~1ull;
+    std::vector<uint32_t> head(at_rec, 0);
+    head[0] = C;
+    head[1] = NV;
+    head[2] = S;
+    std::memcpy(head.data() + at_cvo, g->h_var_off.data(), ((size_t)C + 1) * 4);
+    uint64_t total = at_rec;
+    for (uint32_t v = 0; v < NV; ++v) {
+        head[at_voff + v] = (uint32_t)total;
+        total += sizes[v];
+        if (total >> 32) return fail("bt_gibbs_genotypes: more than 2^32 words in one launch");
+    }
+    head[at_voff + NV] = (uint32_t)total;
+    uint32_t *grown = nullptr;   // an error below leaves nothing allocated that was not allocated before
+    if (g->geno_cap < total) {
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&grown), total * 4));
+    }
+    struct Undo {
+        uint32_t *&p;
+        ~Undo() {
+            if (p) (void)hipFree(p);
+        }
+    } undo{grown};
+    uint32_t *w = grown ? grown : g->d_geno;
+    BT_HIP(hipMemcpyAsync(w, head.data(), at_rec * 4, hipMemcpyHostToDevice, st));
+    uint32_t ordered_from = btgeno::kOrderFreeBelow;
+    if (const char *e = getenv("BT_GENOTYPES_ORDERED_FROM")) ordered_from = std::min<uint32_t>(ordered_from, (uint32_t)std::strtoul(e, nullptr, 10));   // tests: lower the threshold
+    const uint64_t cells = (uint64_t)NV * S;
+    if (cells) {
+        if ((cells + 255) / 256 >> 31) return fail("bt_gibbs_genotypes: more than 2^32 words in one launch");
+        hipLaunchKernelGGL(geno_cell_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const TileDesc *)g->d_tiles, g->d_pool, (const ClusterLoc *)g->d_loc, NV, S,
+                           (const uint32_t *)d_cvo, (const uint32_t *)d_var_cluster, (const uint32_t *)(w + at_voff), w, f->min_genotype_posterior, f->min_number_of_kmers,
+                           (const float *)d_minfrac, ordered_from, d_flags + 2);
+        BT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(geno_variant_kernel, dim3((NV + 255) / 256), dim3(256), 0, st, (const TileDesc *)g->d_tiles, g->d_pool, (const ClusterLoc *)g->d_loc, NV, S, (const uint32_t *)d_cvo,
+                           (const uint32_t *)d_var_cluster, (const uint32_t *)(w + at_voff), w);
+        BT_CHECK_LAUNCH();
+    }
+    if (debug) BT_HIP(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, st));
+    BT_HIP(hipStreamSynchronize(st));
+    if (debug) {
+        uint64_t cells12 = 0;   // what bt_gibbs_result_words would hand out for the same launch
+        for (uint32_t c = 0; c < C; ++c) cells12 += (uint64_t)S * g->h_A[c];
+        const uint64_t nd = sizes[NV], wire = ((4 + 2ull * C + nd * (1ull + S) + 1) & ~1ull) + cells12 * 24;
+        fprintf(stderr, "bt_gibbs_genotypes: %u clusters, %u variants, %llu cells (%u walked in (h1, h2) order, ordered from %u collected sweeps), %llu words (bt_gibbs_result_words: %llu words)\n",
+                C, NV, (unsigned long long)cells, flags[2], ordered_from, (unsigned long long)total, (unsigned long long)wire);
+    }
+    if (grown) {
+        if (g->d_geno) (void)hipFree(g->d_geno);
+        g->d_geno = grown;
+        g->geno_cap = total;
+        grown = nullptr;
+    }
+    *d_words = g->d_geno;
+    *num_words = total;
+    return BT_OK;
+}
+
 int bt_gibbs_trace_enable(bt_gibbs *g, uint32_t max_sweeps) {
     if (!g) return fail("bt_gibbs_trace_enable: null handle");
     if (chain_in_flight(g)) return fail("bt_gibbs_trace_enable: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
@@ -3109,6 +3306,53 @@ int bt_diag_prof(unsigned long long *h_out16, int reset) {
     return BT_OK;
 }
 #endif
+
+// bt_gibbs_genotypes' records for ONE cluster given on the host as bth_cluster_genotypes takes it (entries in bt_gibbs_result_fetch's order), computed by the
+// same __host__ __device__ code the kernels run: h_words receives the string of a launch of this one cluster (*num_words; capacity checked)
+int bt_diag_genotype_cluster(uint32_t S, uint32_t H, uint32_t V, const uint16_t *hap_allele, const uint16_t *var_num_alleles, const uint8_t *var_has_dependency,
+                             uint64_t num_diplotypes, const uint16_t *h1, const uint16_t *h2, const uint32_t *freq, const double *stats, const uint8_t *ploidy,
+                             const bt_genotype_filters *f, uint32_t *h_words, uint64_t capacity, uint64_t *num_words) {
+    if (!var_num_alleles || !var_has_dependency || !ploidy || !f || !f->min_fraction_observed_kmers || !num_words || (V && H && !hap_allele) || (num_diplotypes && (!h1 || !h2 || !freq)) ||
+        (V && S && !stats))
+        return fail("bt_diag_genotype_cluster: null argument");
+    const uint64_t at_voff = 4 + 2, at_rec = (at_voff + V + 1 + 1) & ~1ull;
+    std::vector<uint64_t> var_off((size_t)V + 1);
+    std::vector<uint32_t> allele_base((size_t)V + 1, 0);
+    uint64_t total = at_rec;
+    for (uint32_t v = 0; v < V; ++v) {
+        var_off[v] = total;
+        total += btgeno::variant_head_words(var_num_alleles[v]);
+        for (uint32_t s = 0; s < S; ++s) total += btgeno::sample_words(var_num_alleles[v], ploidy[s]);
+        allele_base[v + 1] = allele_base[v] + var_num_alleles[v];
+    }
+    var_off[V] = total;
+    *num_words = total;
+    if (total >> 32) return fail("bt_diag_genotype_cluster: more than 2^32 words");
+    if (!h_words || capacity < total) return fail("bt_diag_genotype_cluster: buffer too small");
+    std::fill(h_words, h_words + at_rec, 0u);
+    h_words[0] = 1;
+    h_words[1] = V;
+    h_words[2] = S;
+    h_words[5] = V;
+    for (uint32_t v = 0; v <= V; ++v) h_words[at_voff + v] = (uint32_t)var_off[v];
+    const uint32_t A_total = allele_base[V];
+    for (uint32_t v = 0; v < V; ++v) {
+        const uint32_t A = var_num_alleles[v];
+        uint32_t *rec = h_words + var_off[v];
+        uint64_t at = btgeno::variant_head_words(A);
+        for (uint32_t s = 0; s < S; ++s) {
+            auto entries = [&](auto add) {
+                for (uint64_t e = 0; e < num_diplotypes; ++e) add(h1[e], h2[e], freq[e * S + s]);
+            };
+            auto allele_of = [&](uint16_t h) -> uint16_t { return h != btgeno::NONE ? hap_allele[(size_t)h * V + v] : (uint16_t)(A - 1u); };
+            auto stat = [&](uint32_t a, uint32_t i) -> double { return stats[((size_t)s * A_total + allele_base[v] + a) * 12 + i]; };
+            btgeno::sample_record(rec + at, A, ploidy[s], entries, allele_of, stat, f->min_genotype_posterior, f->min_number_of_kmers, f->min_fraction_observed_kmers[s]);
+            at += btgeno::sample_words(A, ploidy[s]);
+        }
+        btgeno::variant_record(rec, A, var_has_dependency[v] != 0, S, H, [&](uint32_t h) { return hap_allele[(size_t)h * V + v]; });
+    }
+    return BT_OK;
+}
 
 int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint64_t n, double *h_out) {
     if (!h_out) return fail("bt_diag_rng: null argument");

@@ -1,7 +1,10 @@
 #include "Genotypes.hpp"
 
+#include "../csrc/bt_genotypes.hpp"
+
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <sstream>
 #include <stdexcept>
@@ -165,14 +168,26 @@ std::string formatAlleleCover(const VariantGenotypes &g) {
 std::string formatVariantStatsColumns(const VariantGenotypes &g) { return formatQualityFilterAndStats(g) + formatAlleleCover(g); }
 
 std::string formatSampleColumns(const ClusterResults &r, uint32_t variant, const VariantGenotypes &g) {
-    std::ostringstream o;
     uint32_t allele_base = 0, A_total = 0;
     for (uint32_t v = 0; v < r.V; ++v) {
         if (v < variant) allele_base += r.var_num_alleles[v];
         A_total += r.var_num_alleles[v];
     }
     const uint32_t A = r.var_num_alleles[variant];
-    for (uint32_t s = 0; s < r.S; ++s) {
+    std::vector<double> means((size_t)r.S * A * 3);
+    for (uint32_t s = 0; s < r.S; ++s)
+        for (uint32_t a = 0; a < A; ++a) {
+            const double *cell = r.stats + ((size_t)s * A_total + allele_base + a) * 12;
+            auto mean_of = [](const double *ks) { return ks[0] == 0 ? -1.0 : ks[2]; };   // KmerStats::getMean (KmerStats.cpp:82-92)
+            for (uint32_t k = 0; k < 3; ++k) means[((size_t)s * A + a) * 3 + k] = mean_of(cell + 4 * k);
+        }
+    return formatSampleColumns(g, A, means.data());
+}
+
+std::string formatSampleColumns(const VariantGenotypes &g, uint32_t A, const double *means) {
+    std::ostringstream o;
+    const uint32_t S = (uint32_t)g.sample_stats.size();
+    for (uint32_t s = 0; s < S; ++s) {
         const SampleStats &st = g.sample_stats[s];
         o << "\t";
         if (st.genotype_estimate.empty()) {
@@ -190,25 +205,83 @@ std::string formatSampleColumns(const ClusterResults &r, uint32_t variant, const
         writeAlleleField(o, st.allele_posteriors);
         o << ":";
         {   // writeAlleleKmerStats: the means of the count / fraction / mean statistics per allele, -1 when nothing was added
-            std::ostringstream counts, fractions, means;
+            std::ostringstream counts, fractions, kmer_means;
             for (uint32_t a = 0; a < A; ++a) {
-                const double *cell = r.stats + ((size_t)s * A_total + allele_base + a) * 12;
-                auto mean_of = [](const double *ks) { return ks[0] == 0 ? -1.0 : ks[2]; };   // KmerStats::getMean (KmerStats.cpp:82-92)
+                const double *m = means + ((size_t)s * A + a) * 3;
                 if (a) {
                     counts << ",";
                     fractions << ",";
-                    means << ",";
+                    kmer_means << ",";
                 }
-                counts << mean_of(cell);
-                fractions << mean_of(cell + 4);
-                means << mean_of(cell + 8);
+                counts << m[0];
+                fractions << m[1];
+                kmer_means << m[2];
             }
-            o << counts.str() << ":" << fractions.str() << ":" << means.str();
+            o << counts.str() << ":" << fractions.str() << ":" << kmer_means.str();
         }
         o << ":";
         writeAlleleField(o, st.allele_filters);
     }
     return o.str();
+}
+
+uint32_t genotypeQuality(float best_value) {
+    if (floatCompare(best_value, 1)) return 99;
+    if (floatCompare(best_value, 0)) return 0;
+    return (uint32_t)(-10 * std::log10(1 - best_value));
+}
+
+DecodedVariant decodeGenotypeRecord(const uint32_t *rec, uint32_t S) {
+    DecodedVariant d;
+    auto as_float = [](uint32_t w) {
+        float f;
+        std::memcpy(&f, &w, 4);
+        return f;
+    };
+    const uint32_t A = rec[0];
+    if (A == 0) throw std::runtime_error("genotype string: a variant without alleles");
+    d.A = A;
+    VariantStats &vs = d.genotypes.variant_stats;
+    vs.total_count = rec[1];
+    vs.max_alt_allele_call_probability = as_float(rec[2]);
+    vs.alt_allele_counts.assign(A - 1, 0);
+    vs.alt_allele_frequency.assign(A - 1, 0.f);
+    vs.allele_call_probabilities.assign(A, 0.f);
+    const uint32_t *al = rec + btgeno::kVariantHead;
+    for (uint32_t a = 0; a < A; ++a) {
+        vs.allele_call_probabilities[a] = as_float(al[4 * a]);
+        if (a) {
+            vs.alt_allele_counts[a - 1] = al[4 * a + 1];
+            vs.alt_allele_frequency[a - 1] = as_float(al[4 * a + 2]);
+        }
+        if (al[4 * a + 3]) d.genotypes.non_covered_alleles.push_back((uint16_t)a);
+    }
+    d.means.resize((size_t)S * A * 3);
+    const uint32_t *sr = rec + btgeno::variant_head_words(A);
+    d.genotypes.sample_stats.resize(S);
+    for (uint32_t s = 0; s < S; ++s) {
+        SampleStats &st = d.genotypes.sample_stats[s];
+        const uint32_t ploidy = sr[0];
+        if (ploidy > 2) throw std::runtime_error("genotype string: a ploidy above 2");
+        const uint64_t G = btgeno::num_genotypes(A, ploidy);
+        const uint32_t Ap = ploidy ? A : 0;
+        if (ploidy >= 1) st.genotype_estimate.push_back((uint16_t)(sr[1] & 0xFFFFu));
+        if (ploidy == 2) st.genotype_estimate.push_back((uint16_t)(sr[1] >> 16));
+        st.genotype_quality = genotypeQuality(as_float(sr[2]));
+        st.genotype_posteriors.resize(G);
+        st.allele_posteriors.resize(Ap);
+        st.allele_filters.resize(Ap);
+        const uint32_t *p = sr + btgeno::kSampleHead;
+        for (uint64_t i = 0; i < G; ++i) st.genotype_posteriors[i] = as_float(p[i]);
+        for (uint32_t a = 0; a < Ap; ++a) {
+            st.allele_posteriors[a] = as_float(p[G + a]);
+            st.allele_filters[a] = (uint16_t)p[G + Ap + a];
+        }
+        std::memcpy(d.means.data() + (size_t)s * A * 3, sr + btgeno::sample_means_at(A, ploidy), (size_t)A * 24);
+        sr += btgeno::sample_words(A, ploidy);
+    }
+    d.words = (uint64_t)(sr - rec);
+    return d;
 }
 
 }  // namespace bthost

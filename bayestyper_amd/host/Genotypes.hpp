@@ -65,5 +65,21 @@ std::string formatVariantStatsColumns(const VariantGenotypes &g);
 std::string formatQualityFilterAndStats(const VariantGenotypes &g);   // "<QUAL>\t<FILTER>\tAC=..;AF=..;AN=..;ACP=.."
 std::string formatAlleleCover(const VariantGenotypes &g);             // ";ANC=.." or ""
 std::string formatSampleColumns(const ClusterResults &r, uint32_t variant, const VariantGenotypes &g);
+// the same text from the three k-mer means per (sample, allele) — KmerStats::getMean of the count / fraction / mean statistics, means[(s * A + a) * 3 + k] —
+// instead of a cluster's statistics (what bt_gibbs_genotypes' string carries)
+std::string formatSampleColumns(const VariantGenotypes &g, uint32_t A, const double *means);
+
+// GQ from the best genotype posterior (VariantClusterGenotyper.cpp:372-388), as getGenotypes computes it
+uint32_t genotypeQuality(float best_value);
+
+// One variant record of bt_gibbs_genotypes' word string (include/btgpu.h; bayestyper_amd/csrc/bt_genotypes.hpp) as the structures the formatters take.
+// GQ is derived here, on the host, from the record's best posterior.
+struct DecodedVariant {
+    VariantGenotypes genotypes;
+    uint32_t A = 0;
+    std::vector<double> means;   // [S][A][3]
+    uint64_t words = 0;          // length of the record
+};
+DecodedVariant decodeGenotypeRecord(const uint32_t *record, uint32_t S);
 
 }  // namespace bthost

@@ -156,6 +156,10 @@ struct GpuSampler : GibbsSampler {
         check(bt_gibbs_result_words(g, d_words, num_words), "bt_gibbs_result_words");
         return true;
     }
+    bool genotypeWords(const bt_genotype_filters &filters, const uint32_t **d_words, uint64_t *num_words) override {
+        check(bt_gibbs_genotypes(g, &filters, d_words, num_words), "bt_gibbs_genotypes");
+        return true;
+    }
     BatchResults results(uint32_t num_clusters) override {
         BatchResults r;
         uint64_t nd = 0, nc = 0;
@@ -498,6 +502,27 @@ void InferenceEngine::runDefault(const GibbsBatchData &batch, const CountDistrib
 void InferenceEngine::handOver(std::unique_ptr<Sampler> &sampler, const GibbsBatchData &batch, const Collector &collect) {
     const uint32_t *d_words = nullptr;
     uint64_t num_words = 0;
+    if (geno_collect || geno_wire) {
+        if (geno_min_fraction.size() != gender.size()) throw std::runtime_error("InferenceEngine: one min_fraction_observed_kmers per sample");
+        // (the stage is only listed when this route was taken: a sampler without the summaries falls through to the sample route and its labels)
+        const char *label = geno_wire ? "genotypes on the device (bt_gibbs_genotypes, string stays on the device)" : "genotypes on the device (bt_gibbs_genotypes + one copy)";
+        const auto t0 = std::chrono::steady_clock::now();
+        const bt_genotype_filters f{geno_min_gpp, geno_min_kmers, geno_min_fraction.data()};
+        if (sampler->genotypeWords(f, &d_words, &num_words)) {
+            std::vector<uint32_t> words;
+            if (geno_wire) geno_wire(batch, d_words, num_words);
+            else {
+                words.resize(num_words);
+                if (num_words && bt_memcpy_d2h(ctx, words.data(), d_words, num_words * 4) != BT_OK) throw std::runtime_error(std::string("bt_memcpy_d2h: ") + bt_last_error());
+            }
+            sampler.reset();
+            StageTimes::get().add(label, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            if (!geno_wire) geno_collect(batch, words);
+            return;
+        }
+        d_words = nullptr;
+        num_words = 0;
+    }
     if (wire_collect) {
         StageScope stage("Gibbs: result string (device pack, stays on the device)");
         if (sampler->resultWords(&d_words, &num_words)) {

@@ -100,6 +100,9 @@ struct GibbsSampler {
     virtual BatchResults results(uint32_t num_clusters) = 0;
     // the same results as one word string in the sampler's DEVICE memory (bt_gibbs_result_words; valid while the sampler lives); false: not supported
     virtual bool resultWords(const uint32_t ** /*d_words*/, uint64_t * /*num_words*/) { return false; }
+    // the launch's genotype summaries computed on the sampler's side, as one word string in its DEVICE memory (bt_gibbs_genotypes; valid while the sampler
+    // lives); false: not supported — the caller then takes the samples (results / resultWords) and summarises them on the host
+    virtual bool genotypeWords(const bt_genotype_filters & /*filters*/, const uint32_t ** /*d_words*/, uint64_t * /*num_words*/) { return false; }
 };
 typedef std::function<std::unique_ptr<GibbsSampler>(const bt_gibbs_params &, const GibbsBatchData &)> SamplerFactory;
 
@@ -111,6 +114,19 @@ class InferenceEngine {
     // keeps on the device for the gather to rank 0.  Used instead of the Collector whenever it is set and the sampler has the string.
     typedef std::function<void(const GibbsBatchData &batch, const uint32_t *d_words, uint64_t num_words)> WireCollector;
     void setWireCollector(WireCollector w) { wire_collect = std::move(w); }
+    // The device route of collectGenotypes: with a genotype collector registered, a finished launch hands over its genotype summaries
+    // (GibbsSampler::genotypeWords with these filters) instead of its samples — on the host after ONE device-to-host copy of the string (`on_host`), or, for a
+    // run of several ranks, still on the device (`on_device`, which the caller appends to the strings it gathers).  A sampler without the summaries
+    // (the CPU tests' samplers) takes the sample route above.  min_fraction_observed_kmers: one per sample.
+    typedef std::function<void(const GibbsBatchData &batch, const std::vector<uint32_t> &words)> GenotypeCollector;
+    void setGenotypeCollector(float min_genotype_posterior, float min_number_of_kmers, std::vector<float> min_fraction_observed_kmers, GenotypeCollector on_host,
+                              WireCollector on_device = nullptr) {
+        geno_min_gpp = min_genotype_posterior;
+        geno_min_kmers = min_number_of_kmers;
+        geno_min_fraction = std::move(min_fraction_observed_kmers);
+        geno_collect = std::move(on_host);
+        geno_wire = std::move(on_device);
+    }
     typedef std::function<void(uint64_t *hist, size_t n)> HistReducer;   // sums the S*256 counters over all ranks in place
 
     InferenceEngine(bt_ctx *ctx, std::vector<uint8_t> gender, std::vector<std::string> sample_names, const GibbsOptions &options, HistReducer reduce_hist = nullptr);
@@ -147,6 +163,10 @@ class InferenceEngine {
 
     void handOver(std::unique_ptr<Sampler> &sampler, const GibbsBatchData &batch, const Collector &collect);
     WireCollector wire_collect;
+    GenotypeCollector geno_collect;
+    WireCollector geno_wire;
+    float geno_min_gpp = 0, geno_min_kmers = 0;
+    std::vector<float> geno_min_fraction;
     bt_ctx *ctx;
     std::vector<uint8_t> gender;
     std::vector<std::string> sample_names;

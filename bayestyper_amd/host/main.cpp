@@ -59,6 +59,8 @@ const unsigned max_parameter_kmers = 1000000;   // main.cpp:73
 const char *const intercluster_regions_file_prefix = "intercluster_regions";
 const char *const multigroup_kmers_file_prefix = "multigroup_kmers";
 const char *const parameter_kmers_file_prefix = "parameter_kmers";
+// collectGenotypes without BT_GENOTYPES_ON_HOST in the environment: bt_gibbs_genotypes on the device (true) or getGenotypes on the host (the measurement behind it)
+const bool kGenotypesOnDeviceDefault = true;
 
 std::string stamp() { return "[" + getLocalTime() + "] "; }
 const std::chrono::steady_clock::time_point g_main_start = std::chrono::steady_clock::now();   // (static initialisation: just before main())
@@ -513,7 +515,49 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         for (auto &part : lines)
             for (auto &l : part) genotype_writer.append(*l.first, std::move(l.second));
     };
+    // The device route of the same: every launch's genotype summaries are computed by bt_gibbs_genotypes where the samples lie, and what reaches the host (or
+    // rank 0) is one string of records per launch instead of the diplotype tables and 96 bytes of statistics per allele cell.  where[c] = (the string that
+    // holds cluster c of `b`, its cluster index in that string).  GQ is derived here from each record's best posterior (decodeGenotypeRecord).
+    // BT_GENOTYPES_ON_HOST: 1 = the route above, 0 = this one, unset = the default (kGenotypesOnDeviceDefault); BT_GATHER_FROM_HOST=1 implies the route above.
+    const char *route_env = getenv("BT_GENOTYPES_ON_HOST");
+    const bool genotypes_on_device = (route_env && *route_env ? std::strcmp(route_env, "0") == 0 : kGenotypesOnDeviceDefault) && !(comm && getenv("BT_GATHER_FROM_HOST"));
+    typedef std::vector<std::pair<const uint32_t *, uint32_t>> RecordIndex;
+    auto emit_records = [&](const GibbsBatchData &b, const RecordIndex &where) {
+        StageScope stage("VCF lines from the records of bt_gibbs_genotypes (-p host threads)");
+        std::vector<std::vector<std::pair<const std::string *, GenotypeWriter::GenotypedVariant>>> lines(host_threads);
+        parallelFor(b.numGroups(), host_threads, [&](size_t g_begin, size_t g_end, unsigned part) {
+            auto &mine = lines[part];
+            for (uint32_t g = (uint32_t)g_begin; g < (uint32_t)g_end; g++) {
+                const ClusterGroup &grp = unit.variant_cluster_groups[b.group_index[g]];
+                for (uint32_t c = b.group_cluster_off[g]; c < b.group_cluster_off[g + 1]; c++) {
+                    const VariantCluster &cluster = grp.clusters[c - b.group_cluster_off[g]];
+                    const std::vector<VariantInfo> info = variantClusterInfo(cluster);
+                    const uint32_t *w = where[c].first, local = where[c].second;
+                    const uint32_t *cluster_var_off = w + 4, *var_off = cluster_var_off + w[0] + 1;
+                    if (w[2] != S || local >= w[0] || cluster_var_off[local + 1] - cluster_var_off[local] != info.size())
+                        throw std::runtime_error("genotype string: the records do not match the unit's clusters");
+                    const ClusterAnnotation annotation{cluster.chrom_name, (uint32_t)info.size(), variantClusterRegion(cluster.chrom_name, info), (uint32_t)grp.clusters.size(), grp.region(),
+                                                       b.num_haplotypes[c]};
+                    for (size_t v = 0; v < info.size(); v++) {
+                        const DecodedVariant d = decodeGenotypeRecord(w + var_off[cluster_var_off[local] + v], (uint32_t)S);
+                        if (d.A != info[v].numberOfAlleles()) throw std::runtime_error("genotype string: a record with another number of alleles than its variant");
+                        mine.emplace_back(&cluster.chrom_name, genotype_writer.formatGenotypes(annotation, info[v], d.genotypes, formatSampleColumns(d.genotypes, d.A, d.means.data())));
+                    }
+                }
+            }
+        });
+        for (auto &part : lines)
+            for (auto &l : part) genotype_writer.append(*l.first, std::move(l.second));
+    };
     if (!comm) {
+        if (genotypes_on_device)
+            inference_engine.setGenotypeCollector(filters.min_genotype_posterior, filters.min_number_of_kmers, filters.min_fraction_observed_kmers,
+                                                  [&](const GibbsBatchData &b, const std::vector<uint32_t> &words) {
+                                                      if (words.size() < 4 || words[0] != b.numClusters()) throw std::runtime_error("genotype string: the records do not cover the launch's clusters");
+                                                      RecordIndex where(b.numClusters());
+                                                      for (uint32_t c = 0; c < b.numClusters(); c++) where[c] = std::make_pair(words.data(), c);
+                                                      emit_records(b, where);
+                                                  });
         if (!noise_genotyping) inference_engine.estimateGenotypes(batch, count_distribution, collect);
         else inference_engine.estimateNoiseAndGenotypes(batch, &count_distribution, collect, noise_prefix);
     } else {
@@ -537,7 +581,16 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         // device memory and go into the gather from there; `keep` only serves a sampler without such a string (BT_GATHER_FROM_HOST=1: the old path)
         DeviceWords on_device(ctx.h);
         uint64_t device_clusters = 0;
-        if (!getenv("BT_GATHER_FROM_HOST"))
+        // the device route: every launch's genotype string waits in device memory instead, and the gather moves summaries, not samples
+        DeviceWords genotypes_device(ctx.h);
+        uint64_t genotype_clusters = 0;
+        if (genotypes_on_device)
+            inference_engine.setGenotypeCollector(filters.min_genotype_posterior, filters.min_number_of_kmers, filters.min_fraction_observed_kmers, nullptr,
+                                                  [&](const GibbsBatchData &b, const uint32_t *d_words, uint64_t n) {
+                                                      genotypes_device.append(d_words, n);
+                                                      genotype_clusters += b.numClusters();
+                                                  });
+        else if (!getenv("BT_GATHER_FROM_HOST"))
             inference_engine.setWireCollector([&](const GibbsBatchData &b, const uint32_t *d_words, uint64_t n) {
                 on_device.append(d_words, n);
                 device_clusters += b.numClusters();
@@ -545,21 +598,57 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         if (!noise_genotyping) inference_engine.estimateGenotypes(my_batch, count_distribution, keep);
         else inference_engine.estimateNoiseAndGenotypes(my_batch, &count_distribution, keep, noise_prefix);
         bool from_host = mine.dip_off.size() > 1;
-        const bool covered = (from_host ? mine.dip_off.size() - 1 : device_clusters) == (size_t)my_batch.numClusters() && !(from_host && device_clusters);
-        {   // the ranks AGREE on the path (and on a failure) before the first collective of the gather: the two paths happen to issue the same collectives
-            // today, but nothing else keeps a rank without clusters — which has neither kind of result — on its peers' path
-            uint64_t votes[3] = {from_host ? 1u : 0u, !from_host && device_clusters ? 1u : 0u, covered ? 0u : 1u};
-            comm->allreduceHist(votes, 3);
+        bool as_genotypes = genotype_clusters != 0;
+        const uint64_t have = from_host ? mine.dip_off.size() - 1 : (as_genotypes ? genotype_clusters : device_clusters);
+        const bool covered = have == (uint64_t)my_batch.numClusters() && (from_host ? 1 : 0) + (device_clusters ? 1 : 0) + (as_genotypes ? 1 : 0) <= 1;
+        {   // the ranks AGREE on the path (and on a failure) before the first collective of the gather: the paths happen to issue the same collectives
+            // today, but nothing else keeps a rank without clusters — which has no kind of result — on its peers' path
+            uint64_t votes[4] = {from_host ? 1u : 0u, !from_host && device_clusters ? 1u : 0u, covered ? 0u : 1u, as_genotypes ? 1u : 0u};
+            comm->allreduceHist(votes, 4);
             if (votes[2]) throw std::runtime_error("rank " + std::to_string(rank) + ": collected samples do not cover " + (covered ? "another rank's" : "the rank's") + " clusters");
-            if (votes[0] && votes[1]) throw std::runtime_error("the ranks collected their samples in different ways (BT_GATHER_FROM_HOST set on some ranks only?)");
+            if ((votes[0] ? 1 : 0) + (votes[1] ? 1 : 0) + (votes[3] ? 1 : 0) > 1)
+                throw std::runtime_error("the ranks collected their samples in different ways (BT_GATHER_FROM_HOST or BT_GENOTYPES_ON_HOST set on some ranks only?)");
             from_host = votes[0] != 0;
+            as_genotypes = votes[3] != 0;
         }
-        std::unique_ptr<StageScope> gather_stage(new StageScope("gather of the collected samples to rank 0"));
-        const BatchResults all = from_host ? gatherResults(*comm, batch, rank_groups, mine, (uint32_t)S) : gatherResults(*comm, batch, rank_groups, on_device, (uint32_t)S);
-        gather_stage.reset();
-        std::cout << "[" << rank << "] gather: " << (from_host ? "from the host" : "from the device") << ", " << (from_host ? 1u : on_device.parts()) << " launch(es), "
-                  << (from_host ? (uint64_t)0 : on_device.size()) * 4 << " bytes of result strings on this rank" << std::endl;
-        if (rank == 0) collect(batch, all);
+        if (as_genotypes) {
+            std::unique_ptr<StageScope> gather_stage(new StageScope("gather of the genotype strings (bt_gibbs_genotypes) to rank 0"));
+            std::vector<uint64_t> off;
+            const std::vector<uint32_t> all = comm->gatherWordsDevice(genotypes_device.data(), genotypes_device.size(), &off);
+            gather_stage.reset();
+            std::cout << "[" << rank << "] gather: from the device, " << genotypes_device.parts() << " launch(es), " << genotypes_device.size() * 4
+                      << " bytes of genotype strings (bt_gibbs_genotypes) on this rank" << std::endl;
+            if (rank == 0) {   // the unit's cluster order from the strings' own tables: rank r sent its launches' strings in order, each with its clusters in order
+                RecordIndex where(batch.numClusters(), std::make_pair((const uint32_t *)nullptr, 0u));
+                for (int r = 0; r < world; r++) {
+                    uint64_t at = off[r];
+                    uint32_t local = 0, in_string = 0;
+                    const uint32_t *w = nullptr;
+                    for (uint32_t g : rank_groups[r])
+                        for (uint32_t c = batch.group_cluster_off[g]; c < batch.group_cluster_off[g + 1]; c++) {
+                            if (!w || local == in_string) {   // the next launch's string
+                                if (off[r + 1] - at < 6) throw std::runtime_error("rank " + std::to_string(r) + " did not send the genotypes of all its clusters");
+                                w = all.data() + at;
+                                in_string = w[0];
+                                local = 0;
+                                const uint64_t words = w[4 + (uint64_t)in_string + 1 + w[1]];
+                                if (!in_string || words > off[r + 1] - at) throw std::runtime_error("truncated genotype string from rank " + std::to_string(r));
+                                at += words;
+                            }
+                            where[c] = std::make_pair(w, local++);
+                        }
+                    if (at != off[r + 1] || local != in_string) throw std::runtime_error("rank " + std::to_string(r) + " sent genotypes of other clusters than its own");
+                }
+                emit_records(batch, where);
+            }
+        } else {
+            std::unique_ptr<StageScope> gather_stage(new StageScope("gather of the collected samples to rank 0"));
+            const BatchResults all = from_host ? gatherResults(*comm, batch, rank_groups, mine, (uint32_t)S) : gatherResults(*comm, batch, rank_groups, on_device, (uint32_t)S);
+            gather_stage.reset();
+            std::cout << "[" << rank << "] gather: " << (from_host ? "from the host" : "from the device") << ", " << (from_host ? 1u : on_device.parts()) << " launch(es), "
+                      << (from_host ? (uint64_t)0 : on_device.size()) * 4 << " bytes of result strings on this rank" << std::endl;
+            if (rank == 0) collect(batch, all);
+        }
     }
     if (rank != 0) {   // rank 0 writes the outputs; the other ranks' parameter files are copies of its own
         std::remove((output_prefix + "_genomic_parameters" + rank_suffix + ".txt").c_str());

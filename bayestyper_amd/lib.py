@@ -569,6 +569,7 @@ bt_gibbs_reset_groups = _sig("bt_gibbs_reset_groups", [vp])
 bt_gibbs_result_sizes = _sig("bt_gibbs_result_sizes", [vp, u64p, u64p])
 bt_gibbs_result_fetch = _sig("bt_gibbs_result_fetch", [vp] * 7)
 bt_gibbs_result_words = _sig("bt_gibbs_result_words", [vp, C.POINTER(vp), u64p])
+bt_gibbs_genotypes = _sig("bt_gibbs_genotypes", [vp, vp, C.POINTER(vp), u64p])
 bt_gibbs_trace_enable = _sig("bt_gibbs_trace_enable", [vp, C.c_uint32])
 bt_gibbs_trace_fetch = _sig("bt_gibbs_trace_fetch", [vp, vp, C.c_uint64, u64p])
 bt_gibbs_posterior_summary = _sig("bt_gibbs_posterior_summary", [vp, vp])
@@ -582,6 +583,7 @@ bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, v
 bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
+bt_diag_genotype_cluster = _sig("bt_diag_genotype_cluster", [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p])
 bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
 
 
@@ -658,6 +660,111 @@ def parse_result_words(w):
     dip_off = np.concatenate([[0], np.cumsum(sizes[:, 0])]).astype(np.uint64)
     cell_off = np.concatenate([[0], np.cumsum(sizes[:, 1])]).astype(np.uint64)
     return {"dip_off": dip_off, "h1": (keys & 0xFFFF).astype(np.uint16), "h2": (keys >> 16).astype(np.uint16), "freq": freq.copy(), "cell_off": cell_off, "stats": stats}, at
+
+
+class GenotypeFilters(C.Structure):   # include/btgpu.h: bt_genotype_filters
+    _fields_ = [("min_genotype_posterior", C.c_float), ("min_number_of_kmers", C.c_float), ("min_fraction_observed_kmers", vp)]
+
+
+def _genotype_filters(min_gpp, min_kmers, min_fraction):
+    mf = np.ascontiguousarray(min_fraction, np.float32)
+    f = GenotypeFilters()
+    f.min_genotype_posterior, f.min_number_of_kmers, f.min_fraction_observed_kmers = min_gpp, min_kmers, mf.ctypes.data
+    return f, mf
+
+
+_log10f = None
+
+
+def genotype_quality(best):
+    """GQ from the best genotype posterior as the host layer derives it (Genotypes.cpp: floatCompare against 1 and 0, else
+    (uint32_t)(-10 * log10f(1 - best)) with the C library's log10f — the digit depends on its last bit, so numpy's own log10 will not do)"""
+    global _log10f
+    if _log10f is None:
+        import ctypes.util
+
+        m = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        _log10f = m.log10f
+        _log10f.argtypes, _log10f.restype = [C.c_float], C.c_float
+    f32 = np.float32
+
+    def cmp(a, b):
+        return a == b or abs(f32(a - b)) < f32(f32(abs(min(a, b)) * np.finfo(f32).eps) * f32(100))
+
+    best = f32(best)
+    if cmp(best, f32(1)):
+        return 99
+    if cmp(best, f32(0)):
+        return 0
+    return int(f32(f32(-10) * f32(_log10f(f32(f32(1) - best)))))
+
+
+def parse_genotype_words(w):
+    """one launch's genotype string (bt_gibbs_genotypes / bt_diag_genotype_cluster; layout: include/btgpu.h) -> per cluster, in the sampler's cluster
+    order, the dictionary of arrays bayestyper_amd.host.genotypes.cluster_genotypes returns (gq derived from `best` on the host), plus "best" [V, S],
+    "ploidy" [S] and "kmer_means" [V, S, Amax, 3] (count / fraction / mean statistic: NAK, FAK, MAC; rows past a variant's alleles are 0)"""
+    w = np.ascontiguousarray(w, np.uint32)
+    Cn, NV, S = int(w[0]), int(w[1]), int(w[2])
+    cvo = w[4:4 + Cn + 1].astype(np.int64)
+    voff = w[5 + Cn:5 + Cn + NV + 1].astype(np.int64)
+    fw = w.view(np.float32)
+    out = []
+    for c in range(Cn):
+        v0, V = int(cvo[c]), int(cvo[c + 1] - cvo[c])
+        vna = np.array([w[voff[v0 + v]] for v in range(V)], np.uint16)
+        Amax = int(vna.max()) if V else 0
+        Gmax = Amax * (Amax + 1) // 2
+        d = {"gpp": np.zeros((V, S, Gmax), np.float32), "app": np.zeros((V, S, Amax), np.float32), "filters": np.zeros((V, S, Amax), np.uint16),
+             "estimate": np.full((V, S, 2), 0xFFFF, np.uint16), "gq": np.zeros((V, S), np.uint32), "total_count": np.zeros(V, np.uint32),
+             "alt_counts": np.zeros((V, Amax), np.uint32), "alt_freq": np.zeros((V, Amax), np.float32), "acp": np.zeros((V, Amax), np.float32),
+             "max_alt_acp": np.zeros(V, np.float32), "non_covered": np.zeros((V, Amax), np.uint8), "num_alleles": vna,
+             "best": np.zeros((V, S), np.float32), "ploidy": np.zeros(S, np.uint8), "kmer_means": np.zeros((V, S, Amax, 3), np.float64),
+             "has_dependency": np.zeros(V, np.uint8)}
+        for v in range(V):
+            at = int(voff[v0 + v])
+            A = int(w[at])
+            d["total_count"][v], d["max_alt_acp"][v], d["has_dependency"][v] = w[at + 1], fw[at + 2], w[at + 3]
+            al = w[at + 4:at + 4 + 4 * A].reshape(A, 4)
+            d["acp"][v, :A] = al[:, 0].view(np.float32)
+            d["alt_counts"][v, :A - 1] = al[1:, 1]
+            d["alt_freq"][v, :A - 1] = al[1:, 2].view(np.float32)
+            d["non_covered"][v, :A] = al[:, 3]
+            at += 4 + 4 * A
+            for s in range(S):
+                ploidy = int(w[at])
+                d["ploidy"][s] = ploidy
+                d["estimate"][v, s] = (w[at + 1] & 0xFFFF, w[at + 1] >> 16)
+                d["best"][v, s] = fw[at + 2]
+                d["gq"][v, s] = genotype_quality(fw[at + 2])
+                G = A * (A + 1) // 2 if ploidy == 2 else (A if ploidy == 1 else 0)
+                Ap = A if ploidy else 0
+                d["gpp"][v, s, :G] = fw[at + 4:at + 4 + G]
+                d["app"][v, s, :Ap] = fw[at + 4 + G:at + 4 + G + Ap]
+                d["filters"][v, s, :Ap] = w[at + 4 + G + Ap:at + 4 + G + 2 * Ap]
+                at += 4 + G + 2 * Ap
+                at += at & 1
+                d["kmer_means"][v, s, :A] = w[at:at + 6 * A].copy().view(np.float64).reshape(A, 3)
+                at += 6 * A
+            assert at == int(voff[v0 + v + 1]), "genotype string: a record does not end where the next begins"
+        out.append(d)
+    return out
+
+
+def diag_genotype_cluster(S, H, V, hap_allele, var_num_alleles, var_has_dependency, h1, h2, freq, stats, ploidy, min_gpp, min_kmers, min_fraction):
+    """bt_diag_genotype_cluster: the device's summary code run on the host for one cluster given as bth_cluster_genotypes takes it -> the word string"""
+    arrs = [np.ascontiguousarray(hap_allele, np.uint16).reshape(-1), np.ascontiguousarray(var_num_alleles, np.uint16), np.ascontiguousarray(var_has_dependency, np.uint8),
+            np.ascontiguousarray(h1, np.uint16), np.ascontiguousarray(h2, np.uint16), np.ascontiguousarray(freq, np.uint32).reshape(-1),
+            np.ascontiguousarray(stats, np.float64).reshape(-1), np.ascontiguousarray(ploidy, np.uint8)]
+    nd = len(arrs[3])
+    arrs = [a if a.size else np.zeros(1, a.dtype) for a in arrs]
+    f, keep = _genotype_filters(min_gpp, min_kmers, min_fraction)
+    n = C.c_uint64()
+    args = [S, H, V, _np_ptr(arrs[0]), _np_ptr(arrs[1]), _np_ptr(arrs[2]), nd, _np_ptr(arrs[3]), _np_ptr(arrs[4]), _np_ptr(arrs[5]), _np_ptr(arrs[6]), _np_ptr(arrs[7]), C.addressof(f)]
+    bt_diag_genotype_cluster(*args, None, 0, C.byref(n))   # (fails with "buffer too small" after setting the size)
+    out = np.zeros(n.value, np.uint32)
+    check(bt_diag_genotype_cluster(*args, _np_ptr(out), out.size, C.byref(n)))
+    del keep
+    return out
 
 
 class Gibbs:
@@ -792,6 +899,17 @@ class Gibbs:
     def result_words_host(self):
         p, n = self.result_words()
         out = np.zeros(n, np.uint32)
+        check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), p, out.nbytes))
+        return out
+
+    def genotypes(self, min_gpp, min_kmers, min_fraction):
+        """bt_gibbs_genotypes: the launch's genotype summaries computed on the device -> the word string on the host (parse_genotype_words)"""
+        f, keep = _genotype_filters(min_gpp, min_kmers, min_fraction)
+        if len(keep) != self.S:
+            raise ValueError("one min_fraction_observed_kmers per sample")
+        p, n = vp(), C.c_uint64()
+        check(bt_gibbs_genotypes(self.h, C.addressof(f), C.byref(p), C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
         check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), p, out.nbytes))
         return out
 

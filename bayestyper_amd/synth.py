@@ -47,35 +47,63 @@ class ClusterSpec:
         self.kv.extend(kv)
 
 
-def make_cluster(rng, V, H, kmers_per_allele, flank_kmers=0, ic_kmers=0, has_dependency=False):
+def make_cluster(rng, V, H, kmers_per_allele, flank_kmers=0, ic_kmers=0, has_dependency=False, alleles=None):
     """biallelic variants; haplotype 0 is all-reference, the others are distinct random allele combinations.
-    kmers_per_allele: one number, or a [V][2] table (k-mers of the reference / alternative allele of every variant)"""
+    kmers_per_allele: one number, or a [V][2] table (k-mers of the reference / alternative allele of every variant)
+    alleles: None (biallelic: the draws of earlier versions), or the number of alleles a candidate can carry — reference included, 2 to 6 — as one number
+    or per variant; every alternative allele gets the alternative's k-mers, and with has_dependency the missing allele comes on top (numberOfAlleles())"""
     c = ClusterSpec(H, V)
     kpa = np.broadcast_to(np.asarray(kmers_per_allele, np.int64).reshape(-1, 2) if np.ndim(kmers_per_allele) else np.full((V, 2), int(kmers_per_allele)), (V, 2))
     if has_dependency:
         c.var_has_dep[:] = 1
         c.var_num_alleles[:] = 3
-    combos = {tuple([0] * V)}
-    haps = [tuple([0] * V)]
-    # single-alt haplotypes first so every allele is covered, then random combinations
-    for v in range(V):
-        if len(haps) < H:
-            t = tuple(1 if i == v else 0 for i in range(V))
-            if t not in combos:
+    if alleles is not None:
+        n_al = np.broadcast_to(np.asarray(alleles, np.int64), (V,))
+        assert (n_al >= 2).all() and (n_al <= 6).all(), "2 to 6 alleles per variant"
+        c.var_num_alleles[:] = n_al + (1 if has_dependency else 0)
+        combos = {tuple([0] * V)}
+        haps = [tuple([0] * V)]
+        for v in range(V):   # one haplotype per alternative allele first, so that alleles are covered as far as H allows
+            for a in range(1, int(n_al[v])):
+                if len(haps) < H:
+                    haps.append(tuple(a if i == v else 0 for i in range(V)))
+                    combos.add(haps[-1])
+        total = int(np.prod(n_al))
+        while len(haps) < H:
+            t = tuple(int(rng.integers(0, n_al[i])) for i in range(V))
+            if t not in combos or total <= len(combos):
                 combos.add(t)
                 haps.append(t)
-    while len(haps) < H:
-        t = tuple(int(x) for x in rng.integers(0, 2, V))
-        if t not in combos or 2 ** V <= len(combos):
-            combos.add(t)
-            haps.append(t)
-    c.hap_allele[:, :] = np.asarray(haps, np.uint16)
-    for v in range(V):
-        for a in (0, 1):
-            carriers = c.hap_allele[:, v] == a
-            n_ka = int(kpa[v, a])
-            rows = np.tile(carriers.astype(np.uint8), (n_ka, 1))
-            c.add_kmers(rows, [[(v, carriers.copy())] for _ in range(n_ka)])
+        c.hap_allele[:, :] = np.asarray(haps, np.uint16)
+        for v in range(V):
+            for a in range(int(n_al[v])):
+                carriers = c.hap_allele[:, v] == a
+                if not carriers.any():   # an allele on no candidate has no path, hence no k-mers (it is reported as not covered)
+                    continue
+                n_ka = int(kpa[v, min(a, 1)])
+                c.add_kmers(np.tile(carriers.astype(np.uint8), (n_ka, 1)), [[(v, carriers.copy())] for _ in range(n_ka)])
+    else:
+        combos = {tuple([0] * V)}
+        haps = [tuple([0] * V)]
+        # single-alt haplotypes first so every allele is covered, then random combinations
+        for v in range(V):
+            if len(haps) < H:
+                t = tuple(1 if i == v else 0 for i in range(V))
+                if t not in combos:
+                    combos.add(t)
+                    haps.append(t)
+        while len(haps) < H:
+            t = tuple(int(x) for x in rng.integers(0, 2, V))
+            if t not in combos or 2 ** V <= len(combos):
+                combos.add(t)
+                haps.append(t)
+        c.hap_allele[:, :] = np.asarray(haps, np.uint16)
+        for v in range(V):
+            for a in (0, 1):
+                carriers = c.hap_allele[:, v] == a
+                n_ka = int(kpa[v, a])
+                rows = np.tile(carriers.astype(np.uint8), (n_ka, 1))
+                c.add_kmers(rows, [[(v, carriers.copy())] for _ in range(n_ka)])
     if flank_kmers:   # k-mers on every haplotype, overlapping no variant allele specifically
         c.add_kmers(np.ones((flank_kmers, H), np.uint8), [[] for _ in range(flank_kmers)])
     if ic_kmers:      # allele k-mers that also occur once elsewhere in the genome (intercluster multiplicity 2 = diploid)
@@ -421,6 +449,7 @@ def make_batch(shape, n_groups, S, seed, templates=1):
 def edge_group(rng, spec, cid=0):
     """One group of EXACTLY the dimensions of `spec` (a dict; make_edge_batch):
       V, H                  variants and haplotype candidates of the root cluster (2**V >= H, or candidates repeat)
+      alleles, dep          alleles per variant a candidate can carry (2 to 6, one number or per variant; default 2) and has_dependency (the missing allele on top)
       kpa                   k-mers per allele (default 1), flank / ic_kmers: k-mers on every haplotype / allele k-mers with an intercluster copy
       ic                    the intercluster multiplicities (female, male) of the ic k-mers (default (2, 2))
       mult                  the haplotype matrix's non-zero entries become this value (a number, one per k-mer row or a (K, H) array), default: as built (1).
@@ -429,7 +458,8 @@ def edge_group(rng, spec, cid=0):
       shared_mult           (root, child) multiplicity of the shared k-mers on the haplotypes that carry them (default (1, 1))
       shared_ic             intercluster multiplicities (female, male) of the shared k-mers (default (0, 0))"""
     def build(s):
-        c = make_cluster(rng, s["V"], s["H"], s.get("kpa", 1), flank_kmers=s.get("flank", 0), ic_kmers=s.get("ic_kmers", 0), has_dependency=s.get("dep", False))
+        c = make_cluster(rng, s["V"], s["H"], s.get("kpa", 1), flank_kmers=s.get("flank", 0), ic_kmers=s.get("ic_kmers", 0), has_dependency=s.get("dep", False),
+                         alleles=s.get("alleles"))
         if "ic" in s:
             c.ic[c.ic.any(axis=1)] = np.asarray(s["ic"], np.uint8)
         if "mult" in s:

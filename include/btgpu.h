@@ -580,6 +580,37 @@ int bt_gibbs_result_fetch(bt_gibbs *g, uint64_t *h_dip_off, uint16_t *h_dip_h1, 
  * per entry (order of bt_gibbs_result_fetch), counts [entry][S], one pad word if the count so far is odd, statistics
  * [cell][12] doubles.  *d_words belongs to the sampler (valid until the next call or bt_gibbs_destroy); complete on return. */
 int bt_gibbs_result_words(bt_gibbs *g, const uint32_t **d_words, uint64_t *num_words);
+/* Genotype summaries computed ON THE DEVICE: what VariantClusterGenotyper::getGenotypes (VariantClusterGenotyper.cpp:208-567) derives from the collected
+ * samples — genotype / allele posteriors, allele filters, the call, AC / AF / AN / ACP, the non-covered alleles — for every variant of every cluster of the
+ * launch, as ONE string of 32-bit words in DEVICE memory.  The string belongs to the sampler (valid until the next call or bt_gibbs_destroy) and is complete
+ * on return, like bt_gibbs_result_words'; the sampler's state is not touched (bt_gibbs_result_fetch before and after returns the same arrays).
+ * Floats are the host layer's bit for bit (same floatCompare / floatLess, same float sums divided by the number of collected sweeps, the diplotype entries
+ * visited in bt_gibbs_result_fetch's order wherever the order can matter).  GQ is NOT in the string: (uint32_t)(-10 * log10(1 - best)) truncates at values
+ * common posteriors sit on, so the reader derives it from `best` with its own log10 (99 if best compares equal to 1, 0 if to 0).
+ * Layout (word offsets count from the start of the string; every record starts on an even word and has an even length):
+ *   [0] C clusters  [1] NV variants of all clusters  [2] S  [3] 0
+ *   cluster_var_off [C+1]: the variants of cluster c (the sampler's cluster order) are cluster_var_off[c] .. cluster_var_off[c+1]
+ *   var_off [NV+1]: word offset of the record of variant v; var_off[NV] = *num_words (a reader may reorder clusters without recomputing sizes)
+ *   one pad word if the count so far is odd
+ *   per variant:  [0] A = numberOfAlleles() incl. the missing allele  [1] total_count (AN)  [2] max_alt_allele_call_probability (f32)  [3] has_dependency
+ *                 per allele a < A, 4 words: allele call probability ACP (f32); alt allele count AC and alt allele frequency AF (f32) of allele a
+ *                 (Genotypes::VariantStats' alt_allele_counts[a - 1]; 0 for a = 0); 1 if no haplotype candidate covers the allele (ANC), else 0
+ *     then per sample: [0] chromosome ploidy of the cluster's group  [1] the genotype estimate: first | second << 16 (0xFFFF = no call; second unused for ploidy 1,
+ *                 both for ploidy 0)  [2] best = the largest genotype posterior (f32)  [3] 0
+ *                 genotype posteriors f32 [G]: G = A (A + 1) / 2 for ploidy 2 (alleles a <= b at b (b + 1) / 2 + a), A for ploidy 1, 0 for ploidy 0
+ *                 allele posteriors f32 [A'], allele filter bits [A'] (1 = NAK, 2 = FAK) with A' = A, or 0 for ploidy 0
+ *                 one pad word if the count so far is odd
+ *                 k-mer means f64 [A][3]: KmerStats::getMean of the allele's count / fraction / mean statistics (-1 when nothing was added): NAK, FAK, MAC
+ * Errors (each with a message): a null argument; a resident noise chain in flight; an overflowed diplotype table; more than 2^32 words; nothing collected
+ * yet.  An error leaves nothing allocated that was not allocated before.  With BT_GIBBS_DEBUG set, a line on stderr tells how many cells visited their
+ * entries in (h1, h2) order — the cells whose sample collected 83 887 sweeps or more, below which the order cannot matter; BT_GENOTYPES_ORDERED_FROM lowers
+ * that threshold for tests. */
+typedef struct bt_genotype_filters {
+    float min_genotype_posterior;
+    float min_number_of_kmers;
+    const float *min_fraction_observed_kmers;   /* [S] */
+} bt_genotype_filters;                           /* Filters.cpp:33-54 */
+int bt_gibbs_genotypes(bt_gibbs *g, const bt_genotype_filters *f, const uint32_t **d_words, uint64_t *num_words);
 /* compact posterior summary on the DEVICE (input of the cross-GPU gather to rank 0): for cluster c, sample s
  * d_out[(c*S+s)*2] = h1 | h2<<16 of the most frequently sampled diplotype, d_out[(c*S+s)*2+1] = its frequency */
 int bt_gibbs_posterior_summary(bt_gibbs *g, uint32_t *d_out);
@@ -630,6 +661,12 @@ int bt_diag_uset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *v
  * 2 gamma(shape=a, scale=b) with one persistent distribution object, 3 uniform_int(0, a), 4 bernoulli(float a),
  * 5 std::shuffle of 0..a-1 (h_out gets the permutation as doubles, n ignored) */
 int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint64_t n, double *h_out);
+/* Host-side run of the genotype summaries behind bt_gibbs_genotypes for ONE cluster given in host arrays (what bt_gibbs_result_fetch returns for it, entries
+ * in that call's order; stats [(s * A_total + allele_base(v) + a) * 12]; ploidy [S] of the cluster's group): h_words receives the string bt_gibbs_genotypes
+ * would produce for a launch of this one cluster, *num_words its length (an error when capacity is smaller; *num_words is set first). */
+int bt_diag_genotype_cluster(uint32_t S, uint32_t H, uint32_t V, const uint16_t *hap_allele, const uint16_t *var_num_alleles, const uint8_t *var_has_dependency,
+                             uint64_t num_diplotypes, const uint16_t *h1, const uint16_t *h2, const uint32_t *freq, const double *stats, const uint8_t *ploidy,
+                             const bt_genotype_filters *f, uint32_t *h_words, uint64_t capacity, uint64_t *num_words);
 /* Host-side run of the container replay behind bt_paths_count_multigroup: n DISTINCT k-mers (2 x u64 each) are inserted, in the given
  * order, into an emulated libstdc++ std::unordered_set<std::bitset<2k>> that starts with `initial_buckets` buckets (1 = freshly
  * constructed; a set that was clear()ed keeps its bucket count); h_rank[i] = position of k-mer i in the set's iteration order,
