@@ -9,9 +9,11 @@
 // Every lane works in a private scratch region (path slots with a free list, per-vertex path lists, the cluster's generator).
 // Integer work except the k-mer score ratio (fp64 division, IEEE).  First version: per-cluster scratch is contiguous, not
 // lane-interleaved (DESIGN.md §7 lists that as the next step for this kernel).
+// A cluster of hundreds of vertices runs on a wavefront of its own instead (find_paths_wave_kernel below, BT_FIND_PATHS_WAVE_MIN), with the same decisions.
 #include "bt_internal.hpp"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -23,6 +25,7 @@ namespace {
 
 constexpr uint32_t MIN_OBSERVED_KMERS = 2;      // VariantClusterGraphPath.cpp:36
 constexpr uint32_t MIN_NUM_SAMPLE_PATHS = 1;    // VariantClusterGraph.cpp:60
+constexpr uint32_t WAVE_MIN_DEFAULT = 0;        // BT_FIND_PATHS_WAVE_MIN when unset (profiles/find_paths_wide.txt); 0: every cluster on the lane kernel
 constexpr uint32_t HDR_WORDS = 8;               // slot header: len, score_first, score_second, window count, window lo (2), window hi (2)
 
 struct FindCluster {
@@ -377,6 +380,295 @@ __global__ __launch_bounds__(64) void find_paths_kernel(const FindCluster *__res
     best_count[c] = nrows;
 }
 
+// ---- one wavefront per cluster ------------------------------------------------------------------------------------
+// The same search with the same decisions for a cluster of hundreds of vertices: a 64-thread workgroup (one wavefront) runs one
+// cluster.  What is independent is spread over the lanes — the candidate paths of a vertex in add_vertex, the existing paths a
+// merged-in path is tested against (lowest match wins: ballot, first set bit), the scores of a greedy round, the words of a copy,
+// the bytes of a row —, what is order-dependent (free list, appends to cur, the greedy scan with its tolerance compare) is
+// executed by every lane on the same values or, where it reads what it writes (shuffle, swaps, generator), by lane 0.  Phases that
+// hand data from one lane to another are separated by __syncthreads(); no loop waits for another lane.
+#define BT_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+
+struct WaveWork {
+    double *kscore;     // cur_cap  (scores of the candidate paths of a greedy round, by position in cur)
+    uint32_t *vscore;   // cur_cap
+    uint32_t *plen;     // cur_cap
+};
+
+__device__ inline uint32_t wave_slot_alloc(Work &w, uint32_t lane) {   // every lane: the same pop
+    if (w.free_top == 0) {
+        if (lane == 0) atomicExch(w.overflow, 1u);
+        return 0;
+    }
+    return BT_UNI(w.free_stack[--w.free_top]);
+}
+// every lane pushes the same value to the same place
+__device__ inline void wave_slot_free(Work &w, uint32_t s) { w.free_stack[w.free_top++] = s; }
+// words over lanes; the caller separates it from readers of dst and writers of src
+__device__ inline void wave_slot_copy(const Work &w, uint32_t dst, uint32_t src, uint32_t lane) {
+    const uint32_t *a = slot(w, src);
+    uint32_t *b = slot(w, dst);
+    const uint32_t n = HDR_WORDS + BT_UNI(a[0]);
+    for (uint32_t i = lane; i < n; i += 64) b[i] = a[i];
+}
+// index of the lowest m in [0, n) for which the path of slot_of(m) and the fixed path e2 / n2 are redundant, or n; FIXED_FIRST: the fixed path is the
+// first argument of paths_redundant (addPathIndices), else the second (mergePaths), as in the lane kernel
+template <bool FIXED_FIRST, class SlotOf>
+__device__ inline uint32_t wave_first_redundant(const Work &w, uint32_t n, SlotOf slot_of, const uint32_t *e2, uint32_t n2, uint32_t lane) {
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t m = base + lane;
+        bool hit = false;
+        if (m < n) {
+            const uint32_t s = slot_of(m);
+            if (s != 0xFFFFFFFFu) {
+                const uint32_t *mp = slot(w, s);
+                hit = FIXED_FIRST ? paths_redundant(w, e2, n2, mp + HDR_WORDS, mp[0]) : paths_redundant(w, mp + HDR_WORDS, mp[0], e2, n2);
+            }
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (mask) return base + (uint32_t)__builtin_ctzll(mask);
+    }
+    return n;
+}
+__device__ inline void wave_merge_paths(Work &w, uint32_t &ncur, const uint32_t *in, uint32_t nin, uint32_t cur_cap, uint32_t lane) {
+    const uint32_t main_size = ncur;
+    for (uint32_t j = 0; j < nin; ++j) {
+        const uint32_t sj = BT_UNI(in[j]);
+        const uint32_t *ip = slot(w, sj);
+        const uint32_t ilen = BT_UNI(ip[0]);
+        const uint32_t m = wave_first_redundant<false>(w, main_size, [&](uint32_t i) { return w.cur[i]; }, ip + HDR_WORDS, ilen, lane);
+        __syncthreads();   // (the tests have read what the copy below overwrites)
+        if (m < main_size) {
+            const uint32_t sm = BT_UNI(w.cur[m]);
+            if (BT_UNI(slot(w, sm)[0]) < ilen) wave_slot_copy(w, sm, sj, lane);
+        } else {
+            if (ncur >= cur_cap) {
+                if (lane == 0) atomicExch(w.overflow, 1u);
+                return;
+            }
+            const uint32_t s = wave_slot_alloc(w, lane);
+            wave_slot_copy(w, s, sj, lane);
+            w.cur[ncur++] = s;
+        }
+        __syncthreads();
+    }
+}
+__device__ inline void wave_clear_covered(const Work &w, uint32_t lane) {
+    for (uint32_t i = lane; i < w.nv; i += 64) w.covered[i] = 0;
+}
+// update_covered: the entries over lanes (every write is a 1), the short tail walk by every lane alike
+__device__ inline void wave_update_covered(const Work &w, const uint32_t *p, bool is_complete, uint32_t lane) {
+    const uint32_t *ent = p + HDR_WORDS;
+    const uint32_t len = BT_UNI(p[0]);
+    for (uint32_t i = lane; i < len; i += 64)
+        if (ent_obs(ent[i]) == MIN_OBSERVED_KMERS) w.covered[ent_index(ent[i])] = 1;
+    if (!is_complete) {
+        uint32_t cur = 0;
+        for (int32_t r = (int32_t)len - 1; r >= 0; --r) {
+            if ((w.k - 1u) <= cur || ent_obs(ent[r]) == MIN_OBSERVED_KMERS) break;
+            w.covered[ent_index(ent[r])] = 1;
+            cur += vlen(w, ent_index(ent[r]));
+        }
+    }
+}
+__device__ inline void wave_filter_paths(Work &w, const WaveWork &ww, uint32_t &ncur, uint32_t max_paths, bool is_complete, uint32_t lane) {
+    if (!(ncur > max_paths || (is_complete && ncur > MIN_NUM_SAMPLE_PATHS))) return;
+    bool is_first_pass = true, fresh = true;
+    wave_clear_covered(w, lane);
+    __syncthreads();
+    uint32_t sorted_end = 0;
+    while (sorted_end != ncur) {
+        // the scores of this round: in the first pass `covered` changed, in the second they are the same numbers round after round (and move with their paths)
+        if (fresh) {
+            for (uint32_t it = sorted_end + lane; it < ncur; it += 64) {
+                const uint32_t *p = slot(w, w.cur[it]);
+                ww.kscore[it] = kmer_score(p);
+                ww.vscore[it] = vertex_score(w, p, is_complete);
+                ww.plen[it] = p[0];
+            }
+            __syncthreads();
+        }
+        // the scan of filterPaths on those numbers, by every lane alike
+        uint32_t best = sorted_end;
+        double best_kmer = ww.kscore[best];
+        uint32_t best_vertex = ww.vscore[best];
+        for (uint32_t it = sorted_end + 1; it < ncur; ++it) {
+            const double cur_kmer = ww.kscore[it];
+            const uint32_t cur_vertex = ww.vscore[it];
+            if (is_first_pass) {
+                if (cur_vertex > 0) {
+                    if ((double_compare(cur_kmer, best_kmer) && cur_vertex > best_vertex) || cur_kmer > best_kmer || best_vertex == 0) {
+                        best = it;
+                        best_kmer = cur_kmer;
+                        best_vertex = cur_vertex;
+                    }
+                }
+            } else if (!is_complete || cur_vertex == ww.plen[it]) {
+                if (cur_kmer > best_kmer) {
+                    best = it;
+                    best_kmer = cur_kmer;
+                    best_vertex = cur_vertex;
+                }
+            }
+        }
+        best = BT_UNI(best);
+        best_vertex = BT_UNI(best_vertex);
+        const uint32_t s_best = BT_UNI(w.cur[best]), s_front = BT_UNI(w.cur[sorted_end]);
+        const uint32_t best_len = BT_UNI(ww.plen[best]), front_vertex = BT_UNI(ww.vscore[sorted_end]), front_len = BT_UNI(ww.plen[sorted_end]);
+        const double front_kmer = ww.kscore[sorted_end];
+        if (is_first_pass) wave_update_covered(w, slot(w, s_best), is_complete, lane);
+        else if (is_complete && sorted_end >= MIN_NUM_SAMPLE_PATHS && best_vertex < best_len) break;
+        __syncthreads();   // (every lane has read cur and the scores)
+        if (sorted_end != best && lane == 0) {
+            w.cur[sorted_end] = s_best;
+            w.cur[best] = s_front;
+            ww.kscore[sorted_end] = best_kmer, ww.vscore[sorted_end] = best_vertex, ww.plen[sorted_end] = best_len;
+            ww.kscore[best] = front_kmer, ww.vscore[best] = front_vertex, ww.plen[best] = front_len;
+        }
+        fresh = is_first_pass;
+        if (is_first_pass && best_vertex == 0) {
+            is_first_pass = false;
+            wave_clear_covered(w, lane);
+        } else {
+            ++sorted_end;
+            if (sorted_end == max_paths) break;
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (uint32_t i = sorted_end; i < ncur; ++i) wave_slot_free(w, BT_UNI(w.cur[i]));
+    ncur = sorted_end;
+}
+// a best row := the vertices of path p (bytes over lanes)
+__device__ inline void wave_write_row(uint8_t *row, uint32_t nv, const uint32_t *p, uint32_t lane) {
+    for (uint32_t vi = lane; vi < nv; vi += 64) row[vi] = 0;
+    __syncthreads();
+    const uint32_t len = BT_UNI(p[0]);
+    for (uint32_t i = lane; i < len; i += 64) row[ent_index(p[HDR_WORDS + i])] = 1;
+}
+
+__global__ __launch_bounds__(64) void find_paths_wave_kernel(const FindCluster *__restrict__ clusters, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds, uint32_t k,
+                                                             uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows, uint32_t *__restrict__ best_count,
+                                                             uint32_t *__restrict__ overflow, uint32_t *__restrict__ max_candidates) {
+    const uint32_t c = blockIdx.x, lane = threadIdx.x;
+    const FindCluster fc = clusters[c];
+    Work w;
+    WaveWork ww;
+    uint32_t *base = scratch + fc.scratch;
+    w.slots = base;
+    base += (size_t)fc.cap_slots * fc.slot_words;
+    w.free_stack = base;
+    base += fc.cap_slots;
+    w.vlist = base;
+    base += (size_t)fc.nv * max_haps;
+    w.vcount = base;
+    base += fc.nv;
+    w.cur = base;
+    base += fc.cur_cap;
+    w.tmp = base;
+    base += fc.nv;
+    w.covered = base;
+    base += fc.nv;
+    w.mt = base;
+    base += MT_WORDS;
+    base += (base - scratch) & 1u;   // (the region starts at a multiple of four words: an even word offset is 8-byte aligned)
+    ww.kscore = reinterpret_cast<double *>(base);
+    base += 2u * fc.cur_cap;
+    ww.vscore = base;
+    base += fc.cur_cap;
+    ww.plen = base;
+    w.slot_words = fc.slot_words;
+    w.nv = fc.nv;
+    w.v0 = fc.v0;
+    w.k = k;
+    w.max_haps = max_haps;
+    w.g = g;
+    w.bloom = bloom;
+    w.overflow = overflow;
+    w.free_top = fc.cap_slots;
+    for (uint32_t i = lane; i < fc.cap_slots; i += 64) w.free_stack[i] = fc.cap_slots - 1u - i;
+    for (uint32_t i = lane; i < fc.nv; i += 64) w.vcount[i] = 0;
+    if (lane == 0) mt_seed(w.mt, seeds[c]);
+    __syncthreads();
+    Mt rng = mt_open(w.mt);   // (lane 0 draws)
+    uint32_t ncur = 0, max_cand = 0;
+    for (uint32_t vi = 0; vi < fc.nv; ++vi) {
+        ncur = 0;
+        const uint32_t e0 = g.in_off[fc.v0 + vi], e1 = g.in_off[fc.v0 + vi + 1];
+        if (e0 == e1) {
+            const uint32_t s = wave_slot_alloc(w, lane);
+            if (lane < HDR_WORDS) slot(w, s)[lane] = 0;
+            w.cur[ncur++] = s;
+        } else {
+            for (uint32_t e = e0; e < e1; ++e) {
+                const uint32_t src = g.in_src[e];
+                wave_merge_paths(w, ncur, w.vlist + (size_t)src * max_haps, BT_UNI(w.vcount[src]), fc.cur_cap, lane);
+            }
+        }
+        __syncthreads();
+        if (lane == 0) rng_shuffle_u32(rng, w.cur, ncur);
+        __syncthreads();
+        for (uint32_t i = lane; i < ncur; i += 64) add_vertex(w, slot(w, w.cur[i]), vi);
+        __syncthreads();
+        max_cand = max_cand > ncur ? max_cand : ncur;
+        wave_filter_paths(w, ww, ncur, max_haps, false, lane);
+        __syncthreads();
+        for (uint32_t i = lane; i < ncur; i += 64) w.vlist[(size_t)vi * max_haps + i] = w.cur[i];
+        w.vcount[vi] = ncur;
+        for (uint32_t e = e0; e < e1; ++e) {
+            const uint32_t src = g.in_src[e];
+            const uint32_t n = BT_UNI(w.vcount[src]);
+            if (g.last_use[fc.v0 + src] == vi && n) {
+                for (uint32_t i = 0; i < n; ++i) wave_slot_free(w, BT_UNI(w.vlist[(size_t)src * max_haps + i]));
+                w.vcount[src] = 0;
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) mt_close(rng);
+    max_cand = max_cand > ncur ? max_cand : ncur;
+    wave_filter_paths(w, ww, ncur, max_haps, true, lane);
+    __syncthreads();
+    // ---- addPathIndices: the rows in order, a row's test against the final paths over lanes (the first unmarked match wins) ----
+    uint8_t *rows = best_rows + fc.best;
+    uint32_t nrows = best_count[c];
+    for (uint32_t r = 0; r < nrows; ++r) {
+        uint8_t *row = rows + (size_t)r * fc.nv;
+        uint32_t nb = 0;
+        for (uint32_t b0 = 0; b0 < fc.nv; b0 += 64) {
+            const uint32_t vi = b0 + lane;
+            const bool set = vi < fc.nv && row[vi];
+            const unsigned long long mask = __ballot(set);
+            if (set) w.tmp[nb + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = vi;
+            nb += (uint32_t)__popcll(mask);
+        }
+        __syncthreads();
+        const uint32_t pi = wave_first_redundant<true>(w, ncur, [&](uint32_t i) { const uint32_t s = w.cur[i]; return (s & 0x80000000u) ? 0xFFFFFFFFu : s; }, w.tmp, nb, lane);
+        __syncthreads();
+        if (pi < ncur) {
+            const uint32_t s = BT_UNI(w.cur[pi]);
+            const uint32_t *p = slot(w, s);
+            if (nb < BT_UNI(p[0])) wave_write_row(row, fc.nv, p, lane);
+            if (lane == 0) w.cur[pi] = s | 0x80000000u;
+        }
+        __syncthreads();
+    }
+    for (uint32_t pi = 0; pi < ncur; ++pi) {
+        const uint32_t s = BT_UNI(w.cur[pi]);
+        if (s & 0x80000000u) continue;
+        if (nrows >= fc.best_cap) {
+            if (lane == 0) atomicExch(overflow, 2u);
+            break;
+        }
+        wave_write_row(rows + (size_t)nrows * fc.nv, fc.nv, slot(w, s), lane);
+        ++nrows;
+    }
+    if (lane == 0) {
+        best_count[c] = nrows;
+        atomicMax(max_candidates, max_cand);
+    }
+}
+
 }  // namespace
 
 struct bt_find_paths {
@@ -390,7 +682,23 @@ struct bt_find_paths {
     uint8_t *d_best = nullptr;
     uint64_t best_bytes = 0;
     std::vector<void *> owned;
+    // Clusters of at least wave_min vertices (BT_FIND_PATHS_WAVE_MIN) run on a wavefront each.  The device arrays (clusters, seeds, best counts) are in LAUNCH
+    // order: the other clusters first, in batch order — find_paths_kernel runs over that prefix unchanged —, then the wide ones by descending vertex count.
+    // No wide cluster: launch order is batch order and `order` stays empty.
+    uint32_t wave_min = 0, num_wave = 0, max_nv = 0;
+    std::vector<uint32_t> order;         // launch position -> cluster of the batch
+    std::vector<uint32_t> staged;        // seeds / counts in launch order
+    uint32_t *d_max_candidates = nullptr;   // (second word of the overflow allocation)
+    hipEvent_t ev_seeds = nullptr, ev_wave = nullptr;
 };
+
+// best_count by cluster of the batch (the device keeps it in launch order)
+static hipError_t fetch_counts(bt_find_paths *f, uint32_t *out) {
+    if (f->order.empty()) return hipMemcpy(out, f->d_best_count, (size_t)f->C * 4, hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(f->staged.data(), f->d_best_count, (size_t)f->C * 4, hipMemcpyDeviceToHost);
+    for (uint32_t i = 0; i < f->C; ++i) out[f->order[i]] = f->staged[i];
+    return e;
+}
 
 extern "C" {
 
@@ -408,6 +716,8 @@ int bt_find_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, uint3
     const uint32_t C = f->C, NV = b->vertex_off[C];
     std::vector<uint32_t> last_use(NV);
     uint64_t scratch_words = 0, best_bytes = 0;
+    if (const char *e = getenv("BT_FIND_PATHS_WAVE_MIN")) f->wave_min = (uint32_t)std::strtoul(e, nullptr, 10);
+    else f->wave_min = WAVE_MIN_DEFAULT;
     for (uint32_t c = 0; c < C; ++c) {
         const uint32_t v0 = b->vertex_off[c], nv = b->vertex_off[c + 1] - v0;
         if (nv == 0 || nv >= (1u << 24)) {
@@ -451,12 +761,26 @@ int bt_find_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, uint3
         fc.scratch = scratch_words;
         fc.best = best_bytes;
         scratch_words += (uint64_t)fc.cap_slots * fc.slot_words + fc.cap_slots + (uint64_t)nv * max_sample_haplotypes + nv + fc.cur_cap + nv + nv + MT_WORDS;
+        f->max_nv = std::max(f->max_nv, nv);
+        if (f->wave_min && nv >= f->wave_min) {   // the wave kernel's score arrays of a greedy round: a double and two words per candidate path, 8-byte aligned
+            scratch_words += 1 + 4ull * fc.cur_cap;
+            f->num_wave++;
+        }
         scratch_words = (scratch_words + 3) & ~3ull;
         best_bytes += (uint64_t)fc.best_cap * nv;
         f->clusters.push_back(fc);
         f->nv.push_back(nv);
     }
     f->best_bytes = best_bytes;
+    std::vector<FindCluster> launch_order;
+    if (f->num_wave) {
+        std::vector<uint32_t> wide;
+        for (uint32_t c = 0; c < C; ++c) (f->nv[c] >= f->wave_min ? wide : f->order).push_back(c);
+        std::stable_sort(wide.begin(), wide.end(), [&](uint32_t a, uint32_t b) { return f->nv[a] > f->nv[b]; });   // the longest starts first
+        f->order.insert(f->order.end(), wide.begin(), wide.end());
+        for (uint32_t c : f->order) launch_order.push_back(f->clusters[c]);
+        f->staged.resize(C);
+    }
     int rc = BT_OK;
     auto up = [&](auto **dst, const auto *src, uint64_t n) {
         if (rc != BT_OK) return;
@@ -479,13 +803,18 @@ int bt_find_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, uint3
     up(&d_in_off, b->in_off, (uint64_t)NV + 1);
     up(&d_in_src, b->in_src, b->in_off[NV]);
     up(&d_last, last_use.data(), NV);
-    up(&f->d_clusters, f->clusters.data(), C);
+    up(&f->d_clusters, f->num_wave ? launch_order.data() : f->clusters.data(), C);
     up(&f->d_scratch, (const uint32_t *)nullptr, scratch_words);
     up(&f->d_best, (const uint8_t *)nullptr, best_bytes);
     up(&f->d_best_count, (const uint32_t *)nullptr, C);
-    up(&f->d_overflow, (const uint32_t *)nullptr, 1);
+    up(&f->d_overflow, (const uint32_t *)nullptr, f->num_wave ? 2 : 1);
     up(&f->d_seeds, (const uint32_t *)nullptr, C);
-    if (rc == BT_OK && (hipMemset(f->d_best_count, 0, (size_t)C * 4) != hipSuccess || hipMemset(f->d_overflow, 0, 4) != hipSuccess)) rc = fail("bt_find_paths_create: memset failed");
+    if (rc == BT_OK && (hipMemset(f->d_best_count, 0, (size_t)C * 4) != hipSuccess || hipMemset(f->d_overflow, 0, f->num_wave ? 8 : 4) != hipSuccess)) rc = fail("bt_find_paths_create: memset failed");
+    if (rc == BT_OK && f->num_wave) {
+        f->d_max_candidates = f->d_overflow + 1;
+        if (hipEventCreateWithFlags(&f->ev_seeds, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&f->ev_wave, hipEventDisableTiming) != hipSuccess)
+            rc = fail("bt_find_paths_create: event creation failed");
+    }
     if (rc != BT_OK) {
         bt_find_paths_destroy(f);
         return rc;
@@ -500,6 +829,8 @@ int bt_find_paths_destroy(bt_find_paths *f) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
     for (void *q : f->owned) (void)hipFree(q);
+    if (f->ev_seeds) (void)hipEventDestroy(f->ev_seeds);
+    if (f->ev_wave) (void)hipEventDestroy(f->ev_wave);
     delete f;
     return BT_OK;
 }
@@ -509,10 +840,41 @@ int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_
     if (sample_bloom->k != f->k) return fail("bt_find_paths_sample: k mismatch");
     BT_HIP(hipSetDevice(f->ctx->device));
     hipStream_t st = f->ctx->stream;
-    BT_HIP(hipMemcpyAsync(f->d_seeds, h_seeds, (size_t)f->C * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(find_paths_kernel, dim3((f->C + 63) / 64), dim3(64), 0, st, f->d_clusters, f->C, f->g, sample_bloom->view(), f->d_seeds, f->k, f->max_haps,
-                       f->d_scratch, f->d_best, f->d_best_count, f->d_overflow);
-    BT_CHECK_LAUNCH();
+    if (f->num_wave == 0) {
+        BT_HIP(hipMemcpyAsync(f->d_seeds, h_seeds, (size_t)f->C * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(find_paths_kernel, dim3((f->C + 63) / 64), dim3(64), 0, st, f->d_clusters, f->C, f->g, sample_bloom->view(), f->d_seeds, f->k, f->max_haps,
+                           f->d_scratch, f->d_best, f->d_best_count, f->d_overflow);
+        BT_CHECK_LAUNCH();
+    } else {
+        // the wide clusters on a wavefront each, beside the lane kernel when the context has a stream that PROVED concurrent with its own, else before it
+        const uint32_t lanes = f->C - f->num_wave;
+        hipStream_t wave_st = st;
+        if (lanes) {
+            int prio_lo = 0, prio_hi = 0;
+            BT_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+            hipStream_t cs[1] = {nullptr};
+            BT_HIP(ctx_class_streams(f->ctx, 1, getenv("BT_GIBBS_NO_PRIO") ? prio_lo : prio_hi, cs));   // (the priority the samplers ask for: one probe per context)
+            if (f->ctx->class_streams_concurrent >= 1) wave_st = cs[0];
+        }
+        for (uint32_t i = 0; i < f->C; ++i) f->staged[i] = h_seeds[f->order[i]];
+        BT_HIP(hipMemcpyAsync(f->d_seeds, f->staged.data(), (size_t)f->C * 4, hipMemcpyHostToDevice, st));
+        if (wave_st != st) {
+            BT_HIP(hipEventRecord(f->ev_seeds, st));
+            BT_HIP(hipStreamWaitEvent(wave_st, f->ev_seeds, 0));
+        }
+        hipLaunchKernelGGL(find_paths_wave_kernel, dim3(f->num_wave), dim3(64), 0, wave_st, f->d_clusters + lanes, f->g, sample_bloom->view(), f->d_seeds + lanes, f->k,
+                           f->max_haps, f->d_scratch, f->d_best, f->d_best_count + lanes, f->d_overflow, f->d_max_candidates);
+        BT_CHECK_LAUNCH();
+        if (lanes) {
+            hipLaunchKernelGGL(find_paths_kernel, dim3((lanes + 63) / 64), dim3(64), 0, st, f->d_clusters, lanes, f->g, sample_bloom->view(), f->d_seeds, f->k, f->max_haps,
+                               f->d_scratch, f->d_best, f->d_best_count, f->d_overflow);
+            BT_CHECK_LAUNCH();
+        }
+        if (wave_st != st) {   // both launches are joined before the flag is read
+            BT_HIP(hipEventRecord(f->ev_wave, wave_st));
+            BT_HIP(hipStreamWaitEvent(st, f->ev_wave, 0));
+        }
+    }
     uint32_t ov = 0;
     BT_HIP(hipMemcpyAsync(&ov, f->d_overflow, 4, hipMemcpyDeviceToHost, st));
     BT_HIP(hipStreamSynchronize(st));
@@ -521,11 +883,26 @@ int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_
     return BT_OK;
 }
 
+int bt_find_paths_info(bt_find_paths *f, bt_find_paths_stats *out) {
+    if (!f || !out) return fail("bt_find_paths_info: null argument");
+    BT_HIP(hipSetDevice(f->ctx->device));
+    out->num_clusters = f->C;
+    out->num_wave_clusters = f->num_wave;
+    out->wave_min_vertices = f->wave_min;
+    out->max_vertices = f->max_nv;
+    out->max_candidate_paths = 0;
+    if (f->num_wave) {
+        BT_HIP(hipStreamSynchronize(f->ctx->stream));
+        BT_HIP(hipMemcpy(&out->max_candidate_paths, f->d_max_candidates, 4, hipMemcpyDeviceToHost));
+    }
+    return BT_OK;
+}
+
 int bt_find_paths_sizes(bt_find_paths *f, uint32_t *h_num_paths, uint64_t *h_total_bytes) {
     if (!f || !h_num_paths) return fail("bt_find_paths_sizes: null argument");
     BT_HIP(hipSetDevice(f->ctx->device));
     BT_HIP(hipStreamSynchronize(f->ctx->stream));
-    BT_HIP(hipMemcpy(h_num_paths, f->d_best_count, (size_t)f->C * 4, hipMemcpyDeviceToHost));
+    BT_HIP(fetch_counts(f, h_num_paths));
     uint64_t total = 0;
     for (uint32_t c = 0; c < f->C; ++c) total += (uint64_t)h_num_paths[c] * f->nv[c];
     if (h_total_bytes) *h_total_bytes = total;
@@ -537,7 +914,7 @@ int bt_find_paths_fetch(bt_find_paths *f, uint8_t *h_path_vertices) {
     BT_HIP(hipSetDevice(f->ctx->device));
     BT_HIP(hipStreamSynchronize(f->ctx->stream));
     std::vector<uint32_t> n(f->C);
-    BT_HIP(hipMemcpy(n.data(), f->d_best_count, (size_t)f->C * 4, hipMemcpyDeviceToHost));
+    BT_HIP(fetch_counts(f, n.data()));
     std::vector<uint8_t> all(f->best_bytes);
     if (f->best_bytes) BT_HIP(hipMemcpy(all.data(), f->d_best, f->best_bytes, hipMemcpyDeviceToHost));
     uint8_t *o = h_path_vertices;

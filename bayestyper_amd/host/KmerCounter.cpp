@@ -353,6 +353,13 @@ void KmerCounter::findVariantClusterPaths(InferenceUnit *unit, const UnitGraphs 
         }
         StageTimes::get().add("  sample Bloom filters: load, or wait for the loader thread", load_wait_s);
         StageTimes::get().add("  best-path search of every sample (device)", search_s);
+        bt_find_paths_stats routes{};
+        check(bt_find_paths_info(fp, &routes), "bt_find_paths_info");
+        if (routes.num_wave_clusters > 0)   // (its time is part of the line above: the wide clusters run beside the launch of the others)
+            StageTimes::get().add("    of it: " + std::to_string(routes.num_wave_clusters) + " cluster(s) of >= " + std::to_string(routes.wave_min_vertices) +
+                                      " vertices on a wavefront each (largest " + std::to_string(routes.max_vertices) + " vertices, " +
+                                      std::to_string(routes.max_candidate_paths) + " candidate paths)",
+                                  search_s);
         std::vector<uint32_t> num_paths(C);
         uint64_t total = 0;
         check(bt_find_paths_sizes(fp, num_paths.data(), &total), "bt_find_paths_sizes");

@@ -71,6 +71,7 @@ bt_find_paths_destroy = _sig("bt_find_paths_destroy", [vp])
 bt_find_paths_sample = _sig("bt_find_paths_sample", [vp, vp, vp])
 bt_find_paths_sizes = _sig("bt_find_paths_sizes", [vp, vp, u64p])
 bt_find_paths_fetch = _sig("bt_find_paths_fetch", [vp, vp])
+bt_find_paths_info = _sig("bt_find_paths_info", [vp, vp])
 bt_paths_create = _sig("bt_paths_create", [vp, vp, C.c_uint32, C.POINTER(vp), u64p])
 bt_paths_destroy = _sig("bt_paths_destroy", [vp])
 bt_paths_count_kmers = _sig("bt_paths_count_kmers", [vp, vp])
@@ -445,6 +446,10 @@ class Paths:
             self.h = None
 
 
+class FindPathsStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("num_clusters", "num_wave_clusters", "wave_min_vertices", "max_vertices", "max_candidate_paths")]
+
+
 class FindPaths:
     """Per-sample best-path search over flattened graphs (bt_find_paths_*)"""
 
@@ -474,6 +479,12 @@ class FindPaths:
             res.append(out[at:at + m].reshape(int(n[c]), int(self.nv[c])).copy())
             at += m
         return res
+
+    def info(self):
+        """how the clusters are routed (bt_find_paths_stats): num_clusters, num_wave_clusters, wave_min_vertices, max_vertices, max_candidate_paths"""
+        st = FindPathsStats()
+        check(bt_find_paths_info(self.h, C.byref(st)))
+        return st
 
     def close(self):
         if self.h:

@@ -404,6 +404,14 @@ int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_
 /* best_paths_indices so far: h_num_paths[c] rows of |V_c| bytes each, clusters concatenated (bt_paths_batch::path_vertices layout) */
 int bt_find_paths_sizes(bt_find_paths *f, uint32_t *h_num_paths, uint64_t *h_total_bytes);
 int bt_find_paths_fetch(bt_find_paths *f, uint8_t *h_path_vertices);
+/* How the search of VariantClusterGraph.cpp:389-798 is laid out on the device.  A cluster with at least wave_min_vertices vertices runs on a wavefront of
+ * its own beside the launch that gives every other cluster a lane; the results are the same rows.  The threshold is BT_FIND_PATHS_WAVE_MIN, read when the
+ * object is created: 0 = never (every cluster on a lane), 1 = every cluster on a wavefront, unset = the library's default.  max_candidate_paths: the largest
+ * number of candidate paths a wavefront met at a vertex before filterPaths, over all bt_find_paths_sample calls so far (0 when no cluster took that route). */
+typedef struct {
+    uint32_t num_clusters, num_wave_clusters, wave_min_vertices, max_vertices, max_candidate_paths;
+} bt_find_paths_stats;
+int bt_find_paths_info(bt_find_paths *f, bt_find_paths_stats *out);
 
 /* ------------------------------------------------------------------------------------------
  * Count model LUTs: CountDistribution (src/bayesTyper/CountDistribution.cpp:215-265)
