@@ -4,12 +4,24 @@
 // The search is a sequential dynamic programme over the vertices of ONE cluster (candidate paths of a vertex = merged paths of
 // its predecessors, shuffled with the cluster's mt19937, extended by the vertex with one sample-Bloom lookup per completed k-mer,
 // then cut to max_sample_haplotypes by a two-pass greedy); clusters are independent.  As for the Gibbs sampler the unit of
-// parallelism is therefore the cluster: one lane runs one cluster's search, a launch carries all clusters of a unit, and the
-// random accesses into the (GB-sized) sample Bloom filter of thousands of concurrently running searches overlap in HBM.
-// Every lane works in a private scratch region (path slots with a free list, per-vertex path lists, the cluster's generator).
-// Integer work except the k-mer score ratio (fp64 division, IEEE).  First version: per-cluster scratch is contiguous, not
-// lane-interleaved (DESIGN.md §7 lists that as the next step for this kernel).
-// A cluster of hundreds of vertices runs on a wavefront of its own instead (find_paths_wave_kernel below, BT_FIND_PATHS_WAVE_MIN), with the same decisions.
+// parallelism is therefore the cluster, and the random accesses into the (GB-sized) sample Bloom filter of thousands of concurrently
+// running searches overlap in HBM.  Every cluster works in a private scratch region (scratch_layout: path slots with a free list,
+// per-vertex path lists, the cluster's generator), contiguous, not lane-interleaved (DESIGN.md §7 lists that as the next step).
+// Integer work except the k-mer score ratio (fp64 division, IEEE).
+//
+// There is ONE search, written once as templates over the TEAM that executes a cluster:
+//   LaneTeam — one lane.  find_paths_kernel: a launch carries all clusters of a unit, 64 per workgroup.
+//   WaveTeam — the 64 lanes of a wavefront.  find_paths_wave_kernel: one 64-thread workgroup per cluster of at least
+//              BT_FIND_PATHS_WAVE_MIN vertices (the search is quadratic in the vertex count).
+// What is independent is spread over the team's lanes — the candidate paths of a vertex in add_vertex, the existing paths a
+// merged-in path is tested against (lowest match wins: ballot, first set bit), the scores of a greedy round, the words of a copy,
+// the bytes of a row —, what is order-dependent (free list, appends to cur, the greedy scan with its tolerance compare) is
+// executed by every lane on the same values or, where it reads what it writes (shuffle, swaps, generator), by lane 0.  Phases that
+// hand data from one lane to another are separated by sync(); no loop waits for another lane.  With a team of one, `for (i = lane();
+// i < n; i += W)` is the plain loop, a ballot is the flag itself, lane() == 0 always holds and sync() is nothing: the sequential
+// search.  The teams differ in one place, filter_paths: a wavefront computes the scores of a greedy round over its lanes into
+// arrays of its scratch region and moves them with their paths, a single lane computes a candidate's scores when the scan reaches
+// it and has no such arrays.
 #include "bt_internal.hpp"
 
 #include <algorithm>
@@ -45,16 +57,72 @@ struct FindGraph {
     const uint32_t *last_use;          // per global vertex: local index of its last successor (or its own index)
 };
 
+// who executes one cluster's search
+struct LaneTeam {
+    static constexpr uint32_t W = 1;
+    __device__ static uint32_t lane() { return 0; }
+    __device__ static void sync() {}
+    __device__ static uint32_t uni(uint32_t x) { return x; }
+    __device__ static unsigned long long ballot(bool b) { return b ? 1ull : 0ull; }
+};
+struct WaveTeam {
+    static constexpr uint32_t W = 64;
+    __device__ static uint32_t lane() { return threadIdx.x; }
+    __device__ static void sync() { __syncthreads(); }
+    __device__ static uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }   // a value every lane holds alike
+    __device__ static unsigned long long ballot(bool b) { return __ballot(b); }
+};
+
+// one cluster's scratch region: word offsets of its arrays from the region's start, and its size
+struct ScratchLayout {
+    uint64_t slots;       // cap_slots * slot_words
+    uint64_t free_stack;  // cap_slots
+    uint64_t vlist;       // nv * max_haps
+    uint64_t vcount;      // nv
+    uint64_t cur;         // cur_cap
+    uint64_t tmp;         // nv   (vertex list of a best row)
+    uint64_t covered;     // nv   (0/1)
+    uint64_t mt;          // MT_WORDS
+    uint64_t kscore;      // wavefront only: cur_cap doubles (scores of the candidate paths of a greedy round, by position in cur)
+    uint64_t vscore;      // wavefront only: cur_cap
+    uint64_t plen;        // wavefront only: cur_cap
+    uint64_t total;       // a multiple of four words
+};
+__host__ __device__ inline ScratchLayout scratch_layout(const FindCluster &fc, uint32_t max_haps, bool wave) {
+    ScratchLayout l{};
+    uint64_t o = 0;
+    l.slots = o;
+    o += (uint64_t)fc.cap_slots * fc.slot_words;
+    l.free_stack = o;
+    o += fc.cap_slots;
+    l.vlist = o;
+    o += (uint64_t)fc.nv * max_haps;
+    l.vcount = o;
+    o += fc.nv;
+    l.cur = o;
+    o += fc.cur_cap;
+    l.tmp = o;
+    o += fc.nv;
+    l.covered = o;
+    o += fc.nv;
+    l.mt = o;
+    o += MT_WORDS;
+    if (wave) {
+        // a region starts at a multiple of four words, so an even offset is 8-byte aligned; the pad word is reserved whether it is used or not
+        l.kscore = o + (o & 1u);
+        l.vscore = l.kscore + 2ull * fc.cur_cap;
+        l.plen = l.vscore + fc.cur_cap;
+        o += 1 + 4ull * fc.cur_cap;
+    }
+    l.total = (o + 3) & ~3ull;
+    return l;
+}
+
 // view of one cluster's scratch region
 struct Work {
-    uint32_t *slots;      // cap_slots * slot_words
-    uint32_t *free_stack; // cap_slots
-    uint32_t *vlist;      // nv * max_haps
-    uint32_t *vcount;     // nv
-    uint32_t *cur;        // cur_cap
-    uint32_t *tmp;        // nv   (vertex list of a best row)
-    uint32_t *covered;    // nv   (0/1)
-    uint32_t *mt;         // MT_WORDS
+    uint32_t *slots, *free_stack, *vlist, *vcount, *cur, *tmp, *covered, *mt;   // (ScratchLayout)
+    double *kscore;       // wavefront only, with vscore and plen: never set for a team of one, and read only under `if constexpr (T::W > 1)`
+    uint32_t *vscore, *plen;
     uint32_t free_top;
     uint32_t slot_words, nv, v0, k, max_haps;
     FindGraph g;
@@ -70,19 +138,22 @@ __device__ inline uint32_t *slot(const Work &w, uint32_t s) { return w.slots + (
 __device__ inline uint32_t ent_index(uint32_t e) { return e & 0xFFFFFFu; }
 __device__ inline uint32_t ent_obs(uint32_t e) { return e >> 24; }
 
-__device__ inline uint32_t slot_alloc(Work &w) {
+template <class T>
+__device__ inline uint32_t slot_alloc(Work &w) {   // every lane: the same pop
     if (w.free_top == 0) {
-        atomicExch(w.overflow, 1u);
+        if (T::lane() == 0) atomicExch(w.overflow, 1u);
         return 0;
     }
-    return w.free_stack[--w.free_top];
+    return T::uni(w.free_stack[--w.free_top]);
 }
 __device__ inline void slot_free(Work &w, uint32_t s) { w.free_stack[w.free_top++] = s; }
+// words over lanes; the caller separates it from readers of dst and writers of src
+template <class T>
 __device__ inline void slot_copy(const Work &w, uint32_t dst, uint32_t src) {
     const uint32_t *a = slot(w, src);
     uint32_t *b = slot(w, dst);
-    const uint32_t n = HDR_WORDS + a[0];
-    for (uint32_t i = 0; i < n; ++i) b[i] = a[i];
+    const uint32_t n = HDR_WORDS + T::uni(a[0]);
+    for (uint32_t i = T::lane(); i < n; i += T::W) b[i] = a[i];
 }
 
 // VariantClusterGraphPath::updateScore (VariantClusterGraphPath.cpp:87-129)
@@ -150,13 +221,20 @@ __device__ inline uint32_t vertex_score(const Work &w, const uint32_t *p, bool i
     }
     return score;
 }
-__device__ inline void update_covered(const Work &w, const uint32_t *p, bool is_complete) {   // :190-225
+template <class T>
+__device__ inline void clear_covered(const Work &w) {
+    for (uint32_t i = T::lane(); i < w.nv; i += T::W) w.covered[i] = 0;
+}
+// :190-225; the entries over lanes (every write is a 1), the short tail walk by every lane alike
+template <class T>
+__device__ inline void update_covered(const Work &w, const uint32_t *p, bool is_complete) {
     const uint32_t *ent = p + HDR_WORDS;
-    for (uint32_t i = 0; i < p[0]; ++i)
+    const uint32_t len = T::uni(p[0]);
+    for (uint32_t i = T::lane(); i < len; i += T::W)
         if (ent_obs(ent[i]) == MIN_OBSERVED_KMERS) w.covered[ent_index(ent[i])] = 1;
     if (!is_complete) {
         uint32_t cur = 0;
-        for (int32_t r = (int32_t)p[0] - 1; r >= 0; --r) {
+        for (int32_t r = (int32_t)len - 1; r >= 0; --r) {
             if ((w.k - 1u) <= cur || ent_obs(ent[r]) == MIN_OBSERVED_KMERS) break;
             w.covered[ent_index(ent[r])] = 1;
             cur += vlen(w, ent_index(ent[r]));
@@ -198,225 +276,12 @@ __device__ inline bool paths_redundant(const Work &w, const uint32_t *e1, uint32
     }
     return !(i1 >= 0 || i2 >= 0);
 }
-// mergePaths (:474-523), copy semantics (the reference's move on the last edge is an optimisation)
-__device__ inline void merge_paths(Work &w, uint32_t &ncur, const uint32_t *in, uint32_t nin, uint32_t cur_cap) {
-    const uint32_t main_size = ncur;
-    for (uint32_t j = 0; j < nin; ++j) {
-        const uint32_t *ip = slot(w, in[j]);
-        bool redundant = false;
-        for (uint32_t m = 0; m < main_size; ++m) {
-            uint32_t *mp = slot(w, w.cur[m]);
-            if (paths_redundant(w, mp + HDR_WORDS, mp[0], ip + HDR_WORDS, ip[0])) {
-                if (mp[0] < ip[0]) slot_copy(w, w.cur[m], in[j]);
-                redundant = true;
-                break;
-            }
-        }
-        if (!redundant) {
-            if (ncur >= cur_cap) {
-                atomicExch(w.overflow, 1u);
-                return;
-            }
-            const uint32_t s = slot_alloc(w);
-            slot_copy(w, s, in[j]);
-            w.cur[ncur++] = s;
-        }
-    }
-}
-__device__ inline bool double_compare(double a, double b) {   // Utils::doubleCompare (Utils.hpp:81-87)
-    const double mn = a < b ? a : b;
-    return a == b || fabs(a - b) < fabs(mn) * 2.220446049250313080847263336181640625e-16 * 100;
-}
-// filterPaths (:628-724)
-__device__ inline void filter_paths(Work &w, uint32_t &ncur, uint32_t max_paths, bool is_complete) {
-    if (!(ncur > max_paths || (is_complete && ncur > MIN_NUM_SAMPLE_PATHS))) return;
-    bool is_first_pass = true;
-    for (uint32_t i = 0; i < w.nv; ++i) w.covered[i] = 0;
-    uint32_t sorted_end = 0;
-    while (sorted_end != ncur) {
-        uint32_t best = sorted_end;
-        double best_kmer = kmer_score(slot(w, w.cur[best]));
-        uint32_t best_vertex = vertex_score(w, slot(w, w.cur[best]), is_complete);
-        for (uint32_t it = sorted_end + 1; it < ncur; ++it) {
-            const uint32_t *p = slot(w, w.cur[it]);
-            const double cur_kmer = kmer_score(p);
-            const uint32_t cur_vertex = vertex_score(w, p, is_complete);
-            if (is_first_pass) {
-                if (cur_vertex > 0) {
-                    if ((double_compare(cur_kmer, best_kmer) && cur_vertex > best_vertex) || cur_kmer > best_kmer || best_vertex == 0) {
-                        best = it;
-                        best_kmer = cur_kmer;
-                        best_vertex = cur_vertex;
-                    }
-                }
-            } else if (!is_complete || cur_vertex == p[0]) {
-                if (cur_kmer > best_kmer) {
-                    best = it;
-                    best_kmer = cur_kmer;
-                    best_vertex = cur_vertex;
-                }
-            }
-        }
-        if (is_first_pass) update_covered(w, slot(w, w.cur[best]), is_complete);
-        else if (is_complete && sorted_end >= MIN_NUM_SAMPLE_PATHS && best_vertex < slot(w, w.cur[best])[0]) break;
-        if (sorted_end != best) {
-            const uint32_t t = w.cur[sorted_end];
-            w.cur[sorted_end] = w.cur[best];
-            w.cur[best] = t;
-        }
-        if (is_first_pass && best_vertex == 0) {
-            is_first_pass = false;
-            for (uint32_t i = 0; i < w.nv; ++i) w.covered[i] = 0;
-        } else {
-            ++sorted_end;
-            if (sorted_end == max_paths) break;
-        }
-    }
-    for (uint32_t i = sorted_end; i < ncur; ++i) slot_free(w, w.cur[i]);
-    ncur = sorted_end;
-}
-
-__global__ __launch_bounds__(64) void find_paths_kernel(const FindCluster *__restrict__ clusters, uint32_t C, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds,
-                                                        uint32_t k, uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows,
-                                                        uint32_t *__restrict__ best_count, uint32_t *__restrict__ overflow) {
-    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
-    if (c >= C) return;
-    const FindCluster fc = clusters[c];
-    Work w;
-    uint32_t *base = scratch + fc.scratch;
-    w.slots = base;
-    base += (size_t)fc.cap_slots * fc.slot_words;
-    w.free_stack = base;
-    base += fc.cap_slots;
-    w.vlist = base;
-    base += (size_t)fc.nv * max_haps;
-    w.vcount = base;
-    base += fc.nv;
-    w.cur = base;
-    base += fc.cur_cap;
-    w.tmp = base;
-    base += fc.nv;
-    w.covered = base;
-    base += fc.nv;
-    w.mt = base;
-    w.slot_words = fc.slot_words;
-    w.nv = fc.nv;
-    w.v0 = fc.v0;
-    w.k = k;
-    w.max_haps = max_haps;
-    w.g = g;
-    w.bloom = bloom;
-    w.overflow = overflow;
-    w.free_top = fc.cap_slots;
-    for (uint32_t i = 0; i < fc.cap_slots; ++i) w.free_stack[i] = fc.cap_slots - 1u - i;
-    for (uint32_t i = 0; i < fc.nv; ++i) w.vcount[i] = 0;
-    mt_seed(w.mt, seeds[c]);
-    Mt rng = mt_open(w.mt);
-    // ---- findSamplePaths (:389-472) ----
-    uint32_t ncur = 0;
-    for (uint32_t vi = 0; vi < fc.nv; ++vi) {
-        ncur = 0;
-        const uint32_t e0 = g.in_off[fc.v0 + vi], e1 = g.in_off[fc.v0 + vi + 1];
-        if (e0 == e1) {
-            const uint32_t s = slot_alloc(w);
-            uint32_t *p = slot(w, s);
-            for (uint32_t i = 0; i < HDR_WORDS; ++i) p[i] = 0;
-            w.cur[ncur++] = s;
-        } else {
-            for (uint32_t e = e0; e < e1; ++e) {
-                const uint32_t src = g.in_src[e];
-                merge_paths(w, ncur, w.vlist + (size_t)src * max_haps, w.vcount[src], fc.cur_cap);
-            }
-        }
-        rng_shuffle_u32(rng, w.cur, ncur);
-        for (uint32_t i = 0; i < ncur; ++i) add_vertex(w, slot(w, w.cur[i]), vi);
-        filter_paths(w, ncur, max_haps, false);
-        for (uint32_t i = 0; i < ncur; ++i) w.vlist[(size_t)vi * max_haps + i] = w.cur[i];
-        w.vcount[vi] = ncur;
-        for (uint32_t e = e0; e < e1; ++e) {   // predecessors whose last successor this vertex is are no longer needed
-            const uint32_t src = g.in_src[e];
-            if (g.last_use[fc.v0 + src] == vi && w.vcount[src]) {
-                for (uint32_t i = 0; i < w.vcount[src]; ++i) slot_free(w, w.vlist[(size_t)src * max_haps + i]);
-                w.vcount[src] = 0;
-            }
-        }
-    }
-    mt_close(rng);
-    filter_paths(w, ncur, max_haps, true);
-    // ---- addPathIndices (:726-798) ----
-    uint8_t *rows = best_rows + fc.best;
-    uint32_t nrows = best_count[c];
-    // redundant flags of the final paths live in the high bit of cur[]
-    for (uint32_t r = 0; r < nrows; ++r) {
-        uint8_t *row = rows + (size_t)r * fc.nv;
-        uint32_t nb = 0;
-        for (uint32_t vi = 0; vi < fc.nv; ++vi)
-            if (row[vi]) w.tmp[nb++] = vi;
-        for (uint32_t pi = 0; pi < ncur; ++pi) {
-            if (w.cur[pi] & 0x80000000u) continue;
-            const uint32_t *p = slot(w, w.cur[pi]);
-            if (paths_redundant(w, w.tmp, nb, p + HDR_WORDS, p[0])) {
-                if (nb < p[0]) {
-                    for (uint32_t vi = 0; vi < fc.nv; ++vi) row[vi] = 0;
-                    for (uint32_t i = 0; i < p[0]; ++i) row[ent_index(p[HDR_WORDS + i])] = 1;
-                }
-                w.cur[pi] |= 0x80000000u;
-                break;
-            }
-        }
-    }
-    for (uint32_t pi = 0; pi < ncur; ++pi) {
-        if (w.cur[pi] & 0x80000000u) continue;
-        if (nrows >= fc.best_cap) {
-            atomicExch(overflow, 2u);
-            break;
-        }
-        const uint32_t *p = slot(w, w.cur[pi]);
-        uint8_t *row = rows + (size_t)nrows * fc.nv;
-        for (uint32_t vi = 0; vi < fc.nv; ++vi) row[vi] = 0;
-        for (uint32_t i = 0; i < p[0]; ++i) row[ent_index(p[HDR_WORDS + i])] = 1;
-        ++nrows;
-    }
-    best_count[c] = nrows;
-}
-
-// ---- one wavefront per cluster ------------------------------------------------------------------------------------
-// The same search with the same decisions for a cluster of hundreds of vertices: a 64-thread workgroup (one wavefront) runs one
-// cluster.  What is independent is spread over the lanes — the candidate paths of a vertex in add_vertex, the existing paths a
-// merged-in path is tested against (lowest match wins: ballot, first set bit), the scores of a greedy round, the words of a copy,
-// the bytes of a row —, what is order-dependent (free list, appends to cur, the greedy scan with its tolerance compare) is
-// executed by every lane on the same values or, where it reads what it writes (shuffle, swaps, generator), by lane 0.  Phases that
-// hand data from one lane to another are separated by __syncthreads(); no loop waits for another lane.
-#define BT_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
-
-struct WaveWork {
-    double *kscore;     // cur_cap  (scores of the candidate paths of a greedy round, by position in cur)
-    uint32_t *vscore;   // cur_cap
-    uint32_t *plen;     // cur_cap
-};
-
-__device__ inline uint32_t wave_slot_alloc(Work &w, uint32_t lane) {   // every lane: the same pop
-    if (w.free_top == 0) {
-        if (lane == 0) atomicExch(w.overflow, 1u);
-        return 0;
-    }
-    return BT_UNI(w.free_stack[--w.free_top]);
-}
-// every lane pushes the same value to the same place
-__device__ inline void wave_slot_free(Work &w, uint32_t s) { w.free_stack[w.free_top++] = s; }
-// words over lanes; the caller separates it from readers of dst and writers of src
-__device__ inline void wave_slot_copy(const Work &w, uint32_t dst, uint32_t src, uint32_t lane) {
-    const uint32_t *a = slot(w, src);
-    uint32_t *b = slot(w, dst);
-    const uint32_t n = HDR_WORDS + BT_UNI(a[0]);
-    for (uint32_t i = lane; i < n; i += 64) b[i] = a[i];
-}
-// index of the lowest m in [0, n) for which the path of slot_of(m) and the fixed path e2 / n2 are redundant, or n; FIXED_FIRST: the fixed path is the
-// first argument of paths_redundant (addPathIndices), else the second (mergePaths), as in the lane kernel
-template <bool FIXED_FIRST, class SlotOf>
-__device__ inline uint32_t wave_first_redundant(const Work &w, uint32_t n, SlotOf slot_of, const uint32_t *e2, uint32_t n2, uint32_t lane) {
-    for (uint32_t base = 0; base < n; base += 64) {
-        const uint32_t m = base + lane;
+// index of the lowest m in [0, n) for which the path of slot_of(m) (0xFFFFFFFF: none) and the fixed path e2 / n2 are redundant, or n; FIXED_FIRST: the
+// fixed path is the first argument of paths_redundant (addPathIndices), else the second (mergePaths)
+template <class T, bool FIXED_FIRST, class SlotOf>
+__device__ inline uint32_t first_redundant(const Work &w, uint32_t n, SlotOf slot_of, const uint32_t *e2, uint32_t n2) {
+    for (uint32_t base = 0; base < n; base += T::W) {
+        const uint32_t m = base + T::lane();
         bool hit = false;
         if (m < n) {
             const uint32_t s = slot_of(m);
@@ -425,158 +290,159 @@ __device__ inline uint32_t wave_first_redundant(const Work &w, uint32_t n, SlotO
                 hit = FIXED_FIRST ? paths_redundant(w, e2, n2, mp + HDR_WORDS, mp[0]) : paths_redundant(w, mp + HDR_WORDS, mp[0], e2, n2);
             }
         }
-        const unsigned long long mask = __ballot(hit);
+        const unsigned long long mask = T::ballot(hit);
         if (mask) return base + (uint32_t)__builtin_ctzll(mask);
     }
     return n;
 }
-__device__ inline void wave_merge_paths(Work &w, uint32_t &ncur, const uint32_t *in, uint32_t nin, uint32_t cur_cap, uint32_t lane) {
+// mergePaths (:474-523), copy semantics (the reference's move on the last edge is an optimisation)
+template <class T>
+__device__ inline void merge_paths(Work &w, uint32_t &ncur, const uint32_t *in, uint32_t nin, uint32_t cur_cap) {
     const uint32_t main_size = ncur;
     for (uint32_t j = 0; j < nin; ++j) {
-        const uint32_t sj = BT_UNI(in[j]);
+        const uint32_t sj = T::uni(in[j]);
         const uint32_t *ip = slot(w, sj);
-        const uint32_t ilen = BT_UNI(ip[0]);
-        const uint32_t m = wave_first_redundant<false>(w, main_size, [&](uint32_t i) { return w.cur[i]; }, ip + HDR_WORDS, ilen, lane);
-        __syncthreads();   // (the tests have read what the copy below overwrites)
+        const uint32_t ilen = T::uni(ip[0]);
+        const uint32_t m = first_redundant<T, false>(w, main_size, [&](uint32_t i) { return w.cur[i]; }, ip + HDR_WORDS, ilen);
+        T::sync();   // (the tests have read what the copy below overwrites)
         if (m < main_size) {
-            const uint32_t sm = BT_UNI(w.cur[m]);
-            if (BT_UNI(slot(w, sm)[0]) < ilen) wave_slot_copy(w, sm, sj, lane);
+            const uint32_t sm = T::uni(w.cur[m]);
+            if (T::uni(slot(w, sm)[0]) < ilen) slot_copy<T>(w, sm, sj);
         } else {
             if (ncur >= cur_cap) {
-                if (lane == 0) atomicExch(w.overflow, 1u);
+                if (T::lane() == 0) atomicExch(w.overflow, 1u);
                 return;
             }
-            const uint32_t s = wave_slot_alloc(w, lane);
-            wave_slot_copy(w, s, sj, lane);
+            const uint32_t s = slot_alloc<T>(w);
+            slot_copy<T>(w, s, sj);
             w.cur[ncur++] = s;
         }
-        __syncthreads();
+        T::sync();
     }
 }
-__device__ inline void wave_clear_covered(const Work &w, uint32_t lane) {
-    for (uint32_t i = lane; i < w.nv; i += 64) w.covered[i] = 0;
+__device__ inline bool double_compare(double a, double b) {   // Utils::doubleCompare (Utils.hpp:81-87)
+    const double mn = a < b ? a : b;
+    return a == b || fabs(a - b) < fabs(mn) * 2.220446049250313080847263336181640625e-16 * 100;
 }
-// update_covered: the entries over lanes (every write is a 1), the short tail walk by every lane alike
-__device__ inline void wave_update_covered(const Work &w, const uint32_t *p, bool is_complete, uint32_t lane) {
-    const uint32_t *ent = p + HDR_WORDS;
-    const uint32_t len = BT_UNI(p[0]);
-    for (uint32_t i = lane; i < len; i += 64)
-        if (ent_obs(ent[i]) == MIN_OBSERVED_KMERS) w.covered[ent_index(ent[i])] = 1;
-    if (!is_complete) {
-        uint32_t cur = 0;
-        for (int32_t r = (int32_t)len - 1; r >= 0; --r) {
-            if ((w.k - 1u) <= cur || ent_obs(ent[r]) == MIN_OBSERVED_KMERS) break;
-            w.covered[ent_index(ent[r])] = 1;
-            cur += vlen(w, ent_index(ent[r]));
-        }
+// k-mer score, vertex score and length of the candidate path at position `it` of cur: a wavefront reads what the fill of its greedy round wrote, a
+// lane computes them here
+struct Scores {
+    double kmer;
+    uint32_t vertex, len;
+};
+template <class T>
+__device__ inline Scores scores_at(const Work &w, uint32_t it, bool is_complete) {
+    if constexpr (T::W > 1) {
+        return Scores{w.kscore[it], w.vscore[it], w.plen[it]};
+    } else {
+        const uint32_t *p = slot(w, w.cur[it]);
+        return Scores{kmer_score(p), vertex_score(w, p, is_complete), p[0]};
     }
 }
-__device__ inline void wave_filter_paths(Work &w, const WaveWork &ww, uint32_t &ncur, uint32_t max_paths, bool is_complete, uint32_t lane) {
+// filterPaths (:628-724)
+template <class T>
+__device__ inline void filter_paths(Work &w, uint32_t &ncur, uint32_t max_paths, bool is_complete) {
     if (!(ncur > max_paths || (is_complete && ncur > MIN_NUM_SAMPLE_PATHS))) return;
-    bool is_first_pass = true, fresh = true;
-    wave_clear_covered(w, lane);
-    __syncthreads();
+    bool is_first_pass = true;
+    [[maybe_unused]] bool fresh = true;
+    clear_covered<T>(w);
+    T::sync();
     uint32_t sorted_end = 0;
     while (sorted_end != ncur) {
-        // the scores of this round: in the first pass `covered` changed, in the second they are the same numbers round after round (and move with their paths)
-        if (fresh) {
-            for (uint32_t it = sorted_end + lane; it < ncur; it += 64) {
-                const uint32_t *p = slot(w, w.cur[it]);
-                ww.kscore[it] = kmer_score(p);
-                ww.vscore[it] = vertex_score(w, p, is_complete);
-                ww.plen[it] = p[0];
+        if constexpr (T::W > 1) {
+            // the scores of this round over the lanes: in the first pass `covered` changed, in the second they are the same numbers round after round
+            // (and move with their paths)
+            if (fresh) {
+                for (uint32_t it = sorted_end + T::lane(); it < ncur; it += T::W) {
+                    const uint32_t *p = slot(w, w.cur[it]);
+                    w.kscore[it] = kmer_score(p);
+                    w.vscore[it] = vertex_score(w, p, is_complete);
+                    w.plen[it] = p[0];
+                }
+                T::sync();
             }
-            __syncthreads();
+            fresh = is_first_pass;
         }
-        // the scan of filterPaths on those numbers, by every lane alike
+        // the scan of filterPaths, by every lane alike (the tolerance compare is not associative: no tree reduction)
+        const Scores front = scores_at<T>(w, sorted_end, is_complete);
         uint32_t best = sorted_end;
-        double best_kmer = ww.kscore[best];
-        uint32_t best_vertex = ww.vscore[best];
+        double best_kmer = front.kmer;
+        uint32_t best_vertex = front.vertex;
         for (uint32_t it = sorted_end + 1; it < ncur; ++it) {
-            const double cur_kmer = ww.kscore[it];
-            const uint32_t cur_vertex = ww.vscore[it];
+            const Scores c = scores_at<T>(w, it, is_complete);
             if (is_first_pass) {
-                if (cur_vertex > 0) {
-                    if ((double_compare(cur_kmer, best_kmer) && cur_vertex > best_vertex) || cur_kmer > best_kmer || best_vertex == 0) {
+                if (c.vertex > 0) {
+                    if ((double_compare(c.kmer, best_kmer) && c.vertex > best_vertex) || c.kmer > best_kmer || best_vertex == 0) {
                         best = it;
-                        best_kmer = cur_kmer;
-                        best_vertex = cur_vertex;
+                        best_kmer = c.kmer;
+                        best_vertex = c.vertex;
                     }
                 }
-            } else if (!is_complete || cur_vertex == ww.plen[it]) {
-                if (cur_kmer > best_kmer) {
+            } else if (!is_complete || c.vertex == c.len) {
+                if (c.kmer > best_kmer) {
                     best = it;
-                    best_kmer = cur_kmer;
-                    best_vertex = cur_vertex;
+                    best_kmer = c.kmer;
+                    best_vertex = c.vertex;
                 }
             }
         }
-        best = BT_UNI(best);
-        best_vertex = BT_UNI(best_vertex);
-        const uint32_t s_best = BT_UNI(w.cur[best]), s_front = BT_UNI(w.cur[sorted_end]);
-        const uint32_t best_len = BT_UNI(ww.plen[best]), front_vertex = BT_UNI(ww.vscore[sorted_end]), front_len = BT_UNI(ww.plen[sorted_end]);
-        const double front_kmer = ww.kscore[sorted_end];
-        if (is_first_pass) wave_update_covered(w, slot(w, s_best), is_complete, lane);
+        best = T::uni(best);
+        best_vertex = T::uni(best_vertex);
+        const uint32_t s_best = T::uni(w.cur[best]), s_front = T::uni(w.cur[sorted_end]);
+        const uint32_t best_len = T::uni(scores_at<T>(w, best, is_complete).len);
+        if (is_first_pass) update_covered<T>(w, slot(w, s_best), is_complete);
         else if (is_complete && sorted_end >= MIN_NUM_SAMPLE_PATHS && best_vertex < best_len) break;
-        __syncthreads();   // (every lane has read cur and the scores)
-        if (sorted_end != best && lane == 0) {
+        T::sync();   // (every lane has read cur and the scores)
+        if (sorted_end != best && T::lane() == 0) {
             w.cur[sorted_end] = s_best;
             w.cur[best] = s_front;
-            ww.kscore[sorted_end] = best_kmer, ww.vscore[sorted_end] = best_vertex, ww.plen[sorted_end] = best_len;
-            ww.kscore[best] = front_kmer, ww.vscore[best] = front_vertex, ww.plen[best] = front_len;
+            if constexpr (T::W > 1) {
+                w.kscore[sorted_end] = best_kmer, w.vscore[sorted_end] = best_vertex, w.plen[sorted_end] = best_len;
+                w.kscore[best] = front.kmer, w.vscore[best] = front.vertex, w.plen[best] = front.len;
+            }
         }
-        fresh = is_first_pass;
         if (is_first_pass && best_vertex == 0) {
             is_first_pass = false;
-            wave_clear_covered(w, lane);
+            clear_covered<T>(w);
         } else {
             ++sorted_end;
             if (sorted_end == max_paths) break;
         }
-        __syncthreads();
+        T::sync();
     }
-    __syncthreads();
-    for (uint32_t i = sorted_end; i < ncur; ++i) wave_slot_free(w, BT_UNI(w.cur[i]));
+    T::sync();
+    for (uint32_t i = sorted_end; i < ncur; ++i) slot_free(w, T::uni(w.cur[i]));
     ncur = sorted_end;
 }
 // a best row := the vertices of path p (bytes over lanes)
-__device__ inline void wave_write_row(uint8_t *row, uint32_t nv, const uint32_t *p, uint32_t lane) {
-    for (uint32_t vi = lane; vi < nv; vi += 64) row[vi] = 0;
-    __syncthreads();
-    const uint32_t len = BT_UNI(p[0]);
-    for (uint32_t i = lane; i < len; i += 64) row[ent_index(p[HDR_WORDS + i])] = 1;
+template <class T>
+__device__ inline void write_row(uint8_t *row, uint32_t nv, const uint32_t *p) {
+    for (uint32_t vi = T::lane(); vi < nv; vi += T::W) row[vi] = 0;
+    T::sync();
+    const uint32_t len = T::uni(p[0]);
+    for (uint32_t i = T::lane(); i < len; i += T::W) row[ent_index(p[HDR_WORDS + i])] = 1;
 }
 
-__global__ __launch_bounds__(64) void find_paths_wave_kernel(const FindCluster *__restrict__ clusters, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds, uint32_t k,
-                                                             uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows, uint32_t *__restrict__ best_count,
-                                                             uint32_t *__restrict__ overflow, uint32_t *__restrict__ max_candidates) {
-    const uint32_t c = blockIdx.x, lane = threadIdx.x;
-    const FindCluster fc = clusters[c];
-    Work w;
-    WaveWork ww;
+// the search of one cluster by team T; best_count: the cluster's own counter; max_candidates: null, or where lane 0 records the most candidate paths a vertex had
+template <class T>
+__device__ __forceinline__ void find_paths_cluster(const FindCluster &fc, uint32_t seed, const FindGraph &g, const BloomView &bloom, uint32_t k, uint32_t max_haps,
+                                                   uint32_t *scratch, uint8_t *best_rows, uint32_t *best_count, uint32_t *overflow, uint32_t *max_candidates) {
+    const ScratchLayout l = scratch_layout(fc, max_haps, T::W > 1);
     uint32_t *base = scratch + fc.scratch;
-    w.slots = base;
-    base += (size_t)fc.cap_slots * fc.slot_words;
-    w.free_stack = base;
-    base += fc.cap_slots;
-    w.vlist = base;
-    base += (size_t)fc.nv * max_haps;
-    w.vcount = base;
-    base += fc.nv;
-    w.cur = base;
-    base += fc.cur_cap;
-    w.tmp = base;
-    base += fc.nv;
-    w.covered = base;
-    base += fc.nv;
-    w.mt = base;
-    base += MT_WORDS;
-    base += (base - scratch) & 1u;   // (the region starts at a multiple of four words: an even word offset is 8-byte aligned)
-    ww.kscore = reinterpret_cast<double *>(base);
-    base += 2u * fc.cur_cap;
-    ww.vscore = base;
-    base += fc.cur_cap;
-    ww.plen = base;
+    Work w;
+    w.slots = base + l.slots;
+    w.free_stack = base + l.free_stack;
+    w.vlist = base + l.vlist;
+    w.vcount = base + l.vcount;
+    w.cur = base + l.cur;
+    w.tmp = base + l.tmp;
+    w.covered = base + l.covered;
+    w.mt = base + l.mt;
+    if constexpr (T::W > 1) {
+        w.kscore = reinterpret_cast<double *>(base + l.kscore);
+        w.vscore = base + l.vscore;
+        w.plen = base + l.plen;
+    }
     w.slot_words = fc.slot_words;
     w.nv = fc.nv;
     w.v0 = fc.v0;
@@ -586,87 +452,106 @@ __global__ __launch_bounds__(64) void find_paths_wave_kernel(const FindCluster *
     w.bloom = bloom;
     w.overflow = overflow;
     w.free_top = fc.cap_slots;
-    for (uint32_t i = lane; i < fc.cap_slots; i += 64) w.free_stack[i] = fc.cap_slots - 1u - i;
-    for (uint32_t i = lane; i < fc.nv; i += 64) w.vcount[i] = 0;
-    if (lane == 0) mt_seed(w.mt, seeds[c]);
-    __syncthreads();
+    for (uint32_t i = T::lane(); i < fc.cap_slots; i += T::W) w.free_stack[i] = fc.cap_slots - 1u - i;
+    for (uint32_t i = T::lane(); i < fc.nv; i += T::W) w.vcount[i] = 0;
+    if (T::lane() == 0) mt_seed(w.mt, seed);
+    T::sync();
     Mt rng = mt_open(w.mt);   // (lane 0 draws)
+    // ---- findSamplePaths (:389-472) ----
     uint32_t ncur = 0, max_cand = 0;
     for (uint32_t vi = 0; vi < fc.nv; ++vi) {
         ncur = 0;
         const uint32_t e0 = g.in_off[fc.v0 + vi], e1 = g.in_off[fc.v0 + vi + 1];
         if (e0 == e1) {
-            const uint32_t s = wave_slot_alloc(w, lane);
-            if (lane < HDR_WORDS) slot(w, s)[lane] = 0;
+            const uint32_t s = slot_alloc<T>(w);
+            for (uint32_t i = T::lane(); i < HDR_WORDS; i += T::W) slot(w, s)[i] = 0;
             w.cur[ncur++] = s;
         } else {
             for (uint32_t e = e0; e < e1; ++e) {
                 const uint32_t src = g.in_src[e];
-                wave_merge_paths(w, ncur, w.vlist + (size_t)src * max_haps, BT_UNI(w.vcount[src]), fc.cur_cap, lane);
+                merge_paths<T>(w, ncur, w.vlist + (size_t)src * max_haps, T::uni(w.vcount[src]), fc.cur_cap);
             }
         }
-        __syncthreads();
-        if (lane == 0) rng_shuffle_u32(rng, w.cur, ncur);
-        __syncthreads();
-        for (uint32_t i = lane; i < ncur; i += 64) add_vertex(w, slot(w, w.cur[i]), vi);
-        __syncthreads();
+        T::sync();
+        if (T::lane() == 0) rng_shuffle_u32(rng, w.cur, ncur);
+        T::sync();
+        for (uint32_t i = T::lane(); i < ncur; i += T::W) add_vertex(w, slot(w, w.cur[i]), vi);
+        T::sync();
         max_cand = max_cand > ncur ? max_cand : ncur;
-        wave_filter_paths(w, ww, ncur, max_haps, false, lane);
-        __syncthreads();
-        for (uint32_t i = lane; i < ncur; i += 64) w.vlist[(size_t)vi * max_haps + i] = w.cur[i];
+        filter_paths<T>(w, ncur, max_haps, false);
+        T::sync();
+        for (uint32_t i = T::lane(); i < ncur; i += T::W) w.vlist[(size_t)vi * max_haps + i] = w.cur[i];
         w.vcount[vi] = ncur;
-        for (uint32_t e = e0; e < e1; ++e) {
+        for (uint32_t e = e0; e < e1; ++e) {   // predecessors whose last successor this vertex is are no longer needed
             const uint32_t src = g.in_src[e];
-            const uint32_t n = BT_UNI(w.vcount[src]);
+            const uint32_t n = T::uni(w.vcount[src]);
             if (g.last_use[fc.v0 + src] == vi && n) {
-                for (uint32_t i = 0; i < n; ++i) wave_slot_free(w, BT_UNI(w.vlist[(size_t)src * max_haps + i]));
+                for (uint32_t i = 0; i < n; ++i) slot_free(w, T::uni(w.vlist[(size_t)src * max_haps + i]));
                 w.vcount[src] = 0;
             }
         }
-        __syncthreads();
+        T::sync();
     }
-    if (lane == 0) mt_close(rng);
+    if (T::lane() == 0) mt_close(rng);
     max_cand = max_cand > ncur ? max_cand : ncur;
-    wave_filter_paths(w, ww, ncur, max_haps, true, lane);
-    __syncthreads();
-    // ---- addPathIndices: the rows in order, a row's test against the final paths over lanes (the first unmarked match wins) ----
+    filter_paths<T>(w, ncur, max_haps, true);
+    T::sync();
+    // ---- addPathIndices (:726-798): the rows in order, a row's test against the final paths over lanes (the first unmarked match wins) ----
     uint8_t *rows = best_rows + fc.best;
-    uint32_t nrows = best_count[c];
+    uint32_t nrows = *best_count;
+    // redundant flags of the final paths live in the high bit of cur[]
     for (uint32_t r = 0; r < nrows; ++r) {
         uint8_t *row = rows + (size_t)r * fc.nv;
         uint32_t nb = 0;
-        for (uint32_t b0 = 0; b0 < fc.nv; b0 += 64) {
-            const uint32_t vi = b0 + lane;
+        for (uint32_t b0 = 0; b0 < fc.nv; b0 += T::W) {   // tmp := the row's vertices, in order
+            const uint32_t vi = b0 + T::lane();
             const bool set = vi < fc.nv && row[vi];
-            const unsigned long long mask = __ballot(set);
-            if (set) w.tmp[nb + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = vi;
+            const unsigned long long mask = T::ballot(set);
+            if (set) w.tmp[nb + (uint32_t)__popcll(mask & ((1ull << T::lane()) - 1ull))] = vi;
             nb += (uint32_t)__popcll(mask);
         }
-        __syncthreads();
-        const uint32_t pi = wave_first_redundant<true>(w, ncur, [&](uint32_t i) { const uint32_t s = w.cur[i]; return (s & 0x80000000u) ? 0xFFFFFFFFu : s; }, w.tmp, nb, lane);
-        __syncthreads();
+        T::sync();
+        const uint32_t pi = first_redundant<T, true>(w, ncur, [&](uint32_t i) { const uint32_t s = w.cur[i]; return (s & 0x80000000u) ? 0xFFFFFFFFu : s; }, w.tmp, nb);
+        T::sync();
         if (pi < ncur) {
-            const uint32_t s = BT_UNI(w.cur[pi]);
+            const uint32_t s = T::uni(w.cur[pi]);
             const uint32_t *p = slot(w, s);
-            if (nb < BT_UNI(p[0])) wave_write_row(row, fc.nv, p, lane);
-            if (lane == 0) w.cur[pi] = s | 0x80000000u;
+            if (nb < T::uni(p[0])) write_row<T>(row, fc.nv, p);
+            if (T::lane() == 0) w.cur[pi] = s | 0x80000000u;
         }
-        __syncthreads();
+        T::sync();
     }
     for (uint32_t pi = 0; pi < ncur; ++pi) {
-        const uint32_t s = BT_UNI(w.cur[pi]);
+        const uint32_t s = T::uni(w.cur[pi]);
         if (s & 0x80000000u) continue;
         if (nrows >= fc.best_cap) {
-            if (lane == 0) atomicExch(overflow, 2u);
+            if (T::lane() == 0) atomicExch(overflow, 2u);
             break;
         }
-        wave_write_row(rows + (size_t)nrows * fc.nv, fc.nv, slot(w, s), lane);
+        write_row<T>(rows + (size_t)nrows * fc.nv, fc.nv, slot(w, s));
         ++nrows;
     }
-    if (lane == 0) {
-        best_count[c] = nrows;
-        atomicMax(max_candidates, max_cand);
+    if (T::lane() == 0) {
+        *best_count = nrows;
+        if (max_candidates) atomicMax(max_candidates, max_cand);
     }
+}
+
+__global__ __launch_bounds__(64) void find_paths_kernel(const FindCluster *__restrict__ clusters, uint32_t C, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds,
+                                                        uint32_t k, uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows,
+                                                        uint32_t *__restrict__ best_count, uint32_t *__restrict__ overflow) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    const FindCluster fc = clusters[c];
+    find_paths_cluster<LaneTeam>(fc, seeds[c], g, bloom, k, max_haps, scratch, best_rows, best_count + c, overflow, nullptr);
+}
+
+__global__ __launch_bounds__(64) void find_paths_wave_kernel(const FindCluster *__restrict__ clusters, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds, uint32_t k,
+                                                             uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows, uint32_t *__restrict__ best_count,
+                                                             uint32_t *__restrict__ overflow, uint32_t *__restrict__ max_candidates) {
+    const uint32_t c = blockIdx.x;
+    const FindCluster fc = clusters[c];
+    find_paths_cluster<WaveTeam>(fc, seeds[c], g, bloom, k, max_haps, scratch, best_rows, best_count + c, overflow, max_candidates);
 }
 
 }  // namespace
@@ -760,13 +645,10 @@ int bt_find_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, uint3
         fc.best_cap = max_sample_haplotypes * num_samples;
         fc.scratch = scratch_words;
         fc.best = best_bytes;
-        scratch_words += (uint64_t)fc.cap_slots * fc.slot_words + fc.cap_slots + (uint64_t)nv * max_sample_haplotypes + nv + fc.cur_cap + nv + nv + MT_WORDS;
+        const bool wave = f->wave_min && nv >= f->wave_min;
+        scratch_words += scratch_layout(fc, max_sample_haplotypes, wave).total;
         f->max_nv = std::max(f->max_nv, nv);
-        if (f->wave_min && nv >= f->wave_min) {   // the wave kernel's score arrays of a greedy round: a double and two words per candidate path, 8-byte aligned
-            scratch_words += 1 + 4ull * fc.cur_cap;
-            f->num_wave++;
-        }
-        scratch_words = (scratch_words + 3) & ~3ull;
+        if (wave) f->num_wave++;
         best_bytes += (uint64_t)fc.best_cap * nv;
         f->clusters.push_back(fc);
         f->nv.push_back(nv);

@@ -133,6 +133,23 @@ def test_wave_route_equals_lane_route(gpu_ctx, oracle, monkeypatch):
     case.assert_equal(wave)
 
 
+def test_wide_clusters_inside_the_batch(gpu_ctx, oracle, monkeypatch):
+    """two clusters of 40 variants (about 139 vertices), each followed by ten small ones, threshold 100: a wide cluster's scratch region, score arrays
+    included, lies between other clusters' regions — every region is placed by the one layout the kernels carve it with"""
+    rng = np.random.default_rng(59)
+    small = [int(rng.integers(1, 8)) for _ in range(20)]
+    gs, truth, flat = _clusters(rng, [40] + small[:10] + [40] + small[10:], max_paths=6)
+    nv = flat["vertex_off"][1:] - flat["vertex_off"][:-1]
+    assert np.sort(nv)[-3] < 100 <= np.sort(nv)[-2]
+    case = _Case(gpu_ctx, oracle, rng, gs, truth, flat, 3, 0.05, 6)
+    mixed, st_mixed = case.run(gpu_ctx, monkeypatch, 100)
+    lane, st_lane = case.run(gpu_ctx, monkeypatch, 0)
+    case.close()
+    assert st_mixed.num_wave_clusters == 2 and st_lane.num_wave_clusters == 0
+    case.assert_equal(mixed)
+    case.assert_equal(mixed, lane)
+
+
 def test_more_than_64_candidate_paths_at_a_vertex(gpu_ctx, oracle, monkeypatch):
     """in-degree 3-4 with 32 kept paths per predecessor: the candidate paths of a vertex exceed a wavefront, so the strided lane loops and the
     first-match ballot take more than one pass"""
