@@ -4,6 +4,7 @@
 //                            KmerHash.cpp:202-254) over KmerCounts (KmerCounts.cpp:40-223)
 //   bt_table_count_intercluster <- KmerCounter::countInterclusterKmersCallback (KmerCounter.cpp:291-338)
 //   bt_table_classify_batch     <- VariantClusterGraph::classifyPathKmers, table half (VariantClusterGraph.cpp:902-938)
+//   bt_table_pack / _unpack / _save / _load / _file_info <- no counterpart: the table as packed records and a checkpoint file of them (SURVEY §5 "Checkpoint / resume")
 //   bt_kmc_scan_*         <- KmerCounter::parseSampleKmers(+CallBack) (KmerCounter.cpp:388-524),
 //                            record layout of CKMCFile::ReadNextKmer (kmc_file.cpp:428-494)
 //
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "bt_rng_device.hpp"
+#include "bt_table_file.hpp"
 
 using namespace bt;
 
@@ -126,18 +128,21 @@ __device__ inline int64_t table_find(const TableView &t, Kmer a) {
 // (key words, then the READY state with release semantics) before the loop's exit condition is evaluated, so lanes of the same
 // wavefront that poll that slot always see it published on a later iteration.
 // cword / cw_seen: a count word to fetch along (slot_look) and its value as seen — 0 for a key this lane has just inserted; a hint for sat_add_byte_from.
-__device__ inline int64_t table_find_or_insert(const TableView &t, Kmer a, uint32_t cword = NO_COUNT_WORD, uint32_t *cw_seen = nullptr) {
+// inserted: whether this lane created the record (table_unpack_kernel tells a new key from one that was there).
+__device__ inline int64_t table_find_or_insert(const TableView &t, Kmer a, uint32_t cword = NO_COUNT_WORD, uint32_t *cw_seen = nullptr, bool *inserted = nullptr) {
     uint64_t idx = table_home(a, t);
     int64_t result = -1;
     bool done = false;
     uint64_t probes = 0;
     uint32_t seen = 0;
+    bool won = false;
     while (!done) {
         const SlotLook p = slot_look(t, idx, cword);
         if (p.st == ST_EMPTY) {
             if (atomicCAS(t.state(idx), ST_EMPTY, ST_BUSY) == ST_EMPTY) {
                 publish_slot(t, idx, a);
                 result = (int64_t)idx;
+                won = true;
                 done = true;
             }
             // lost the race: the slot is BUSY or READY now; look at it again
@@ -158,6 +163,7 @@ __device__ inline int64_t table_find_or_insert(const TableView &t, Kmer a, uint3
     }
     // (no key counter is kept: millions of inserts would serialise on that one word; bt_table_status counts the READY slots)
     if (cw_seen) *cw_seen = seen;
+    if (inserted) *inserted = won;
     return result;
 }
 
@@ -1169,6 +1175,86 @@ __global__ __launch_bounds__(BLOCK) void kmc_kmer_stats_kernel(KmcView v, const 
 }
 static_assert(KSTATS_CACHE == 1024, "kmc_kmer_stats_kernel hashes into 2^10 slots");
 
+// ---------------------------------------------------------------------------------------------
+// Packed records (bt_table_pack / bt_table_unpack, the payload of bt_table_save / bt_table_load): per record 4 key words (lo, hi), the meta
+// word and spad / 4 count words.
+// ---------------------------------------------------------------------------------------------
+
+// Every READY slot of [slot0, slot0 + nslots) as one record, in no particular order.  One lane per slot, grid-stride; the trip count is the same for every lane
+// of a block, so every ballot and shuffle sees whole wavefronts.  A wavefront first COUNTS the READY slots of all its trips (state words only) and reserves their
+// output positions with ONE 64-bit atomic — per wavefront and launch, not per trip: one atomic per trip is 4.2 M adds on one address at 2^28 slots, and those took
+// 50 ms whatever the slot size (profiles/table_checkpoint.txt).  Then it walks its trips again: a slot is VEC 16-byte loads (slots are 16-byte aligned), the lanes
+// rank themselves by ballot + mbcnt and the records go out as dwords.  capacity_records 0 (records may be null): only *num_records is counted.
+template <unsigned VEC>
+__global__ __launch_bounds__(BLOCK) void table_pack_kernel(TableView t, uint64_t slot0, uint64_t nslots, uint32_t *__restrict__ records, uint64_t capacity_records,
+                                                           unsigned long long *__restrict__ num_records) {
+    const uint32_t cwords = t.spad / 4u, rec_words = 5u + cwords;
+    const uint64_t first = (uint64_t)blockIdx.x * BLOCK, stride = (uint64_t)gridDim.x * BLOCK;
+    uint32_t mine = 0;
+    for (uint64_t base = first; base < nslots; base += stride) {
+        const uint64_t i = base + threadIdx.x;
+        mine += i < nslots && *t.state(slot0 + i) == ST_READY ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);   // the wavefront's total, in every lane
+    if (!mine) return;
+    unsigned long long at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(num_records, (unsigned long long)mine);
+    at = __shfl(at, 0);
+    if (!capacity_records) return;
+    for (uint64_t base = first; base < nslots; base += stride) {
+        const uint64_t i = base + threadIdx.x;
+        uint32_t w[VEC * 4];
+#pragma unroll
+        for (unsigned v = 0; v < VEC; ++v) w[4 * v] = w[4 * v + 1] = w[4 * v + 2] = w[4 * v + 3] = 0;
+        if (i < nslots) {
+            const uint4 *s = reinterpret_cast<const uint4 *>(t.slot(slot0 + i));
+#pragma unroll
+            for (unsigned v = 0; v < VEC; ++v) {
+                const uint4 q = s[v];
+                w[4 * v] = q.x;
+                w[4 * v + 1] = q.y;
+                w[4 * v + 2] = q.z;
+                w[4 * v + 3] = q.w;
+            }
+        }
+        const bool ready = w[0] == ST_READY;   // (lanes past the range hold zeros: EMPTY)
+        const uint64_t mask = __ballot(ready);
+        const uint64_t mine_at = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        at += (uint64_t)__popcll(mask);
+        if (!ready || mine_at >= capacity_records) continue;
+        uint32_t *out = records + mine_at * rec_words;
+        out[0] = w[2];
+        out[1] = w[3];
+        out[2] = w[4];
+        out[3] = w[5];
+        out[4] = w[1];
+#pragma unroll
+        for (unsigned c = 0; c < VEC * 4 - 6; ++c)
+            if (c < cwords) out[5 + c] = w[6 + c];
+    }
+}
+
+// One lane per record: addKmer, then the record's meta and count words are SET (plain stores: the record is this lane's).  A key that was in the table already —
+// or twice among the records — is left as it was and counted in *duplicates.
+__global__ __launch_bounds__(BLOCK) void table_unpack_kernel(TableView t, const uint32_t *__restrict__ records, uint64_t n, unsigned long long *__restrict__ duplicates) {
+    const uint32_t cwords = t.spad / 4u, rec_words = 5u + cwords;
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < n; r += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t *in = records + r * rec_words;
+        Kmer a;
+        a.lo = (uint64_t)in[0] | ((uint64_t)in[1] << 32);
+        a.hi = (uint64_t)in[2] | ((uint64_t)in[3] << 32);
+        bool inserted = false;
+        const int64_t slot = table_find_or_insert(t, a, NO_COUNT_WORD, nullptr, &inserted);
+        if (slot < 0) continue;   // full: the overflow flag is up
+        if (!inserted) {
+            atomicAdd(duplicates, 1ULL);
+            continue;
+        }
+        *t.meta(slot) = in[4];
+        for (uint32_t c = 0; c < cwords; ++c) t.counts(slot)[c] = in[5 + c];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1387,6 +1473,236 @@ int bt_table_merge_count_rows(bt_table *t, const uint8_t *d_rows, uint64_t num_r
     const unsigned grid = (unsigned)std::min<uint64_t>((num_rows + BLOCK - 1) / BLOCK, 1u << 16);
     hipLaunchKernelGGL(merge_count_rows_kernel, dim3(grid), dim3(BLOCK), 0, t->ctx->stream, t->v, d_rows, num_rows);
     BT_CHECK_LAUNCH();
+    return BT_OK;
+}
+
+int bt_table_record_bytes(bt_table *t, uint32_t *record_bytes) {
+    if (!t || !record_bytes) return fail("bt_table_record_bytes: null argument");
+    *record_bytes = 20u + t->spad;
+    return BT_OK;
+}
+
+// table_pack_kernel over a slot range on the table's stream; d_count (device, 8 bytes) must be zero before the first range it counts
+static hipError_t pack_launch(bt_table *t, uint64_t slot0, uint64_t nslots, uint8_t *d_records, uint64_t capacity_records, unsigned long long *d_count) {
+    const dim3 grid(grid_for(nslots, BLOCK, t->ctx->num_cu * 16)), block(BLOCK);
+    uint32_t *rec = reinterpret_cast<uint32_t *>(d_records);
+    switch (t->v.slot_words) {
+        case 8: hipLaunchKernelGGL(table_pack_kernel<2>, grid, block, 0, t->ctx->stream, t->v, slot0, nslots, rec, capacity_records, d_count); break;
+        case 12: hipLaunchKernelGGL(table_pack_kernel<3>, grid, block, 0, t->ctx->stream, t->v, slot0, nslots, rec, capacity_records, d_count); break;
+        case 16: hipLaunchKernelGGL(table_pack_kernel<4>, grid, block, 0, t->ctx->stream, t->v, slot0, nslots, rec, capacity_records, d_count); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// READY slots of the whole table (a sizing pass of the pack kernel)
+static int pack_count(bt_table *t, unsigned long long *d_count, uint64_t *n) {
+    unsigned long long c = 0;
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, t->ctx->stream);
+    if (e == hipSuccess) e = pack_launch(t, 0, t->capacity, nullptr, 0, d_count);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, t->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+    if (e != hipSuccess) return fail(std::string("bt_table_pack (count): ") + hipGetErrorString(e));
+    *n = c;
+    return BT_OK;
+}
+
+int bt_table_pack(bt_table *t, uint8_t *d_records, uint64_t capacity_records, uint64_t *h_num_records) {
+    if (!t || !h_num_records || (capacity_records && !d_records)) return fail("bt_table_pack: null argument");
+    BT_HIP(hipSetDevice(t->ctx->device));
+    unsigned long long *d_n = nullptr;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_n), 8));
+    // the records are counted first, so that a buffer that is too small is an error before anything is written to it
+    int rc = pack_count(t, d_n, h_num_records);
+    if (rc == BT_OK && capacity_records) {
+        if (*h_num_records > capacity_records) rc = fail("bt_table_pack: output buffer too small (" + std::to_string(*h_num_records) + " records, room for " + std::to_string(capacity_records) + ")");
+        else {
+            hipError_t e = hipMemsetAsync(d_n, 0, 8, t->ctx->stream);
+            if (e == hipSuccess) e = pack_launch(t, 0, t->capacity, d_records, capacity_records, d_n);
+            if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+            if (e != hipSuccess) rc = fail(std::string("bt_table_pack: ") + hipGetErrorString(e));
+        }
+    }
+    (void)hipFree(d_n);
+    return rc;
+}
+
+int bt_table_unpack(bt_table *t, const uint8_t *d_records, uint64_t num_records) {
+    if (!t || (num_records && !d_records)) return fail("bt_table_unpack: null argument");
+    if (num_records == 0) return BT_OK;
+    BT_HIP(hipSetDevice(t->ctx->device));
+    unsigned long long *d_dup = nullptr, dup = 0;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_dup), 8));
+    hipError_t e = hipMemsetAsync(d_dup, 0, 8, t->ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(table_unpack_kernel, dim3(grid_for(num_records, BLOCK, t->ctx->num_cu * 16)), dim3(BLOCK), 0, t->ctx->stream, t->v, reinterpret_cast<const uint32_t *>(d_records),
+                           num_records, d_dup);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&dup, d_dup, 8, hipMemcpyDeviceToHost, t->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+    (void)hipFree(d_dup);
+    if (e != hipSuccess) return fail(std::string("bt_table_unpack: ") + hipGetErrorString(e));
+    if (dup) return fail("bt_table_unpack: " + std::to_string(dup) + " of " + std::to_string(num_records) + " records have a key that the table already held (they were not applied)");
+    return BT_OK;
+}
+
+// slots per range of bt_table_save: 2^22, BT_TABLE_CKPT_SLOTS can only lower it (tests)
+static uint64_t ckpt_range_slots() {
+    uint64_t slots = 1ull << 22;
+    if (const char *e = getenv("BT_TABLE_CKPT_SLOTS")) {
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v >= 64 && v < slots) slots = v;
+    }
+    return slots;
+}
+
+namespace {
+// what bt_table_save / bt_table_load stage through: one device buffer (everything runs on the table's stream, in order) and two pinned host buffers
+struct CkptStaging {
+    uint8_t *d_buf = nullptr, *pin[2] = {nullptr, nullptr};
+    unsigned long long *d_word = nullptr;
+    hipEvent_t moved[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    hipError_t alloc(hipStream_t on, size_t bytes) {
+        stream = on;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_buf), bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_word), 8);
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+            e = hipHostMalloc(reinterpret_cast<void **>(&pin[i]), bytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&moved[i], hipEventDisableTiming);
+        }
+        return e;
+    }
+    ~CkptStaging() {
+        (void)hipStreamSynchronize(stream);   // (an error path may leave a copy in flight)
+        (void)hipFree(d_buf);
+        (void)hipFree(d_word);
+        for (int i = 0; i < 2; ++i) {
+            if (pin[i]) (void)hipHostFree(pin[i]);
+            if (moved[i]) (void)hipEventDestroy(moved[i]);
+        }
+    }
+};
+}  // namespace
+
+int bt_table_save(bt_table *t, const char *path, const char *manifest) {
+    if (!t || !path) return fail("bt_table_save: null argument");
+    BT_HIP(hipSetDevice(t->ctx->device));
+    const uint64_t range = std::min<uint64_t>(ckpt_range_slots(), t->capacity), num_ranges = (t->capacity + range - 1) / range;
+    const uint32_t rb = 20u + t->spad;
+    CkptStaging st;
+    hipError_t e = st.alloc(t->ctx->stream, (size_t)(range * rb));
+    if (e != hipSuccess) return fail(std::string("bt_table_save: staging buffers: ") + hipGetErrorString(e));
+    btfile::Header h;
+    h.k = t->k;
+    h.num_samples = t->num_samples;
+    h.record_bytes = rb;
+    h.max_chunk_records = range;
+    h.manifest = manifest ? manifest : "";
+    if (h.manifest.size() > btfile::MAX_MANIFEST) return fail("bt_table_save: manifest too long");
+    if (pack_count(t, st.d_word, &h.num_records) != BT_OK) return BT_ERR;
+    btfile::Writer w;
+    if (!w.open(path, h)) return fail("bt_table_save: " + w.error);
+    // range i is packed and copied to pin[i & 1] while range i - 1 is written from the other buffer
+    uint64_t have[2] = {0, 0};
+    for (uint64_t i = 0; i <= num_ranges; ++i) {
+        if (i < num_ranges) {
+            unsigned long long n = 0;
+            e = hipMemsetAsync(st.d_word, 0, 8, t->ctx->stream);
+            if (e == hipSuccess) e = pack_launch(t, i * range, std::min(range, t->capacity - i * range), st.d_buf, range, st.d_word);
+            if (e == hipSuccess) e = hipMemcpyAsync(&n, st.d_word, 8, hipMemcpyDeviceToHost, t->ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+            if (e == hipSuccess && n > range) return fail("bt_table_save: a range packed more records than it has slots");
+            if (e == hipSuccess && n) e = hipMemcpyAsync(st.pin[i & 1], st.d_buf, (size_t)(n * rb), hipMemcpyDeviceToHost, t->ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(st.moved[i & 1], t->ctx->stream);
+            if (e != hipSuccess) return fail(std::string("bt_table_save: ") + hipGetErrorString(e));
+            have[i & 1] = n;
+        }
+        if (i > 0 && have[(i - 1) & 1]) {
+            e = hipEventSynchronize(st.moved[(i - 1) & 1]);
+            if (e != hipSuccess) return fail(std::string("bt_table_save: ") + hipGetErrorString(e));
+            if (!w.chunk(st.pin[(i - 1) & 1], have[(i - 1) & 1], rb)) return fail("bt_table_save: " + w.error);
+        }
+    }
+    BT_HIP(hipStreamSynchronize(t->ctx->stream));
+    if (!w.finish()) return fail("bt_table_save: " + w.error);
+    return BT_OK;
+}
+
+int bt_table_load(bt_ctx *ctx, const char *path, const char *expected_manifest, bt_table **out) {
+    if (!ctx || !path || !out) return fail("bt_table_load: null argument");
+    *out = nullptr;
+    btfile::Reader r;
+    if (!r.open(path)) return fail("bt_table_load: " + r.error);
+    if (expected_manifest) {
+        const std::string diff = btfile::manifest_difference(r.header.manifest, expected_manifest);
+        if (!diff.empty()) return fail(std::string("bt_table_load: k-mer table checkpoint ") + path + " was written for other inputs: " + diff);
+    }
+    BT_HIP(hipSetDevice(ctx->device));
+    const btfile::Header &h = r.header;
+    const uint32_t rb = h.record_bytes;
+    CkptStaging st;
+    unsigned long long dup = 0;
+    bt_table *t = nullptr;
+    std::string error;
+    hipError_t e = st.alloc(ctx->stream, (size_t)(std::max<uint64_t>(std::min(h.max_chunk_records, h.num_records), 1) * rb));
+    if (e == hipSuccess) e = hipMemsetAsync(st.d_word, 0, 8, ctx->stream);
+    if (e == hipSuccess && bt_table_create(ctx, h.num_records, h.num_samples, h.k, &t) != BT_OK) return BT_ERR;
+    // chunk i is read and checked in pin[i & 1] while chunk i - 1 is copied and unpacked; the one device buffer is reused in stream order
+    for (uint64_t i = 0; e == hipSuccess && error.empty(); ++i) {
+        uint64_t n = 0;
+        e = hipEventSynchronize(st.moved[i & 1]);   // (the copy of chunk i - 2 has left the buffer)
+        if (e != hipSuccess) break;
+        if (!r.next_chunk(&n) || (n && !r.read_records(st.pin[i & 1], n))) {
+            error = r.error;
+            break;
+        }
+        if (n == 0) break;
+        e = hipMemcpyAsync(st.d_buf, st.pin[i & 1], (size_t)(n * rb), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(st.moved[i & 1], ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(table_unpack_kernel, dim3(grid_for(n, BLOCK, ctx->num_cu * 16)), dim3(BLOCK), 0, ctx->stream, t->v, reinterpret_cast<const uint32_t *>(st.d_buf), n, st.d_word);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&dup, st.d_word, 8, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e2 = hipStreamSynchronize(ctx->stream);   // (also on the error paths: the staging buffers are released below)
+    if (e == hipSuccess) e = e2;
+    int ov = 0;
+    if (e != hipSuccess) error = std::string(hipGetErrorString(e));
+    else if (error.empty() && dup) error = std::string("k-mer table checkpoint ") + path + ": " + std::to_string(dup) + " records repeat a key";
+    else if (error.empty() && (bt_table_status(t, nullptr, nullptr, &ov) != BT_OK || ov)) error = ov ? "the table overflowed" : bt_last_error();
+    if (!error.empty()) {
+        bt_table_destroy(t);
+        return fail("bt_table_load: " + error);
+    }
+    *out = t;
+    return BT_OK;
+}
+
+int bt_table_file_info(const char *path, uint32_t *k, uint32_t *num_samples, uint64_t *num_records, char *manifest, size_t manifest_len) {
+    if (!path) return fail("bt_table_file_info: null argument");
+    btfile::Reader r;
+    if (!r.open(path)) return fail("bt_table_file_info: " + r.error);
+    // the whole file is checked (chunk CRCs, trailer) in pieces of at most a mebibyte
+    const uint64_t piece = std::max<uint64_t>((1u << 20) / r.header.record_bytes, 1);
+    std::vector<uint8_t> buf((size_t)(piece * r.header.record_bytes));
+    while (true) {
+        uint64_t n = 0;
+        if (!r.next_chunk(&n)) return fail("bt_table_file_info: " + r.error);
+        if (n == 0) break;
+        for (uint64_t done = 0; done < n; done += piece)
+            if (!r.read_records(buf.data(), std::min(piece, n - done))) return fail("bt_table_file_info: " + r.error);
+    }
+    if (k) *k = r.header.k;
+    if (num_samples) *num_samples = r.header.num_samples;
+    if (num_records) *num_records = r.header.num_records;
+    if (manifest && manifest_len) {
+        const size_t m = std::min(manifest_len - 1, r.header.manifest.size());
+        std::memcpy(manifest, r.header.manifest.data(), m);
+        manifest[m] = 0;
+    }
     return BT_OK;
 }
 

@@ -16,7 +16,7 @@ for s in "${srcs[@]}"; do
   fi
   objs+=("$o")
 done
-hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$out"
+hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$out" -lz   # zlib: the CRC32 of the table checkpoint file (bt_table_file.hpp)
 echo "built $out"
 # libbtcomm.so: the RCCL exchange steps (include/btcomm.h), a library of its own so that libbtgpu.so carries no RCCL dependency
 comm_src="$here/comm/bt_comm.hip"

@@ -432,12 +432,16 @@ void KmerCounter::countInterclusterParameterKmers(bt_table *parameter_table, con
 
 // ---- genotype stage ---------------------------------------------------------------------------------------------------------------
 
-void KmerCounter::countPathKmers(bt_bloom *path_bloom, const InferenceUnit &unit, const UnitGraphs &ug) {
-    std::cout << "[" << getLocalTime() << "] Counting kmers in variant cluster paths ..." << std::endl;
+void KmerCounter::enumeratePathKmers(const InferenceUnit &unit, const UnitGraphs &ug) {
     PathsBatchBuilder builder;
     buildPathsBatch(&builder, unit, ug);
     unit_paths.reset(new PathsHandle());
     check(bt_paths_create(ctx, &builder.batch(), kmer_size, &unit_paths->h, nullptr), "bt_paths_create");
+}
+
+void KmerCounter::countPathKmers(bt_bloom *path_bloom, const InferenceUnit &unit, const UnitGraphs &ug) {
+    std::cout << "[" << getLocalTime() << "] Counting kmers in variant cluster paths ..." << std::endl;
+    enumeratePathKmers(unit, ug);
     check(bt_paths_count_kmers(unit_paths->h, path_bloom), "bt_paths_count_kmers");
     check(bt_sync(ctx), "bt_sync");
 }

@@ -78,6 +78,8 @@ class KmerCounter {
                                          float parameter_kmer_fraction);
     // ---- genotype stage (KmerCounter.cpp:252-555) ----
     void countPathKmers(bt_bloom *path_bloom, const InferenceUnit &unit, const UnitGraphs &graphs);   // keeps the enumerated paths for classifyPathKmers
+    // countPathKmers without the Bloom insert: what a run that loads its table from a checkpoint (BT_TABLE_CHECKPOINT) still needs for classifyPathKmers
+    void enumeratePathKmers(const InferenceUnit &unit, const UnitGraphs &graphs);
     void countInterclusterKmers(bt_table *table, bt_bloom *path_bloom, const std::string &intercluster_regions_prefix, const Chromosomes &chromosomes, const ChromosomePloidy &chrom_ploidy);
     // comm (several ranks): every rank scans its byte range of every sample's database into its replica of the table; the records with
     // counts are then all-gathered and merged, so that every rank holds the table a one-rank scan fills

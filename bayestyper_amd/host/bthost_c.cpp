@@ -17,6 +17,7 @@
 #include "InferenceUnit.hpp"
 #include "KmerCounter.hpp"
 #include "Sample.hpp"
+#include "TableCheckpoint.hpp"
 #include "VariantClusterGraph.hpp"
 #include "VariantFileParser.hpp"
 
@@ -50,6 +51,39 @@ int bth_parse_kmer_lines(const char *text, unsigned long long len, unsigned long
         }
         return 1;
     }
+}
+
+// tableCheckpointManifest (TableCheckpoint.hpp) of inputs given as plain arrays; names are tab-separated.  Returns the length of the text (copied to out when it fits).
+unsigned long long bth_table_checkpoint_manifest(unsigned k, unsigned S, const char *sample_names, const uint8_t *present, const uint64_t *total_kmers, const uint64_t *suf_bytes,
+                                                 const uint32_t *counter_size, const uint32_t *min_count, const uint64_t *max_count, unsigned F, const char *file_names,
+                                                 const uint64_t *file_bytes, const uint32_t *file_crc, unsigned num_chrom, const char *chrom_names, const uint64_t *chrom_length,
+                                                 const uint8_t *chrom_decoy, const uint8_t *female_ploidy, const uint8_t *male_ploidy, char *out, unsigned long long capacity) {
+    auto split = [](const char *names) {
+        std::vector<std::string> v;
+        std::istringstream in(names);
+        for (std::string n; std::getline(in, n, '\t');) v.push_back(n);
+        return v;
+    };
+    const std::vector<std::string> sn = split(sample_names), fn = split(file_names), cn = split(chrom_names);
+    if (sn.size() != S || fn.size() != F || cn.size() != num_chrom) return 0;
+    TableCheckpointInputs in;
+    in.kmer_size = k;
+    for (unsigned s = 0; s < S; s++) {
+        TableCheckpointInputs::SampleDb db;
+        db.name = sn[s];
+        db.present = present[s] != 0;
+        db.total_kmers = total_kmers[s];
+        db.suf_bytes = suf_bytes[s];
+        db.counter_size = counter_size[s];
+        db.min_count = min_count[s];
+        db.max_count = max_count[s];
+        in.samples.push_back(db);
+    }
+    for (unsigned f = 0; f < F; f++) in.files.push_back(TableCheckpointInputs::InputFile{fn[f], file_bytes[f], file_crc[f]});
+    for (unsigned c = 0; c < num_chrom; c++) in.chromosomes.push_back(TableCheckpointInputs::Chromosome{cn[c], chrom_length[c], chrom_decoy[c] != 0, female_ploidy[c], male_ploidy[c]});
+    const std::string m = tableCheckpointManifest(in);
+    if (out && m.size() < capacity) std::memcpy(out, m.c_str(), m.size() + 1);
+    return m.size();
 }
 
 // LUTs for S samples from per-sample (mean, var, multiplicity) of the parameter k-mers and explicit noise rates

@@ -43,12 +43,14 @@
 #include "Genotypes.hpp"
 #include "InferenceEngine.hpp"
 #include "InferenceUnit.hpp"
+#include "KmcFile.hpp"
 #include "KmerCounter.hpp"
 #include "KmerHashOrder.hpp"
 #include "Options.hpp"
 #include "Parallel.hpp"
 #include "Sample.hpp"
 #include "StageTimes.hpp"
+#include "TableCheckpoint.hpp"
 
 using namespace bthost;
 
@@ -303,6 +305,44 @@ void setGenomicCountDistributions(CountDistribution *cd, bt_table *table, const 
     std::cout << "\n" << stamp() << "Wrote genomic parameters to " << output_prefix << ".txt" << std::endl;
 }
 
+// The manifest of this run's k-mer table (TableCheckpoint.hpp).  databases_optional (a run that loads the checkpoint): a sample whose KMC database is not
+// there gets an "absent" line instead of an error.
+std::string tableCheckpointManifest(unsigned kmer_size, const std::vector<Sample> &samples, const Chromosomes &chromosomes, const ChromosomePloidy &chrom_ploidy,
+                                    const std::vector<std::pair<std::string, std::string>> &input_files, bool databases_optional) {
+    TableCheckpointInputs in;
+    in.kmer_size = kmer_size;
+    for (const Sample &sample : samples) {
+        TableCheckpointInputs::SampleDb db;
+        db.name = sample.name;
+        struct stat sb;
+        if (databases_optional && (stat((sample.file + ".kmc_pre").c_str(), &sb) != 0 || stat((sample.file + ".kmc_suf").c_str(), &sb) != 0)) db.present = false;
+        else {
+            const KmcFile kmc(sample.file);
+            if (stat(kmc.suffix_file().c_str(), &sb) != 0) throw std::runtime_error("Unable to open file " + kmc.suffix_file());
+            db.total_kmers = kmc.total_kmers;
+            db.suf_bytes = (uint64_t)sb.st_size;
+            db.counter_size = kmc.counter_size;
+            db.min_count = kmc.min_count;
+            db.max_count = kmc.max_count;
+        }
+        in.samples.push_back(db);
+    }
+    for (auto &f : input_files) in.files.push_back(inputFileIdentity(f.first, f.second));
+    for (size_t i = 0; i < chromosomes.size(); i++) {
+        TableCheckpointInputs::Chromosome c;
+        c.name = chromosomes.name(i);
+        c.length = chromosomes.sequence(i).size();
+        c.is_decoy = chromosomes.isDecoy(c.name);
+        if (!c.is_decoy) {
+            const auto &gp = chrom_ploidy.getGenderPloidy(c.name);
+            c.female_ploidy = gp[0];
+            c.male_ploidy = gp[1];
+        }
+        in.chromosomes.push_back(c);
+    }
+    return tableCheckpointManifest(in);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
     OptionsContainer options("genotype", BT_VERSION, getLocalTime(), kmer_size);
@@ -345,52 +385,102 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
     const int rank = comm ? comm->rank() : 0, world = comm ? comm->world() : 1;
     if (comm) std::cout << stamp() << "Rank " << rank << " of " << world << " (one GPU per rank)" << std::endl;
     KmerCounter kmer_counter(ctx.h, samples, kmer_size, gibbs.seed);
-    std::unique_ptr<BloomHandle> path_kmer_bloom(new BloomHandle());   // ThreadedKmerBloom(num_path_kmers + max_parameter_kmers, 0.0001)
-    check(bt_bloom_create(ctx.h, unit.num_path_kmers + max_parameter_kmers, 0.0001f, kmer_size, 1, &path_kmer_bloom->h), "bt_bloom_create");
-    TableHandle kmer_hash;   // ObservedKmerCountsHash<N>(num_path_kmers + max_parameter_kmers)
-    check(bt_table_create(ctx.h, unit.num_path_kmers + max_parameter_kmers, (uint32_t)S, kmer_size, &kmer_hash.h), "bt_table_create");
-
-    std::cout << "\n" << stamp() << "Parsing parameter kmers ..." << std::endl;
-    uint64_t num_parameter_kmers = 0;
-    {
-        StageScope stage("parameter k-mers");
-        const std::string text = readGzFile(parameter_kmers_dir_prefix + ".fa.gz");
-        const size_t header_end = std::min(text.find('\n'), text.size());
-        const std::string header = text.substr(0, header_end);
-        if (header != ">k" + std::to_string(kmer_size)) throw std::runtime_error(parameter_kmers_dir_prefix + ".fa.gz was written for another kmer size (" + header + ")");
-        std::vector<uint64_t> kmers;
-        try {   // (the lines are parsed by the -p host threads: a million k-mers were 0.3 s of a chr20-sized run on one)
-            kmers = parseKmerLines(text, header_end + 1, kmer_size, clampThreads(options.getUInt("threads")));
-        } catch (const std::runtime_error &e) {
-            throw std::runtime_error(std::string(e.what()) + " in " + parameter_kmers_dir_prefix + ".fa.gz");
+    const ChromosomePloidy chrom_ploidy(options.getString("chromosome-ploidy-file"), chromosomes, samples);
+    // BT_TABLE_CHECKPOINT=<file> (SURVEY §5 "Checkpoint / resume"; an environment switch, so that the ##BayesTyperOptions= line and every output stay what they
+    // are): the table as it is after parseSampleKmers — a function of the unit's inputs alone, not of the seed, the Gibbs options, the filters or the mode —
+    // is saved to <file> when the file is absent and loaded from it when it is there.  A file written for other inputs, or a damaged one, ends the run.
+    const char *checkpoint_env = getenv("BT_TABLE_CHECKPOINT");
+    const std::string checkpoint_file = checkpoint_env ? checkpoint_env : "";
+    bool checkpoint_load = false;
+    std::string checkpoint_manifest;
+    if (!checkpoint_file.empty()) {
+        struct stat sb;
+        checkpoint_load = stat(checkpoint_file.c_str(), &sb) == 0;
+        if (comm) {   // (the ranks take the same route: a file that only some of them see would leave the others waiting in the scans' collectives)
+            uint64_t votes[2] = {checkpoint_load ? 1u : 0u, checkpoint_load ? 0u : 1u};
+            comm->allreduceHist(votes, 2);
+            if (votes[0] && votes[1]) throw std::runtime_error("BT_TABLE_CHECKPOINT: " + checkpoint_file + " is there for some ranks and absent for others");
         }
-        num_parameter_kmers = kmers.size() / 2;
-        if (num_parameter_kmers > max_parameter_kmers) throw std::runtime_error("more than " + std::to_string(max_parameter_kmers) + " parameter kmers");
-        if (num_parameter_kmers) {   // path_kmer_bloom->addKmer + kmer_hash->addKmer + isParameter(true) (main.cpp:560-577)
-            void *d = nullptr;
-            check(bt_malloc(ctx.h, kmers.size() * 8, &d), "bt_malloc");
-            int rc = bt_memcpy_h2d(ctx.h, d, kmers.data(), kmers.size() * 8);
-            if (rc == BT_OK) rc = bt_bloom_insert_batch(path_kmer_bloom->h, (const uint64_t *)d, num_parameter_kmers);
-            if (rc == BT_OK) rc = bt_table_insert_batch(kmer_hash.h, (const uint64_t *)d, num_parameter_kmers, 1);
-            if (rc == BT_OK) rc = bt_sync(ctx.h);
-            bt_free(ctx.h, d);
-            check(rc, "parameter kmers");
-        }
+        StageScope stage("k-mer table checkpoint manifest");
+        checkpoint_manifest = tableCheckpointManifest(kmer_size, samples, chromosomes, chrom_ploidy,
+                                                      {{"variant_clusters.bin", options.getString("variant-clusters-file")},
+                                                       {"parameter_kmers.fa.gz", parameter_kmers_dir_prefix + ".fa.gz"},
+                                                       {"intercluster_regions.txt.gz", intercluster_regions_dir_prefix + ".txt.gz"}},
+                                                      checkpoint_load);
     }
-    std::cout << stamp() << "Parsed " << num_parameter_kmers << " kmers" << std::endl;
+    std::unique_ptr<BloomHandle> path_kmer_bloom;
+    TableHandle kmer_hash;
+    if (checkpoint_load) {
+        std::cout << "\n" << stamp() << "Loading the kmer table from checkpoint " << checkpoint_file << " ..." << std::endl;
+        StageScope stage("load k-mer table checkpoint");
+        if (checkpoint_manifest.find("=absent\n") != std::string::npos) {   // (a second pass over the file, only taken when a database has been moved away)
+            std::vector<char> stored((1u << 24) + 1);
+            check(bt_table_file_info(checkpoint_file.c_str(), nullptr, nullptr, nullptr, stored.data(), stored.size()), "BT_TABLE_CHECKPOINT");
+            checkpoint_manifest = adoptAbsentDatabases(checkpoint_manifest, stored.data());
+            std::cout << stamp() << "KMC database(s) absent: their identity is taken from the checkpoint" << std::endl;
+        }
+        check(bt_table_load(ctx.h, checkpoint_file.c_str(), checkpoint_manifest.c_str(), &kmer_hash.h), "BT_TABLE_CHECKPOINT");
+        uint64_t num_kmers = 0;
+        check(bt_table_status(kmer_hash.h, &num_kmers, nullptr, nullptr), "bt_table_status");
+        std::cout << stamp() << "Loaded " << num_kmers << " kmers: skipped parsing parameter kmers, the path kmer bloom filter, counting inter-cluster kmers and parsing sample kmers (KMC scans)"
+                  << std::endl;
+    } else {
+        path_kmer_bloom.reset(new BloomHandle());   // ThreadedKmerBloom(num_path_kmers + max_parameter_kmers, 0.0001)
+        check(bt_bloom_create(ctx.h, unit.num_path_kmers + max_parameter_kmers, 0.0001f, kmer_size, 1, &path_kmer_bloom->h), "bt_bloom_create");
+        // ObservedKmerCountsHash<N>(num_path_kmers + max_parameter_kmers)
+        check(bt_table_create(ctx.h, unit.num_path_kmers + max_parameter_kmers, (uint32_t)S, kmer_size, &kmer_hash.h), "bt_table_create");
+
+        std::cout << "\n" << stamp() << "Parsing parameter kmers ..." << std::endl;
+        uint64_t num_parameter_kmers = 0;
+        {
+            StageScope stage("parameter k-mers");
+            const std::string text = readGzFile(parameter_kmers_dir_prefix + ".fa.gz");
+            const size_t header_end = std::min(text.find('\n'), text.size());
+            const std::string header = text.substr(0, header_end);
+            if (header != ">k" + std::to_string(kmer_size)) throw std::runtime_error(parameter_kmers_dir_prefix + ".fa.gz was written for another kmer size (" + header + ")");
+            std::vector<uint64_t> kmers;
+            try {   // (the lines are parsed by the -p host threads: a million k-mers were 0.3 s of a chr20-sized run on one)
+                kmers = parseKmerLines(text, header_end + 1, kmer_size, clampThreads(options.getUInt("threads")));
+            } catch (const std::runtime_error &e) {
+                throw std::runtime_error(std::string(e.what()) + " in " + parameter_kmers_dir_prefix + ".fa.gz");
+            }
+            num_parameter_kmers = kmers.size() / 2;
+            if (num_parameter_kmers > max_parameter_kmers) throw std::runtime_error("more than " + std::to_string(max_parameter_kmers) + " parameter kmers");
+            if (num_parameter_kmers) {   // path_kmer_bloom->addKmer + kmer_hash->addKmer + isParameter(true) (main.cpp:560-577)
+                void *d = nullptr;
+                check(bt_malloc(ctx.h, kmers.size() * 8, &d), "bt_malloc");
+                int rc = bt_memcpy_h2d(ctx.h, d, kmers.data(), kmers.size() * 8);
+                if (rc == BT_OK) rc = bt_bloom_insert_batch(path_kmer_bloom->h, (const uint64_t *)d, num_parameter_kmers);
+                if (rc == BT_OK) rc = bt_table_insert_batch(kmer_hash.h, (const uint64_t *)d, num_parameter_kmers, 1);
+                if (rc == BT_OK) rc = bt_sync(ctx.h);
+                bt_free(ctx.h, d);
+                check(rc, "parameter kmers");
+            }
+        }
+        std::cout << stamp() << "Parsed " << num_parameter_kmers << " kmers" << std::endl;
+    }
     std::cout << "\n" << std::endl;
 
-    const ChromosomePloidy chrom_ploidy(options.getString("chromosome-ploidy-file"), chromosomes, samples);
     st.reset(new StageScope("construct variant cluster graphs (host)"));
     const UnitGraphs graphs(unit, chromosomes, kmer_size, clampThreads(options.getUInt("threads")));
-    st.reset(new StageScope("count path k-mers (enumerate + Bloom insert)"));
-    kmer_counter.countPathKmers(path_kmer_bloom->h, unit, graphs);
-    st.reset(new StageScope("count inter-cluster k-mers"));
-    kmer_counter.countInterclusterKmers(kmer_hash.h, path_kmer_bloom->h, intercluster_regions_dir_prefix, chromosomes, chrom_ploidy);
-    std::cout << std::endl;
-    st.reset(new StageScope("parse sample k-mers (KMC scan incl. H2D)"));
-    kmer_counter.parseSampleKmers(kmer_hash.h, path_kmer_bloom->h, comm.get());
-    path_kmer_bloom.reset();
+    if (checkpoint_load) {   // classification and the candidates need the unit's paths; only their Bloom insert goes
+        st.reset(new StageScope("enumerate path k-mers (no Bloom insert)"));
+        kmer_counter.enumeratePathKmers(unit, graphs);
+    } else {
+        st.reset(new StageScope("count path k-mers (enumerate + Bloom insert)"));
+        kmer_counter.countPathKmers(path_kmer_bloom->h, unit, graphs);
+        st.reset(new StageScope("count inter-cluster k-mers"));
+        kmer_counter.countInterclusterKmers(kmer_hash.h, path_kmer_bloom->h, intercluster_regions_dir_prefix, chromosomes, chrom_ploidy);
+        std::cout << std::endl;
+        st.reset(new StageScope("parse sample k-mers (KMC scan incl. H2D)"));
+        kmer_counter.parseSampleKmers(kmer_hash.h, path_kmer_bloom->h, comm.get());
+        path_kmer_bloom.reset();
+        if (!checkpoint_file.empty() && rank == 0) {   // (several ranks: after the merge every rank holds the whole table)
+            st.reset(new StageScope("save k-mer table checkpoint"));
+            check(bt_table_save(kmer_hash.h, checkpoint_file.c_str(), checkpoint_manifest.c_str()), "BT_TABLE_CHECKPOINT");
+            std::cout << stamp() << "Saved the kmer table to checkpoint " << checkpoint_file << std::endl;
+        }
+    }
     std::cout << std::endl;
     st.reset(new StageScope("classify path k-mers + haplotype candidates"));
     const GibbsBatchData batch = kmer_counter.classifyPathKmers(kmer_hash.h, unit, graphs, multigroup_kmers_dir_prefix, chrom_ploidy);

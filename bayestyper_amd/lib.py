@@ -66,6 +66,12 @@ bt_table_insert_batch = _sig("bt_table_insert_batch", [vp, vp, C.c_uint64, C.c_i
 bt_table_find_batch = _sig("bt_table_find_batch", [vp, vp, C.c_uint64, vp])
 bt_table_read_slots = _sig("bt_table_read_slots", [vp, vp, C.c_uint64, vp, vp])
 bt_table_export = _sig("bt_table_export", [vp, vp, vp, vp, C.c_uint64, u64p])
+bt_table_record_bytes = _sig("bt_table_record_bytes", [vp, u32p])
+bt_table_pack = _sig("bt_table_pack", [vp, vp, C.c_uint64, u64p])
+bt_table_unpack = _sig("bt_table_unpack", [vp, vp, C.c_uint64])
+bt_table_save = _sig("bt_table_save", [vp, C.c_char_p, C.c_char_p])
+bt_table_load = _sig("bt_table_load", [vp, C.c_char_p, C.c_char_p, C.POINTER(vp)])
+bt_table_file_info = _sig("bt_table_file_info", [C.c_char_p, u32p, u32p, u64p, C.c_char_p, C.c_size_t])
 bt_find_paths_create = _sig("bt_find_paths_create", [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)])
 bt_find_paths_destroy = _sig("bt_find_paths_destroy", [vp])
 bt_find_paths_sample = _sig("bt_find_paths_sample", [vp, vp, vp])
@@ -354,10 +360,58 @@ class Table:
         n = w.value
         return kmers[:n], counts[:n], meta[:n]
 
+    def record_bytes(self):
+        """bytes of a packed record: 16 key + 4 meta + the counts padded to a multiple of four"""
+        rb = C.c_uint32()
+        check(bt_table_record_bytes(self.h, C.byref(rb)))
+        return rb.value
+
+    def pack(self):
+        """bt_table_pack -> (DeviceBuffer of packed records, number of records); the caller frees the buffer"""
+        n = C.c_uint64()
+        check(bt_table_pack(self.h, None, 0, C.byref(n)))
+        buf = self.ctx.buffer(max(n.value, 1) * self.record_bytes())
+        try:
+            check(bt_table_pack(self.h, buf.ptr, max(n.value, 1), C.byref(n)))
+        except BtError:
+            buf.free()
+            raise
+        return buf, n.value
+
+    def unpack(self, buf, n):
+        """bt_table_unpack of the first n packed records of a DeviceBuffer: their meta bytes and counts are set, a key already present is an error"""
+        assert int(n) * self.record_bytes() <= buf.nbytes
+        check(bt_table_unpack(self.h, buf.ptr, int(n)))
+
+    def save(self, path, manifest=""):
+        check(bt_table_save(self.h, os.fsencode(path), manifest.encode()))
+
+    @classmethod
+    def load(cls, ctx, path, manifest=None):
+        """bt_table_load: a new table from a checkpoint file; manifest (when given) must equal the file's"""
+        h = vp()
+        check(bt_table_load(ctx.h, os.fsencode(path), None if manifest is None else manifest.encode(), C.byref(h)))
+        info = table_file_info(path)
+        t = cls.__new__(cls)
+        t.ctx, t.num_samples, t.k, t.h = ctx, info["num_samples"], info["k"], h.value
+        return t
+
     def close(self):
         if self.h:
             bt_table_destroy(self.h)
             self.h = None
+
+
+def table_file_info(path):
+    """bt_table_file_info (no GPU): the verified header of a table checkpoint -> {"k", "num_samples", "num_records", "manifest"}"""
+    k, ns, n = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    size = 1 << 16
+    while True:
+        text = C.create_string_buffer(size)
+        check(bt_table_file_info(os.fsencode(path), C.byref(k), C.byref(ns), C.byref(n), text, size))
+        if len(text.value) < size - 1 or size > 1 << 24:
+            return {"k": k.value, "num_samples": ns.value, "num_records": n.value, "manifest": text.value.decode()}
+        size = (1 << 24) + 1
 
 
 CAND_FIELDS = [("kmer_off", np.uint32), ("hap_kmer_mult", np.uint8), ("kmer_key", np.uint64), ("kmer_has_counts", np.uint8), ("kmer_counts", np.uint8),

@@ -178,6 +178,29 @@ int bt_table_export(bt_table *t, uint64_t *h_kmers, uint8_t *h_counts, uint8_t *
 int bt_table_count_row_bytes(bt_table *t, uint32_t *row_bytes);
 int bt_table_export_count_rows(bt_table *t, uint8_t *d_rows, uint64_t capacity_rows, uint64_t *h_num_rows);
 int bt_table_merge_count_rows(bt_table *t, const uint8_t *d_rows, uint64_t num_rows);
+/* The table as packed records, and a checkpoint file of them.  The reference has no counterpart: a genotype run always rebuilds its table; this is
+ * the "optionally persist the matched k-mer table per unit (cheap restart of Gibbs)" of SURVEY.md §5, row "Checkpoint / resume".
+ * A packed record = 16 key bytes (lo, hi, little endian) + the 4 meta bytes in bt_table_read_slots' order + the samples' counts padded with
+ * zeros to a multiple of four: *record_bytes = 20 + that.  Record order is unspecified (as bt_table_export's).
+ * bt_table_pack: every stored record -> d_records (device, capacity_records records); *h_num_records = number of stored records.  Capacity 0 and
+ *   d_records NULL only counts; a capacity that is too small is an error and nothing is written.
+ * bt_table_unpack: addKmer of every record's key, then its meta bytes and counts are SET (not added).  A record whose key the table already holds
+ *   (or that repeats an earlier record's key) is not applied and the call fails; a full table raises the overflow flag (bt_table_status). */
+int bt_table_record_bytes(bt_table *t, uint32_t *record_bytes);
+int bt_table_pack(bt_table *t, uint8_t *d_records, uint64_t capacity_records, uint64_t *h_num_records);
+int bt_table_unpack(bt_table *t, const uint8_t *d_records, uint64_t num_records);
+/* bt_table_save: the table's records -> the file `path` (written as <path>.tmp and renamed when complete), with the caller's `manifest` text (NULL = "")
+ *   — whatever identifies the inputs the table was computed from.  File: header (magic "BTAMDKTBL1", version, k, num_samples, record bytes, record
+ *   count, largest chunk, length-prefixed manifest, CRC32), chunks ("CHNK", record count, records, CRC32), trailer ("TEND", record count, CRC32); all
+ *   little endian.  The table is walked in ranges of 2^22 slots (BT_TABLE_CKPT_SLOTS lowers that): packed on the device, copied out through pinned
+ *   memory while the previous range is written; the host holds two ranges at most.
+ * bt_table_load: a new table sized as bt_table_create(expected_size = record count) holding the file's records.  Header, every chunk's CRC, the
+ *   trailer and — unless expected_manifest is NULL — the manifest are verified; any mismatch is an error (a manifest mismatch names the first line
+ *   that differs), *out stays NULL and nothing is kept.
+ * bt_table_file_info: the same verification of the whole file and its header fields, without a GPU (manifest: NUL-terminated, truncated to manifest_len). */
+int bt_table_save(bt_table *t, const char *path, const char *manifest);
+int bt_table_load(bt_ctx *ctx, const char *path, const char *expected_manifest /* NULL: any */, bt_table **out);
+int bt_table_file_info(const char *path, uint32_t *k, uint32_t *num_samples, uint64_t *num_records, char *manifest, size_t manifest_len);
 
 /* ObservedKmerCountsHash<N>::calculateKmerStats (src/bayesTyper/KmerHash.cpp:256-340): one pass over the table.
  * h_class_counts[7] = {total, unique, multicluster, decoy, max_multiplicity, multigroup, non_cluster} exactly as the reference
