@@ -652,6 +652,9 @@ struct bt_gibbs {
     uint64_t wire_cap = 0;
     uint32_t *d_geno = nullptr;   // bt_gibbs_genotypes' string
     uint64_t geno_cap = 0;
+    uint8_t *d_text = nullptr;    // bt_gibbs_genotype_text's text and index
+    uint32_t *d_text_index = nullptr;
+    uint64_t text_cap = 0, text_index_cap = 0;
     std::vector<uint32_t> h_var_off;   // [C+1] first variant of every cluster among the launch's variants
     uint64_t trace_words = 0;
     // bt_gibbs_noise_iteration: pinned staging of the histogram (device -> host) and of the noise table (host -> device), device histogram
@@ -2342,6 +2345,8 @@ int bt_gibbs_destroy(bt_gibbs *g) {
     if (g->d_trace_counter) (void)hipFree(g->d_trace_counter);
     if (g->d_wire) (void)hipFree(g->d_wire);
     if (g->d_geno) (void)hipFree(g->d_geno);
+    if (g->d_text) (void)hipFree(g->d_text);
+    if (g->d_text_index) (void)hipFree(g->d_text_index);
     {
         const size_t nh = (size_t)g->S * 256;
         if (g->recycles) {
@@ -3196,6 +3201,52 @@ int bt_gibbs_genotypes(bt_gibbs *g, const bt_genotype_filters *f, const uint32_t
     }
     *d_words = g->d_geno;
     *num_words = total;
+    return BT_OK;
+}
+
+// bt_gibbs_genotypes, then the text passes (bt_genotype_text.hip) over its string, into buffers the sampler keeps.  Replaces the formatting of
+// GenotypeWriter.cpp:84-143,261-345 on the writer's threads.
+int bt_gibbs_genotype_text(bt_gibbs *g, const bt_genotype_filters *f, const uint8_t **d_text, uint64_t *text_bytes, const uint32_t **d_index, uint64_t *index_words,
+                           uint32_t *num_not_covered) {
+    if (!g || !f || !f->min_fraction_observed_kmers || !d_text || !text_bytes || !d_index || !index_words || !num_not_covered) return fail("bt_gibbs_genotype_text: null argument");
+    const uint32_t *d_words = nullptr;
+    uint64_t num_words = 0;
+    int rc = bt_gibbs_genotypes(g, f, &d_words, &num_words);
+    if (rc != BT_OK) {   // the same errors, under this entry's name
+        std::string msg = bt_last_error();
+        const std::string from = "bt_gibbs_genotypes";
+        if (msg.compare(0, from.size(), from) == 0) msg = "bt_gibbs_genotype_text" + msg.substr(from.size());
+        return fail(msg);
+    }
+    bt::GenoTextShape sh;
+    rc = bt::geno_text_shape(g->ctx, d_words, num_words, sh, "bt_gibbs_genotype_text");
+    if (rc != BT_OK) return rc;
+    if (g->text_index_cap < sh.index_words) {
+        uint32_t *grown = nullptr;
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&grown), sh.index_words * 4));
+        if (g->d_text_index) (void)hipFree(g->d_text_index);
+        g->d_text_index = grown;
+        g->text_index_cap = sh.index_words;
+    }
+    uint64_t total = 0;
+    rc = bt::geno_text_count(g->ctx, d_words, sh, g->d_text_index, &total, num_not_covered, "bt_gibbs_genotype_text");
+    if (rc != BT_OK) return rc;
+    if (g->text_cap < total) {
+        uint8_t *grown = nullptr;
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&grown), total));
+        if (g->d_text) (void)hipFree(g->d_text);
+        g->d_text = grown;
+        g->text_cap = total;
+    }
+    rc = bt::geno_text_write(g->ctx, d_words, sh, g->d_text_index, g->d_text);
+    if (rc != BT_OK) return rc;
+    if (getenv("BT_GIBBS_DEBUG"))
+        fprintf(stderr, "bt_gibbs_genotype_text: %u variants, %llu text bytes, %llu index words, %u not covered (record string: %llu words)\n", sh.NV, (unsigned long long)total,
+                (unsigned long long)sh.index_words, *num_not_covered, (unsigned long long)num_words);
+    *d_text = g->d_text;
+    *text_bytes = total;
+    *d_index = g->d_text_index;
+    *index_words = sh.index_words;
     return BT_OK;
 }
 

@@ -118,6 +118,16 @@ int paths_device_candidates(bt_paths *p, const char *who, PathsCandidates *out);
 int paths_number_shared(bt_paths *p, const uint32_t *group_cluster_off, uint32_t G, int32_t **d_kmer_shared, uint32_t *h_group_num_shared);
 // the device arrays change owner (appended to allocs; the row keys are released): the handle reports "no candidates" afterwards
 void paths_release_candidates(bt_paths *p, std::vector<void *> &allocs);
+
+// The seam between bt_genotype_text.hip and bt_gibbs.hip (bt_gibbs_genotype_text): the passes of bt_genotype_text over a record string in device memory.
+struct GenoTextShape {
+    uint32_t C = 0, NV = 0, S = 0;
+    uint64_t at_voff = 0, index_words = 0;   // word offset of the string's var_off table; length of the index
+    std::vector<uint32_t> tables;            // host copy of cluster_var_off [C+1] and var_off [NV+1], checked against the string's length
+};
+int geno_text_shape(bt_ctx *ctx, const uint32_t *d_words, uint64_t num_words, GenoTextShape &sh, const char *who);
+int geno_text_count(bt_ctx *ctx, const uint32_t *d_words, const GenoTextShape &sh, uint32_t *d_index, uint64_t *text_bytes, uint32_t *not_covered, const char *who);
+int geno_text_write(bt_ctx *ctx, const uint32_t *d_words, const GenoTextShape &sh, uint32_t *d_index, uint8_t *d_text);
 }  // namespace bt
 
 struct bt_timer {

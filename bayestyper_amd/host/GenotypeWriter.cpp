@@ -44,6 +44,22 @@ void GenotypeWriter::addGenotypes(const ClusterAnnotation &where, const VariantI
 
 GenotypeWriter::GenotypedVariant GenotypeWriter::formatGenotypes(const ClusterAnnotation &where, const VariantInfo &variant_info, const VariantGenotypes &genotypes,
                                                                  const std::string &sample_columns) const {
+    const std::string stats = formatQualityFilterAndStats(genotypes), cover = formatAlleleCover(genotypes);   // QUAL, FILTER, AC/AF/AN/ACP; ";ANC=..." or nothing
+    return formatLine(where, variant_info, stats.data(), stats.size(), cover.data(), cover.size(), sample_columns);
+}
+
+GenotypeWriter::GenotypedVariant GenotypeWriter::formatGenotypesFromText(const ClusterAnnotation &where, const VariantInfo &variant_info, const std::string &quality_and_filter,
+                                                                         const char *stats, size_t stats_len, const char *cover, size_t cover_len,
+                                                                         const std::string &sample_columns) const {
+    std::string qfs = quality_and_filter;
+    qfs += '\t';
+    qfs.append(stats, stats_len);
+    return formatLine(where, variant_info, qfs.data(), qfs.size(), cover, cover_len, sample_columns);
+}
+
+// quality_filter_stats = "<QUAL>\t<FILTER>\tAC=..;AF=..;AN=..;ACP=..", cover = ";ANC=..." or nothing
+GenotypeWriter::GenotypedVariant GenotypeWriter::formatLine(const ClusterAnnotation &where, const VariantInfo &variant_info, const char *quality_filter_stats, size_t qfs_len,
+                                                            const char *cover, size_t cover_len, const std::string &sample_columns) const {
     const int chrom = chromosomes.find(where.chrom_name);
     if (chrom < 0) throw std::runtime_error("GenotypeWriter: unknown chromosome " + where.chrom_name);
     const std::string &chrom_sequence = chromosomes.sequence((size_t)chrom);
@@ -56,10 +72,11 @@ GenotypeWriter::GenotypedVariant GenotypeWriter::formatGenotypes(const ClusterAn
         os << (a ? "," : "") << alt.sequence << chrom_sequence.substr(variant_info.position + alt.ref_length - 1, max_ref_length - alt.ref_length);
     }
     if (variant_info.has_dependency) os << ",*";
-    os << "\t" << formatQualityFilterAndStats(genotypes);   // QUAL, FILTER, AC/AF/AN/ACP
+    os << "\t";
+    os.write(quality_filter_stats, (std::streamsize)qfs_len);
     os << ";VCS=" << where.variant_cluster_size << ";VCR=" << where.variant_cluster_region << ";VCGS=" << where.variant_cluster_group_size << ";VCGR=" << where.variant_cluster_group_region
        << ";HC=" << where.num_candidates;
-    os << formatAlleleCover(genotypes);   // ";ANC=..." or nothing
+    os.write(cover, (std::streamsize)cover_len);
     os << ";ACO=";                        // :232-259
     for (size_t a = 0; a < variant_info.alt_alleles.size(); a++) os << (a ? "," : "") << (variant_info.alt_alleles[a].aco_att.empty() ? "." : variant_info.alt_alleles[a].aco_att);
     if (variant_info.has_dependency) os << ",.";

@@ -45,6 +45,10 @@ class GenotypeWriter {
     void addGenotypes(const ClusterAnnotation &where, const VariantInfo &variant_info, const VariantGenotypes &genotypes, const std::string &sample_columns);
     // the same in two steps, so that worker threads can format (const, thread-safe) and one thread appends in the order of a one-thread run
     GenotypedVariant formatGenotypes(const ClusterAnnotation &where, const VariantInfo &variant_info, const VariantGenotypes &genotypes, const std::string &sample_columns) const;
+    // the same line from text formatted on the device (bt_gibbs_genotype_text): quality_and_filter = formatQualityAndFilter(...), stats = "AC=..;AF=..;AN=..;ACP=..",
+    // cover = ";ANC=.." or empty, sample_columns = the samples piece with the GQs spliced in; the host adds ALT, the cluster annotations, ACO and FORMAT
+    GenotypedVariant formatGenotypesFromText(const ClusterAnnotation &where, const VariantInfo &variant_info, const std::string &quality_and_filter, const char *stats, size_t stats_len,
+                                             const char *cover, size_t cover_len, const std::string &sample_columns) const;
     void append(const std::string &chrom_name, GenotypedVariant &&variant) { genotyped_variants[chrom_name].push_back(std::move(variant)); }
     std::string generateHeader(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header) const;   // :494-551
     // header + sorted lines (finalise :352-492); the file variant writes <output_prefix>.vcf or .vcf.gz and returns the number of variants
@@ -53,6 +57,8 @@ class GenotypeWriter {
                       const std::string &genotype_options_header);
 
   private:
+    GenotypedVariant formatLine(const ClusterAnnotation &where, const VariantInfo &variant_info, const char *quality_filter_stats, size_t qfs_len, const char *cover, size_t cover_len,
+                                const std::string &sample_columns) const;
     std::vector<std::string> samples;
     const Chromosomes &chromosomes;
     std::unordered_map<std::string, std::vector<GenotypedVariant>> genotyped_variants;

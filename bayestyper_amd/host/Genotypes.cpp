@@ -139,13 +139,19 @@ void writeAlleleField(std::ostream &o, const std::vector<T> &v) {   // GenotypeW
 }
 }  // namespace
 
+std::string formatQualityAndFilter(float max_alt_allele_call_probability, uint32_t total_count) {
+    std::ostringstream o;
+    if (floatCompare(max_alt_allele_call_probability, 1)) o << "99";
+    else if (floatCompare(max_alt_allele_call_probability, 0)) o << "0";
+    else o << -10 * std::log10(1 - max_alt_allele_call_probability);
+    o << (total_count == 0 ? "\tAN0" : "\tPASS");
+    return o.str();
+}
+
 std::string formatQualityFilterAndStats(const VariantGenotypes &g) {
     std::ostringstream o;
     const VariantStats &vs = g.variant_stats;
-    if (floatCompare(vs.max_alt_allele_call_probability, 1)) o << "99";
-    else if (floatCompare(vs.max_alt_allele_call_probability, 0)) o << "0";
-    else o << -10 * std::log10(1 - vs.max_alt_allele_call_probability);
-    o << (vs.total_count == 0 ? "\tAN0" : "\tPASS");
+    o << formatQualityAndFilter(vs.max_alt_allele_call_probability, vs.total_count);
     o << "\tAC=";
     writeAlleleField(o, vs.alt_allele_counts);
     o << ";AF=";

@@ -63,6 +63,8 @@ std::vector<VariantGenotypes> getGenotypes(const ClusterResults &r, const Filter
 std::string formatVariantStatsColumns(const VariantGenotypes &g);
 // the two halves of the above: GenotypeWriter puts the cluster annotations (VCS .. HC) between them
 std::string formatQualityFilterAndStats(const VariantGenotypes &g);   // "<QUAL>\t<FILTER>\tAC=..;AF=..;AN=..;ACP=.."
+// "<QUAL>\t<FILTER>" alone, from the two values it depends on (what the device's text route keeps on the host: bt_gibbs_genotype_text's index carries both)
+std::string formatQualityAndFilter(float max_alt_allele_call_probability, uint32_t total_count);
 std::string formatAlleleCover(const VariantGenotypes &g);             // ";ANC=.." or ""
 std::string formatSampleColumns(const ClusterResults &r, uint32_t variant, const VariantGenotypes &g);
 // the same text from the three k-mer means per (sample, allele) — KmerStats::getMean of the count / fraction / mean statistics, means[(s * A + a) * 3 + k] —

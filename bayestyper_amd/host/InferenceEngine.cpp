@@ -160,6 +160,10 @@ struct GpuSampler : GibbsSampler {
         check(bt_gibbs_genotypes(g, &filters, d_words, num_words), "bt_gibbs_genotypes");
         return true;
     }
+    bool genotypeText(const bt_genotype_filters &filters, const uint8_t **d_text, uint64_t *text_bytes, const uint32_t **d_index, uint64_t *index_words, uint32_t *not_covered) override {
+        check(bt_gibbs_genotype_text(g, &filters, d_text, text_bytes, d_index, index_words, not_covered), "bt_gibbs_genotype_text");
+        return true;
+    }
     BatchResults results(uint32_t num_clusters) override {
         BatchResults r;
         uint64_t nd = 0, nc = 0;
@@ -508,6 +512,26 @@ void InferenceEngine::handOver(std::unique_ptr<Sampler> &sampler, const GibbsBat
         const char *label = geno_wire ? "genotypes on the device (bt_gibbs_genotypes, string stays on the device)" : "genotypes on the device (bt_gibbs_genotypes + one copy)";
         const auto t0 = std::chrono::steady_clock::now();
         const bt_genotype_filters f{geno_min_gpp, geno_min_kmers, geno_min_fraction.data()};
+        if (geno_text && geno_collect && !geno_wire) {   // the text route: the device formats, two copies
+            const uint8_t *d_text = nullptr;
+            const uint32_t *d_index = nullptr;
+            uint64_t text_bytes = 0, index_words = 0;
+            uint32_t not_covered = 0;
+            if (sampler->genotypeText(f, &d_text, &text_bytes, &d_index, &index_words, &not_covered)) {
+                if (not_covered == 0) {
+                    std::vector<uint8_t> text(text_bytes);
+                    std::vector<uint32_t> index(index_words);
+                    if ((text_bytes && bt_memcpy_d2h(ctx, text.data(), d_text, text_bytes) != BT_OK) || (index_words && bt_memcpy_d2h(ctx, index.data(), d_index, index_words * 4) != BT_OK))
+                        throw std::runtime_error(std::string("bt_memcpy_d2h: ") + bt_last_error());
+                    sampler.reset();
+                    StageTimes::get().add("genotype text on the device (bt_gibbs_genotype_text + copies)", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                    geno_text(batch, text, index);
+                    return;
+                }
+                std::cerr << "genotype text on the device: " << not_covered << " variant(s) of this launch hold a value outside the device formatter's range; the launch takes the records route"
+                          << std::endl;
+            }
+        }
         if (sampler->genotypeWords(f, &d_words, &num_words)) {
             std::vector<uint32_t> words;
             if (geno_wire) geno_wire(batch, d_words, num_words);

@@ -103,6 +103,12 @@ struct GibbsSampler {
     // the launch's genotype summaries computed on the sampler's side, as one word string in its DEVICE memory (bt_gibbs_genotypes; valid while the sampler
     // lives); false: not supported — the caller then takes the samples (results / resultWords) and summarises them on the host
     virtual bool genotypeWords(const bt_genotype_filters & /*filters*/, const uint32_t ** /*d_words*/, uint64_t * /*num_words*/) { return false; }
+    // the same summaries as TEXT formatted on the sampler's side, with its index, both in its DEVICE memory (bt_gibbs_genotype_text; valid while the sampler
+    // lives); *not_covered = variants holding a value the device's formatter does not cover (their text is not to be used); false: not supported
+    virtual bool genotypeText(const bt_genotype_filters & /*filters*/, const uint8_t ** /*d_text*/, uint64_t * /*text_bytes*/, const uint32_t ** /*d_index*/, uint64_t * /*index_words*/,
+                              uint32_t * /*not_covered*/) {
+        return false;
+    }
 };
 typedef std::function<std::unique_ptr<GibbsSampler>(const bt_gibbs_params &, const GibbsBatchData &)> SamplerFactory;
 
@@ -127,6 +133,11 @@ class InferenceEngine {
         geno_collect = std::move(on_host);
         geno_wire = std::move(on_device);
     }
+    // The text route on top of the device route (one process, a genotype collector `on_host` registered): a finished launch hands over the genotype text the
+    // device formatted and its index (GibbsSampler::genotypeText) after one copy of each.  A launch with a not-covered variant, or a sampler without the text,
+    // takes the records route above.
+    typedef std::function<void(const GibbsBatchData &batch, const std::vector<uint8_t> &text, const std::vector<uint32_t> &index)> GenotypeTextCollector;
+    void setGenotypeTextCollector(GenotypeTextCollector t) { geno_text = std::move(t); }
     typedef std::function<void(uint64_t *hist, size_t n)> HistReducer;   // sums the S*256 counters over all ranks in place
 
     InferenceEngine(bt_ctx *ctx, std::vector<uint8_t> gender, std::vector<std::string> sample_names, const GibbsOptions &options, HistReducer reduce_hist = nullptr);
@@ -165,6 +176,7 @@ class InferenceEngine {
     WireCollector wire_collect;
     GenotypeCollector geno_collect;
     WireCollector geno_wire;
+    GenotypeTextCollector geno_text;
     float geno_min_gpp = 0, geno_min_kmers = 0;
     std::vector<float> geno_min_fraction;
     bt_ctx *ctx;

@@ -730,6 +730,17 @@ int bth_kmc_info(const char *kmc_prefix, unsigned long long *out) {
 
 // the genotype-derived output columns of every variant of one cluster, one line per variant ("<stats columns><sample columns>\n");
 // returns the number of bytes needed (call with out = NULL first)
+// formatQualityAndFilter: "<QUAL>\t<FILTER>" of a variant from its max_alt_allele_call_probability and total_count -> out (when it fits); returns the length or -1
+long long bth_quality_and_filter(float max_alt_allele_call_probability, unsigned total_count, char *out, unsigned long long out_len) {
+    try {
+        const std::string s = formatQualityAndFilter(max_alt_allele_call_probability, total_count);
+        if (out && out_len >= s.size()) std::memcpy(out, s.data(), s.size());
+        return (long long)s.size();
+    } catch (...) {
+        return -1;
+    }
+}
+
 long long bth_cluster_output_columns(unsigned S, unsigned H, unsigned V, const uint16_t *hap_allele, const uint16_t *var_num_alleles, const uint8_t *var_has_dependency,
                                      unsigned long long num_diplotypes, const uint16_t *h1, const uint16_t *h2, const uint32_t *freq, const double *stats,
                                      const uint8_t *ploidy, float min_gpp, float min_kmers, const float *min_fraction, char *out, unsigned long long out_len) {

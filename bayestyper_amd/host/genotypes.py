@@ -94,6 +94,20 @@ def cluster_output_columns(flat, res, c, ploidy, min_fraction, min_gpp=0.99, min
     return buf.raw[:n].decode().split("\n")[:-1]
 
 
+def quality_and_filter(max_alt_acp, total_count):
+    """formatQualityAndFilter: "<QUAL>\\t<FILTER>" as the host layer writes it for a variant with these two statistics"""
+    from . import dll
+
+    fn = dll.bth_quality_and_filter
+    fn.restype = C.c_longlong
+    fn.argtypes = [C.c_float, C.c_uint, C.c_char_p, C.c_ulonglong]
+    buf = C.create_string_buffer(64)
+    n = fn(float(max_alt_acp), int(total_count), buf, 64)
+    if n < 0 or n > 64:
+        raise RuntimeError("quality_and_filter failed")
+    return buf.raw[:n].decode()
+
+
 def batch_output_columns(flat, res, min_fraction, threads, min_gpp=0.99, min_kmers=1.0):
     """the genotype collection of a whole launch on `threads` host threads (bth_batch_output_columns: getGenotypes + the formatted columns of every
     variant of every cluster, as `bayesTyper genotype -p` does per launch); returns the number of bytes formatted"""

@@ -639,7 +639,63 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         for (auto &part : lines)
             for (auto &l : part) genotype_writer.append(*l.first, std::move(l.second));
     };
+    // The text route on top of it (BT_GENOTYPE_TEXT_ON_DEVICE=1, one process): the device formats the genotype-derived text of every line as well
+    // (bt_gibbs_genotype_text); the host adds ALT, QUAL / FILTER, the cluster annotations, ACO and FORMAT, and splices each GQ — derived here from the cell's
+    // best posterior — into its slot.  Same threads, same append order as emit_records.
+    const char *text_env = getenv("BT_GENOTYPE_TEXT_ON_DEVICE");
+    const bool text_asked = text_env && *text_env && std::strcmp(text_env, "0") != 0;
+    if (text_asked && comm && rank == 0) std::cout << "BT_GENOTYPE_TEXT_ON_DEVICE is ignored in a run of several ranks: rank 0 formats the gathered records" << std::endl;
+    auto emit_text = [&](const GibbsBatchData &b, const std::vector<uint8_t> &text, const std::vector<uint32_t> &index) {
+        StageScope stage("VCF lines from the device's text (-p host threads)");
+        if (index.size() < 4 || index[0] != b.numClusters() || index[2] != S || index.size() < 5 + (uint64_t)index[0] + (uint64_t)index[1] * (9 + 2 * S))
+            throw std::runtime_error("genotype text: the index does not cover the launch's clusters");
+        const uint32_t *cluster_var_off = index.data() + 4, *variants = cluster_var_off + index[0] + 1, *cells = variants + 9 * (uint64_t)index[1];
+        const char *bytes = reinterpret_cast<const char *>(text.data());
+        std::vector<std::vector<std::pair<const std::string *, GenotypeWriter::GenotypedVariant>>> lines(host_threads);
+        parallelFor(b.numGroups(), host_threads, [&](size_t g_begin, size_t g_end, unsigned part) {
+            auto &mine = lines[part];
+            std::string sample_columns;
+            for (uint32_t g = (uint32_t)g_begin; g < (uint32_t)g_end; g++) {
+                const ClusterGroup &grp = unit.variant_cluster_groups[b.group_index[g]];
+                for (uint32_t c = b.group_cluster_off[g]; c < b.group_cluster_off[g + 1]; c++) {
+                    const VariantCluster &cluster = grp.clusters[c - b.group_cluster_off[g]];
+                    const std::vector<VariantInfo> info = variantClusterInfo(cluster);
+                    if (cluster_var_off[c + 1] - cluster_var_off[c] != info.size()) throw std::runtime_error("genotype text: the index does not match the unit's clusters");
+                    const ClusterAnnotation annotation{cluster.chrom_name, (uint32_t)info.size(), variantClusterRegion(cluster.chrom_name, info), (uint32_t)grp.clusters.size(), grp.region(),
+                                                       b.num_haplotypes[c]};
+                    for (size_t v = 0; v < info.size(); v++) {
+                        const uint64_t gv = cluster_var_off[c] + v;
+                        const uint32_t *iv = variants + 9 * gv;
+                        const uint64_t off = (uint64_t)iv[0] | ((uint64_t)iv[1] << 32), n_stats = iv[2], n_cover = iv[3], n_samples = iv[4];
+                        if (iv[5] != info[v].numberOfAlleles()) throw std::runtime_error("genotype text: a variant with another number of alleles than its record");
+                        if (iv[8] || off + n_stats + n_cover + n_samples > text.size()) throw std::runtime_error("genotype text: a variant's text is not usable");
+                        const char *samples = bytes + off + n_stats + n_cover;
+                        sample_columns.clear();
+                        uint64_t at = 0;
+                        for (size_t s = 0; s < S; s++) {   // GQ into its slot
+                            const uint32_t *cell = cells + 2 * (gv * S + s);
+                            if (cell[1] == 0xFFFFFFFFu) continue;
+                            if (cell[1] < at || cell[1] > n_samples) throw std::runtime_error("genotype text: a GQ slot outside its samples piece");
+                            float best;
+                            std::memcpy(&best, &cell[0], 4);
+                            sample_columns.append(samples + at, cell[1] - at);
+                            sample_columns += std::to_string(genotypeQuality(best));
+                            at = cell[1];
+                        }
+                        sample_columns.append(samples + at, n_samples - at);
+                        float max_alt;
+                        std::memcpy(&max_alt, &iv[7], 4);
+                        mine.emplace_back(&cluster.chrom_name, genotype_writer.formatGenotypesFromText(annotation, info[v], formatQualityAndFilter(max_alt, iv[6]), bytes + off, n_stats,
+                                                                                                      bytes + off + n_stats, n_cover, sample_columns));
+                    }
+                }
+            }
+        });
+        for (auto &part : lines)
+            for (auto &l : part) genotype_writer.append(*l.first, std::move(l.second));
+    };
     if (!comm) {
+        if (genotypes_on_device && text_asked) inference_engine.setGenotypeTextCollector(emit_text);
         if (genotypes_on_device)
             inference_engine.setGenotypeCollector(filters.min_genotype_posterior, filters.min_number_of_kmers, filters.min_fraction_observed_kmers,
                                                   [&](const GibbsBatchData &b, const std::vector<uint32_t> &words) {

@@ -648,6 +648,11 @@ bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, v
 bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
+bt_genotype_text_sizes = _sig("bt_genotype_text_sizes", [vp, vp, C.c_uint64, u64p, u64p])
+bt_genotype_text = _sig("bt_genotype_text", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p])
+bt_gibbs_genotype_text = _sig("bt_gibbs_genotype_text", [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u32p])
+bt_diag_genotype_text = _sig("bt_diag_genotype_text", [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p])
+bt_diag_format_g6 = _sig("bt_diag_format_g6", [vp, C.c_uint64, vp, vp])
 bt_diag_genotype_cluster = _sig("bt_diag_genotype_cluster", [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p])
 bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
 
@@ -832,6 +837,72 @@ def diag_genotype_cluster(S, H, V, hap_allele, var_num_alleles, var_has_dependen
     return out
 
 
+def diag_format_g6(values):
+    """bt_diag_format_g6: the device's number formatter (printf's %g at precision 6) run on the host -> list of str, None where a value is not covered"""
+    v = np.ascontiguousarray(values, np.float64).reshape(-1)
+    text, lens = np.zeros(max(v.size, 1) * 16, np.uint8), np.zeros(max(v.size, 1), np.int32)
+    check(bt_diag_format_g6(_np_ptr(v) if v.size else None, v.size, _np_ptr(text), _np_ptr(lens)))
+    raw = text.tobytes()
+    return [None if lens[i] < 0 else raw[16 * i:16 * i + int(lens[i])].decode() for i in range(v.size)]
+
+
+def diag_genotype_text(words):
+    """bt_diag_genotype_text: the device's text passes run on the host over a record string -> (text bytes, index words, number of not-covered variants)"""
+    w = np.ascontiguousarray(words, np.uint32)
+    nt, ni, nc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    bt_diag_genotype_text(_np_ptr(w), w.size, None, 0, None, 0, C.byref(nt), C.byref(ni), C.byref(nc))   # (fails with "buffer too small" after setting the sizes)
+    text, index = np.zeros(max(nt.value, 1), np.uint8), np.zeros(max(ni.value, 1), np.uint32)
+    check(bt_diag_genotype_text(_np_ptr(w), w.size, _np_ptr(text), nt.value, _np_ptr(index), ni.value, C.byref(nt), C.byref(ni), C.byref(nc)))
+    return text[:nt.value], index[:ni.value], nc.value
+
+
+def genotype_text_sizes(ctx, d_words, num_words):
+    """bt_genotype_text_sizes of a record string in device memory -> (text bytes, index words)"""
+    nt, ni = C.c_uint64(), C.c_uint64()
+    check(bt_genotype_text_sizes(ctx.h, d_words, num_words, C.byref(nt), C.byref(ni)))
+    return nt.value, ni.value
+
+
+def genotype_text(ctx, d_words, num_words):
+    """bt_genotype_text over a record string in device memory (d_words: device pointer) -> (text bytes, index words, number of not-covered variants) on the host"""
+    nt, ni = genotype_text_sizes(ctx, d_words, num_words)
+    d_text, d_index = DeviceBuffer(ctx, nt), DeviceBuffer(ctx, ni * 4)
+    try:
+        t, i, nc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        check(bt_genotype_text(ctx.h, d_words, num_words, d_text.ptr, nt, d_index.ptr, ni, C.byref(t), C.byref(i), C.byref(nc)))
+        return d_text.download(np.uint8, t.value), d_index.download(np.uint32, i.value), nc.value
+    finally:
+        d_text.free()
+        d_index.free()
+
+
+def parse_genotype_text(text, index):
+    """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
+    dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer
+    does) spliced into its slot — and "A", "total_count", "max_alt_acp" (float32), "flags" (1 = not covered)"""
+    index = np.ascontiguousarray(index, np.uint32)
+    raw = np.ascontiguousarray(text, np.uint8).tobytes()
+    Cn, NV, S = int(index[0]), int(index[1]), int(index[2])
+    var = index[5 + Cn:5 + Cn + 9 * NV].reshape(NV, 9)
+    cells = index[5 + Cn + 9 * NV:5 + Cn + 9 * NV + 2 * NV * S].reshape(NV, S, 2)
+    out = []
+    for v in range(NV):
+        off = int(var[v, 0]) | (int(var[v, 1]) << 32)
+        n_stats, n_cover, n_samples = (int(x) for x in var[v, 2:5])
+        samples = raw[off + n_stats + n_cover:off + n_stats + n_cover + n_samples]
+        parts, at = [], 0
+        for s in range(S):
+            slot = int(cells[v, s, 1])
+            if slot == 0xFFFFFFFF:
+                continue
+            parts.append(samples[at:slot] + str(genotype_quality(cells[v, s, 0:1].view(np.float32)[0])).encode())
+            at = slot
+        parts.append(samples[at:])
+        out.append({"stats": raw[off:off + n_stats].decode(), "cover": raw[off + n_stats:off + n_stats + n_cover].decode(), "samples": b"".join(parts).decode(),
+                    "A": int(var[v, 5]), "total_count": int(var[v, 6]), "max_alt_acp": var[v, 7:8].view(np.float32)[0], "flags": int(var[v, 8])})
+    return out
+
+
 class Gibbs:
     """A batch of variant-cluster groups on one GPU (bt_gibbs_*).  `flat` is a dict as produced by bayestyper_amd.synth."""
 
@@ -977,6 +1048,20 @@ class Gibbs:
         out = np.zeros(n.value, np.uint32)
         check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), p, out.nbytes))
         return out
+
+    def genotype_text(self, min_gpp, min_kmers, min_fraction):
+        """bt_gibbs_genotype_text: the launch's genotype text formatted on the device -> (text bytes, index words, number of not-covered variants) on
+        the host (parse_genotype_text)"""
+        f, keep = _genotype_filters(min_gpp, min_kmers, min_fraction)
+        if len(keep) != self.S:
+            raise ValueError("one min_fraction_observed_kmers per sample")
+        pt, pi, nt, ni, nc = vp(), vp(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        check(bt_gibbs_genotype_text(self.h, C.addressof(f), C.byref(pt), C.byref(nt), C.byref(pi), C.byref(ni), C.byref(nc)))
+        text, index = np.zeros(nt.value, np.uint8), np.zeros(ni.value, np.uint32)
+        if text.size:
+            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(text), pt, text.nbytes))
+        check(bt_memcpy_d2h(self.ctx.h, _np_ptr(index), pi, index.nbytes))
+        return text, index, nc.value
 
     def close(self):
         if self.h:

@@ -642,6 +642,34 @@ typedef struct bt_genotype_filters {
     const float *min_fraction_observed_kmers;   /* [S] */
 } bt_genotype_filters;                           /* Filters.cpp:33-54 */
 int bt_gibbs_genotypes(bt_gibbs *g, const bt_genotype_filters *f, const uint32_t **d_words, uint64_t *num_words);
+/* The genotype-derived TEXT of the launch's VCF lines formatted ON THE DEVICE from a record string of bt_gibbs_genotypes: what GenotypeWriter formats on its
+ * threads (GenotypeWriter.cpp:84-143 the allele fields, :202-230 writeVariantStats / writeAlleleCover, :261-345 writeSamples / writeAlleleKmerStats), byte for
+ * byte as the host layer's stream insertions print it (bayestyper_amd/csrc/bt_genotype_text.hpp holds the formatter, shared by the kernels and the host).
+ * Text: for every variant, in the string's variant order and contiguous, three pieces:
+ *   stats    "AC=..;AF=..;AN=..;ACP=.."
+ *   cover    ";ANC=.." with ascending alleles, or nothing
+ *   samples  per sample "\tGT:" + a GQ slot of NO bytes + ":GPP:APP:NAK:FAK:MAC:SAF"; "\t:.:.:.:.:.:." for ploidy 0 (no slot)
+ * GQ and QUAL are not in the text, for the reason given above: the reader derives GQ from the cell's `best` and QUAL / FILTER from the variant's
+ * max_alt_allele_call_probability and total_count with its own log10, and splices GQ in at the slot.
+ * Index (32-bit words):
+ *   [0] C  [1] NV  [2] S  [3] number of not-covered variants     cluster_var_off [C+1]
+ *   per variant, 9 words:  [0] [1] byte offset of its text (low, high word)  [2] [3] [4] lengths of the stats / cover / samples piece  [5] A  [6] total_count
+ *                          [7] max_alt_allele_call_probability (f32)  [8] flags: 1 = not covered
+ *   per cell (v * S + s), 2 words:  [0] best (f32)  [1] byte offset of the GQ slot inside the samples piece (0xFFFFFFFF: none)
+ * Floats and doubles are printed exactly as printf's %g prints their value (precision 6, round half even) when 1e-27 <= |v| < 1e6 or v = 0.  Any other value
+ * (non-finite, subnormal, outside that range) is NOT COVERED: nothing is printed for it, its variant is flagged and counted, and the caller must take that
+ * variant's — in practice the launch's — text from the record string instead.  This is a condition, not a tolerance: the formatter never guesses.
+ * bt_genotype_text_sizes: the exact sizes for a record string in device memory.  bt_genotype_text: text and index into the caller's device buffers;
+ *   *text_bytes and *index_words are set first; a capacity that is too small is an error and nothing is written.  num_not_covered may be NULL.
+ *   Errors: a null argument; a string whose tables or records do not have bt_gibbs_genotypes' layout (checked before anything is read through them);
+ *   more than 2^32 index words.
+ * bt_gibbs_genotype_text: bt_gibbs_genotypes, then the same passes; text and index belong to the sampler (valid until the next call or bt_gibbs_destroy) and
+ *   are complete on return; the sampler's state is not touched; the errors are bt_gibbs_genotypes', with messages under this entry's name. */
+int bt_genotype_text_sizes(bt_ctx *ctx, const uint32_t *d_words, uint64_t num_words, uint64_t *text_bytes, uint64_t *index_words);
+int bt_genotype_text(bt_ctx *ctx, const uint32_t *d_words, uint64_t num_words, uint8_t *d_text, uint64_t text_capacity, uint32_t *d_index, uint64_t index_capacity,
+                     uint64_t *text_bytes, uint64_t *index_words, uint32_t *num_not_covered);
+int bt_gibbs_genotype_text(bt_gibbs *g, const bt_genotype_filters *f, const uint8_t **d_text, uint64_t *text_bytes, const uint32_t **d_index, uint64_t *index_words,
+                           uint32_t *num_not_covered);
 /* compact posterior summary on the DEVICE (input of the cross-GPU gather to rank 0): for cluster c, sample s
  * d_out[(c*S+s)*2] = h1 | h2<<16 of the most frequently sampled diplotype, d_out[(c*S+s)*2+1] = its frequency */
 int bt_gibbs_posterior_summary(bt_gibbs *g, uint32_t *d_out);
@@ -698,6 +726,13 @@ int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint6
 int bt_diag_genotype_cluster(uint32_t S, uint32_t H, uint32_t V, const uint16_t *hap_allele, const uint16_t *var_num_alleles, const uint8_t *var_has_dependency,
                              uint64_t num_diplotypes, const uint16_t *h1, const uint16_t *h2, const uint32_t *freq, const double *stats, const uint8_t *ploidy,
                              const bt_genotype_filters *f, uint32_t *h_words, uint64_t capacity, uint64_t *num_words);
+/* Host-side run of bt_genotype_text (the same __host__ __device__ code, no GPU) over a record string in host memory; the capacity rule is bt_genotype_text's
+ * (replaces GenotypeWriter.cpp:84-143,261-345 as that entry does). */
+int bt_diag_genotype_text(const uint32_t *h_words, uint64_t num_words, uint8_t *h_text, uint64_t text_capacity, uint32_t *h_index, uint64_t index_capacity, uint64_t *text_bytes,
+                          uint64_t *index_words, uint32_t *num_not_covered);
+/* The number formatter alone: h_text16 [n * 16] receives the text of value i at 16 * i (zero padded), h_len [n] its length, or -1 with no text when the value
+ * is not covered (operator<< of a double, i.e. printf's %g, in GenotypeWriter.cpp:130-143) */
+int bt_diag_format_g6(const double *h_values, uint64_t n, char *h_text16, int32_t *h_len);
 /* Host-side run of the container replay behind bt_paths_count_multigroup: n DISTINCT k-mers (2 x u64 each) are inserted, in the given
  * order, into an emulated libstdc++ std::unordered_set<std::bitset<2k>> that starts with `initial_buckets` buckets (1 = freshly
  * constructed; a set that was clear()ed keeps its bucket count); h_rank[i] = position of k-mer i in the set's iteration order,
