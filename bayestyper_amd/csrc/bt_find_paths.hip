@@ -22,6 +22,12 @@
 // search.  The teams differ in one place, filter_paths: a wavefront computes the scores of a greedy round over its lanes into
 // arrays of its scratch region and moves them with their paths, a single lane computes a candidate's scores when the scan reaches
 // it and has no such arrays.
+//
+// The samples depend on each other from addPathIndices on only.  One sample per call (bt_find_paths_sample) runs a cluster's whole routine,
+// find_paths_cluster, in one kernel.  n samples per call (bt_find_paths_samples) use its two halves: search_cluster (findSamplePaths, mergePaths,
+// filterPaths: graph, filter and seed in, final paths left in the scratch region) for every (sample, cluster) at once, sample j in scratch copy j
+// (find_paths_search_kernel / _search_wave_kernel), then fold_cluster (addPathIndices into the accumulated rows) by one team per cluster over copy 0 .. n-1
+// in that order (find_paths_fold_kernel / _fold_wave_kernel).  Search and fold are ordered by the stream.
 #include "bt_internal.hpp"
 
 #include <algorithm>
@@ -537,6 +543,138 @@ __device__ __forceinline__ void find_paths_cluster(const FindCluster &fc, uint32
     }
 }
 
+// ---- the two halves of find_paths_cluster as functions of their own, for the launches of several samples (bt_find_paths_samples).  They are COPIES: the
+// routine above is the text the per-sample kernels were measured with, and compiling those from the halves moved their register allocation and cost the
+// wave kernel 0.7 % (profiles/find_paths_samples.txt (c)).  A change to the search rules goes into both. ----
+
+// view of a cluster's scratch region at `base`
+template <class T>
+__device__ __forceinline__ Work open_work(const FindCluster &fc, const FindGraph &g, const BloomView &bloom, uint32_t k, uint32_t max_haps, uint32_t *base, uint32_t *overflow) {
+    const ScratchLayout l = scratch_layout(fc, max_haps, T::W > 1);
+    Work w;
+    w.slots = base + l.slots;
+    w.free_stack = base + l.free_stack;
+    w.vlist = base + l.vlist;
+    w.vcount = base + l.vcount;
+    w.cur = base + l.cur;
+    w.tmp = base + l.tmp;
+    w.covered = base + l.covered;
+    w.mt = base + l.mt;
+    if constexpr (T::W > 1) {
+        w.kscore = reinterpret_cast<double *>(base + l.kscore);
+        w.vscore = base + l.vscore;
+        w.plen = base + l.plen;
+    }
+    w.slot_words = fc.slot_words;
+    w.nv = fc.nv;
+    w.v0 = fc.v0;
+    w.k = k;
+    w.max_haps = max_haps;
+    w.g = g;
+    w.bloom = bloom;
+    w.overflow = overflow;
+    w.free_top = 0;
+    return w;
+}
+
+// SEARCH: findSamplePaths, mergePaths and filterPaths of one cluster by team T in the scratch region w.  It reads the graph, the sample's filter and the seed
+// only, and leaves the final paths where they are: cur[0 .. ncur) and their slots.  Returns ncur; max_cand: the most candidate paths a vertex had
+template <class T>
+__device__ __forceinline__ uint32_t search_cluster(Work &w, const FindCluster &fc, uint32_t seed, uint32_t &max_cand) {
+    const FindGraph &g = w.g;
+    const uint32_t max_haps = w.max_haps;
+    w.free_top = fc.cap_slots;
+    for (uint32_t i = T::lane(); i < fc.cap_slots; i += T::W) w.free_stack[i] = fc.cap_slots - 1u - i;
+    for (uint32_t i = T::lane(); i < fc.nv; i += T::W) w.vcount[i] = 0;
+    if (T::lane() == 0) mt_seed(w.mt, seed);
+    T::sync();
+    Mt rng = mt_open(w.mt);   // (lane 0 draws)
+    // ---- findSamplePaths (:389-472) ----
+    uint32_t ncur = 0;
+    max_cand = 0;
+    for (uint32_t vi = 0; vi < fc.nv; ++vi) {
+        ncur = 0;
+        const uint32_t e0 = g.in_off[fc.v0 + vi], e1 = g.in_off[fc.v0 + vi + 1];
+        if (e0 == e1) {
+            const uint32_t s = slot_alloc<T>(w);
+            for (uint32_t i = T::lane(); i < HDR_WORDS; i += T::W) slot(w, s)[i] = 0;
+            w.cur[ncur++] = s;
+        } else {
+            for (uint32_t e = e0; e < e1; ++e) {
+                const uint32_t src = g.in_src[e];
+                merge_paths<T>(w, ncur, w.vlist + (size_t)src * max_haps, T::uni(w.vcount[src]), fc.cur_cap);
+            }
+        }
+        T::sync();
+        if (T::lane() == 0) rng_shuffle_u32(rng, w.cur, ncur);
+        T::sync();
+        for (uint32_t i = T::lane(); i < ncur; i += T::W) add_vertex(w, slot(w, w.cur[i]), vi);
+        T::sync();
+        max_cand = max_cand > ncur ? max_cand : ncur;
+        filter_paths<T>(w, ncur, max_haps, false);
+        T::sync();
+        for (uint32_t i = T::lane(); i < ncur; i += T::W) w.vlist[(size_t)vi * max_haps + i] = w.cur[i];
+        w.vcount[vi] = ncur;
+        for (uint32_t e = e0; e < e1; ++e) {   // predecessors whose last successor this vertex is are no longer needed
+            const uint32_t src = g.in_src[e];
+            const uint32_t n = T::uni(w.vcount[src]);
+            if (g.last_use[fc.v0 + src] == vi && n) {
+                for (uint32_t i = 0; i < n; ++i) slot_free(w, T::uni(w.vlist[(size_t)src * max_haps + i]));
+                w.vcount[src] = 0;
+            }
+        }
+        T::sync();
+    }
+    if (T::lane() == 0) mt_close(rng);
+    max_cand = max_cand > ncur ? max_cand : ncur;
+    filter_paths<T>(w, ncur, max_haps, true);
+    T::sync();
+    return ncur;
+}
+
+// FOLD: addPathIndices (:726-798) of the final paths a search left in the scratch region w (cur[0 .. ncur), ncur <= cur_cap) into the cluster's accumulated
+// rows; best_count: the cluster's own counter.  The rows in order, a row's test against the final paths over lanes (the first unmarked match wins).  This is
+// the one part of a sample's search that depends on the samples before it
+template <class T>
+__device__ __forceinline__ void fold_cluster(Work &w, const FindCluster &fc, uint32_t ncur, uint8_t *best_rows, uint32_t *best_count) {
+    uint32_t *overflow = w.overflow;
+    uint8_t *rows = best_rows + fc.best;
+    uint32_t nrows = *best_count;
+    // redundant flags of the final paths live in the high bit of cur[]
+    for (uint32_t r = 0; r < nrows; ++r) {
+        uint8_t *row = rows + (size_t)r * fc.nv;
+        uint32_t nb = 0;
+        for (uint32_t b0 = 0; b0 < fc.nv; b0 += T::W) {   // tmp := the row's vertices, in order
+            const uint32_t vi = b0 + T::lane();
+            const bool set = vi < fc.nv && row[vi];
+            const unsigned long long mask = T::ballot(set);
+            if (set) w.tmp[nb + (uint32_t)__popcll(mask & ((1ull << T::lane()) - 1ull))] = vi;
+            nb += (uint32_t)__popcll(mask);
+        }
+        T::sync();
+        const uint32_t pi = first_redundant<T, true>(w, ncur, [&](uint32_t i) { const uint32_t s = w.cur[i]; return (s & 0x80000000u) ? 0xFFFFFFFFu : s; }, w.tmp, nb);
+        T::sync();
+        if (pi < ncur) {
+            const uint32_t s = T::uni(w.cur[pi]);
+            const uint32_t *p = slot(w, s);
+            if (nb < T::uni(p[0])) write_row<T>(row, fc.nv, p);
+            if (T::lane() == 0) w.cur[pi] = s | 0x80000000u;
+        }
+        T::sync();
+    }
+    for (uint32_t pi = 0; pi < ncur; ++pi) {
+        const uint32_t s = T::uni(w.cur[pi]);
+        if (s & 0x80000000u) continue;
+        if (nrows >= fc.best_cap) {
+            if (T::lane() == 0) atomicExch(overflow, 2u);
+            break;
+        }
+        write_row<T>(rows + (size_t)nrows * fc.nv, fc.nv, slot(w, s));
+        ++nrows;
+    }
+    if (T::lane() == 0) *best_count = nrows;
+}
+
 __global__ __launch_bounds__(64) void find_paths_kernel(const FindCluster *__restrict__ clusters, uint32_t C, FindGraph g, BloomView bloom, const uint32_t *__restrict__ seeds,
                                                         uint32_t k, uint32_t max_haps, uint32_t *__restrict__ scratch, uint8_t *__restrict__ best_rows,
                                                         uint32_t *__restrict__ best_count, uint32_t *__restrict__ overflow) {
@@ -552,6 +690,69 @@ __global__ __launch_bounds__(64) void find_paths_wave_kernel(const FindCluster *
     const uint32_t c = blockIdx.x;
     const FindCluster fc = clusters[c];
     find_paths_cluster<WaveTeam>(fc, seeds[c], g, bloom, k, max_haps, scratch, best_rows, best_count + c, overflow, max_candidates);
+}
+
+// ---- a batch of n samples (bt_find_paths_samples): every sample's search at once, then one fold per cluster over the samples in order ----
+// Sample j searches in its own copy of the scratch allocation: copy 0 is `scratch`, copy j > 0 lies at extra + (j - 1) * copy_words.
+__device__ __forceinline__ uint32_t *scratch_copy(uint32_t *scratch, uint32_t *extra, uint64_t copy_words, uint32_t j) {
+    return j == 0 ? scratch : extra + (uint64_t)(j - 1) * copy_words;
+}
+
+// one lane per (sample blockIdx.y, cluster); C: clusters of this launch, stride: clusters of the batch (seeds and ncur are [n * stride])
+__global__ __launch_bounds__(64) void find_paths_search_kernel(const FindCluster *__restrict__ clusters, uint32_t C, uint32_t stride, FindGraph g, const BloomView *__restrict__ blooms,
+                                                               const uint32_t *__restrict__ seeds, uint32_t k, uint32_t max_haps, uint32_t *__restrict__ scratch,
+                                                               uint32_t *__restrict__ extra, uint64_t copy_words, uint32_t *__restrict__ ncur_out, uint32_t *__restrict__ overflow) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y;
+    if (c >= C) return;
+    const FindCluster fc = clusters[c];
+    Work w = open_work<LaneTeam>(fc, g, blooms[j], k, max_haps, scratch_copy(scratch, extra, copy_words, j) + fc.scratch, overflow);
+    uint32_t max_cand = 0;
+    ncur_out[(size_t)j * stride + c] = search_cluster<LaneTeam>(w, fc, seeds[(size_t)j * stride + c], max_cand);
+}
+
+// one wavefront per (cluster blockIdx.x / n, sample blockIdx.x % n): the clusters are sorted by descending vertex count, so the longest searches of all samples start first
+__global__ __launch_bounds__(64) void find_paths_search_wave_kernel(const FindCluster *__restrict__ clusters, uint32_t n, uint32_t stride, FindGraph g, const BloomView *__restrict__ blooms,
+                                                                    const uint32_t *__restrict__ seeds, uint32_t k, uint32_t max_haps, uint32_t *__restrict__ scratch,
+                                                                    uint32_t *__restrict__ extra, uint64_t copy_words, uint32_t *__restrict__ ncur_out, uint32_t *__restrict__ overflow,
+                                                                    uint32_t *__restrict__ max_candidates) {
+    const uint32_t c = blockIdx.x / n, j = blockIdx.x % n;
+    const FindCluster fc = clusters[c];
+    Work w = open_work<WaveTeam>(fc, g, blooms[j], k, max_haps, scratch_copy(scratch, extra, copy_words, j) + fc.scratch, overflow);
+    uint32_t max_cand = 0;
+    const uint32_t ncur = search_cluster<WaveTeam>(w, fc, seeds[(size_t)j * stride + c], max_cand);
+    if (threadIdx.x == 0) {
+        ncur_out[(size_t)j * stride + c] = ncur;
+        atomicMax(max_candidates, max_cand);
+    }
+}
+
+// the fold of cluster c by team T: the final paths of copy 0, 1, .. n-1 in that order into the cluster's rows (the order of the samples is the order of the rows)
+template <class T>
+__device__ __forceinline__ void fold_samples(const FindCluster &fc, uint32_t n, uint32_t stride, const FindGraph &g, uint32_t k, uint32_t max_haps, uint32_t *scratch, uint32_t *extra,
+                                             uint64_t copy_words, const uint32_t *ncur_in, uint8_t *best_rows, uint32_t *best_count, uint32_t *overflow) {
+    for (uint32_t j = 0; j < n; ++j) {
+        Work w = open_work<T>(fc, g, BloomView{}, k, max_haps, scratch_copy(scratch, extra, copy_words, j) + fc.scratch, overflow);
+        const uint32_t ncur = T::uni(ncur_in[(size_t)j * stride]);
+        fold_cluster<T>(w, fc, ncur < fc.cur_cap ? ncur : fc.cur_cap, best_rows, best_count);
+        T::sync();   // (the next sample reads the rows and the count this one wrote)
+    }
+}
+
+__global__ __launch_bounds__(64) void find_paths_fold_kernel(const FindCluster *__restrict__ clusters, uint32_t C, uint32_t n, uint32_t stride, FindGraph g, uint32_t k, uint32_t max_haps,
+                                                             uint32_t *__restrict__ scratch, uint32_t *__restrict__ extra, uint64_t copy_words, const uint32_t *__restrict__ ncur_in,
+                                                             uint8_t *__restrict__ best_rows, uint32_t *__restrict__ best_count, uint32_t *__restrict__ overflow) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    const FindCluster fc = clusters[c];
+    fold_samples<LaneTeam>(fc, n, stride, g, k, max_haps, scratch, extra, copy_words, ncur_in + c, best_rows, best_count + c, overflow);
+}
+
+__global__ __launch_bounds__(64) void find_paths_fold_wave_kernel(const FindCluster *__restrict__ clusters, uint32_t n, uint32_t stride, FindGraph g, uint32_t k, uint32_t max_haps,
+                                                                  uint32_t *__restrict__ scratch, uint32_t *__restrict__ extra, uint64_t copy_words, const uint32_t *__restrict__ ncur_in,
+                                                                  uint8_t *__restrict__ best_rows, uint32_t *__restrict__ best_count, uint32_t *__restrict__ overflow) {
+    const uint32_t c = blockIdx.x;
+    const FindCluster fc = clusters[c];
+    fold_samples<WaveTeam>(fc, n, stride, g, k, max_haps, scratch, extra, copy_words, ncur_in + c, best_rows, best_count + c, overflow);
 }
 
 }  // namespace
@@ -575,7 +776,43 @@ struct bt_find_paths {
     std::vector<uint32_t> staged;        // seeds / counts in launch order
     uint32_t *d_max_candidates = nullptr;   // (second word of the overflow allocation)
     hipEvent_t ev_seeds = nullptr, ev_wave = nullptr;
+    // bt_find_paths_samples: what a batch of batch_cap samples needs beyond the above, one allocation (batch_layout), made on the first call with n >= 2 and
+    // replaced only by a call with a larger n
+    uint64_t scratch_words = 0;          // one copy of the scratch allocation
+    uint32_t batch_cap = 0, batch_max_n = 0;   // samples the allocation holds; largest n a call has had
+    uint8_t *d_batch = nullptr;
+    std::vector<uint32_t> staged_batch;  // seeds [n * C] in launch order
+    std::vector<BloomView> views;
 };
+
+// the batch allocation for n >= 2 samples: byte offsets of its parts (each a multiple of 256) and its size
+struct BatchLayout {
+    uint64_t extra, ncur, seeds, blooms, total;
+};
+static BatchLayout batch_layout(const bt_find_paths *f, uint32_t n) {
+    auto up256 = [](uint64_t x) { return (x + 255) & ~255ull; };
+    BatchLayout l{};
+    if (n < 2) return l;
+    l.extra = 0;
+    l.ncur = up256((uint64_t)(n - 1) * f->scratch_words * 4);
+    l.seeds = l.ncur + up256((uint64_t)n * f->C * 4);
+    l.blooms = l.seeds + up256((uint64_t)n * f->C * 4);
+    l.total = l.blooms + up256((uint64_t)n * sizeof(BloomView));
+    return l;
+}
+
+// the stream of the wide clusters' launches: the class stream when the context has one that PROVED concurrent with its own and there are lane clusters beside
+// them, else the context's stream
+static int wave_stream(bt_find_paths *f, uint32_t lanes, hipStream_t *out) {
+    *out = f->ctx->stream;
+    if (!lanes) return BT_OK;
+    int prio_lo = 0, prio_hi = 0;
+    BT_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    hipStream_t cs[1] = {nullptr};
+    BT_HIP(ctx_class_streams(f->ctx, 1, getenv("BT_GIBBS_NO_PRIO") ? prio_lo : prio_hi, cs));   // (the priority the samplers ask for: one probe per context)
+    if (f->ctx->class_streams_concurrent >= 1) *out = cs[0];
+    return BT_OK;
+}
 
 // best_count by cluster of the batch (the device keeps it in launch order)
 static hipError_t fetch_counts(bt_find_paths *f, uint32_t *out) {
@@ -654,6 +891,7 @@ int bt_find_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, uint3
         f->nv.push_back(nv);
     }
     f->best_bytes = best_bytes;
+    f->scratch_words = scratch_words;
     std::vector<FindCluster> launch_order;
     if (f->num_wave) {
         std::vector<uint32_t> wide;
@@ -711,6 +949,7 @@ int bt_find_paths_destroy(bt_find_paths *f) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
     for (void *q : f->owned) (void)hipFree(q);
+    if (f->d_batch) (void)hipFree(f->d_batch);
     if (f->ev_seeds) (void)hipEventDestroy(f->ev_seeds);
     if (f->ev_wave) (void)hipEventDestroy(f->ev_wave);
     delete f;
@@ -731,13 +970,7 @@ int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_
         // the wide clusters on a wavefront each, beside the lane kernel when the context has a stream that PROVED concurrent with its own, else before it
         const uint32_t lanes = f->C - f->num_wave;
         hipStream_t wave_st = st;
-        if (lanes) {
-            int prio_lo = 0, prio_hi = 0;
-            BT_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-            hipStream_t cs[1] = {nullptr};
-            BT_HIP(ctx_class_streams(f->ctx, 1, getenv("BT_GIBBS_NO_PRIO") ? prio_lo : prio_hi, cs));   // (the priority the samplers ask for: one probe per context)
-            if (f->ctx->class_streams_concurrent >= 1) wave_st = cs[0];
-        }
+        if (wave_stream(f, lanes, &wave_st) != BT_OK) return BT_ERR;
         for (uint32_t i = 0; i < f->C; ++i) f->staged[i] = h_seeds[f->order[i]];
         BT_HIP(hipMemcpyAsync(f->d_seeds, f->staged.data(), (size_t)f->C * 4, hipMemcpyHostToDevice, st));
         if (wave_st != st) {
@@ -762,6 +995,97 @@ int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_
     BT_HIP(hipStreamSynchronize(st));
     if (ov == 1) return fail("bt_find_paths_sample: path scratch exhausted (internal sizing error)");
     if (ov == 2) return fail("bt_find_paths_sample: more best paths than max_sample_haplotypes x num_samples");
+    return BT_OK;
+}
+
+int bt_find_paths_batch_bytes(bt_find_paths *f, uint32_t n, uint64_t *bytes) {
+    if (!f || !bytes) return fail("bt_find_paths_batch_bytes: null argument");
+    if (n == 0) return fail("bt_find_paths_batch_bytes: n must be positive");
+    *bytes = n <= f->batch_cap ? 0 : batch_layout(f, n).total - batch_layout(f, f->batch_cap).total;
+    return BT_OK;
+}
+
+int bt_find_paths_batch_info(bt_find_paths *f, uint32_t *largest_n, uint64_t *held_bytes) {
+    if (!f) return fail("bt_find_paths_batch_info: null argument");
+    if (largest_n) *largest_n = f->batch_max_n;
+    if (held_bytes) *held_bytes = batch_layout(f, f->batch_cap).total;
+    return BT_OK;
+}
+
+int bt_find_paths_samples(bt_find_paths *f, bt_bloom *const *sample_blooms, uint32_t n, const uint32_t *h_seeds) {
+    if (!f || !sample_blooms || !h_seeds) return fail("bt_find_paths_samples: null argument");
+    if (n == 0) return fail("bt_find_paths_samples: n must be positive");
+    if (n > 65535) return fail("bt_find_paths_samples: at most 65535 samples per call");
+    for (uint32_t j = 0; j < n; ++j) {
+        if (!sample_blooms[j]) return fail("bt_find_paths_samples: null filter in the array");
+        if (sample_blooms[j]->k != f->k) return fail("bt_find_paths_samples: k mismatch");
+        if (sample_blooms[j]->ctx && sample_blooms[j]->ctx->device != f->ctx->device) return fail("bt_find_paths_samples: a filter lives on another device");
+    }
+    f->batch_max_n = std::max(f->batch_max_n, n);
+    if (n == 1) return bt_find_paths_sample(f, sample_blooms[0], h_seeds);
+    BT_HIP(hipSetDevice(f->ctx->device));
+    hipStream_t st = f->ctx->stream;
+    const uint32_t C = f->C;
+    if (n > f->batch_cap) {   // (nothing of an earlier call is in flight: every call ends with a synchronize)
+        if (f->d_batch) BT_HIP(hipFree(f->d_batch));
+        f->d_batch = nullptr;
+        f->batch_cap = 0;
+        void *p = nullptr;
+        if (hipMalloc(&p, batch_layout(f, n).total) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("bt_find_paths_samples: device allocation of " + std::to_string(batch_layout(f, n).total) + " bytes for " + std::to_string(n) + " samples failed");
+        }
+        f->d_batch = static_cast<uint8_t *>(p);
+        f->batch_cap = n;
+    }
+    const BatchLayout l = batch_layout(f, f->batch_cap);
+    uint32_t *d_extra = reinterpret_cast<uint32_t *>(f->d_batch + l.extra), *d_ncur = reinterpret_cast<uint32_t *>(f->d_batch + l.ncur);
+    uint32_t *d_seeds = reinterpret_cast<uint32_t *>(f->d_batch + l.seeds);
+    BloomView *d_blooms = reinterpret_cast<BloomView *>(f->d_batch + l.blooms);
+    f->views.resize(n);
+    for (uint32_t j = 0; j < n; ++j) f->views[j] = sample_blooms[j]->view();
+    const uint32_t *seeds = h_seeds;
+    if (f->num_wave) {
+        f->staged_batch.resize((size_t)n * C);
+        for (uint32_t j = 0; j < n; ++j)
+            for (uint32_t i = 0; i < C; ++i) f->staged_batch[(size_t)j * C + i] = h_seeds[(size_t)j * C + f->order[i]];
+        seeds = f->staged_batch.data();
+    }
+    BT_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)n * C * 4, hipMemcpyHostToDevice, st));
+    BT_HIP(hipMemcpyAsync(d_blooms, f->views.data(), (size_t)n * sizeof(BloomView), hipMemcpyHostToDevice, st));
+    // the routes of bt_find_paths_sample: the wide clusters' search and fold in stream order on their stream, the others' on the context's, joined at the end
+    const uint32_t lanes = C - f->num_wave;
+    hipStream_t wave_st = st;
+    if (f->num_wave) {
+        if (wave_stream(f, lanes, &wave_st) != BT_OK) return BT_ERR;
+        if (wave_st != st) {
+            BT_HIP(hipEventRecord(f->ev_seeds, st));
+            BT_HIP(hipStreamWaitEvent(wave_st, f->ev_seeds, 0));
+        }
+        hipLaunchKernelGGL(find_paths_search_wave_kernel, dim3(f->num_wave * n), dim3(64), 0, wave_st, f->d_clusters + lanes, n, C, f->g, d_blooms, d_seeds + lanes, f->k, f->max_haps,
+                           f->d_scratch, d_extra, f->scratch_words, d_ncur + lanes, f->d_overflow, f->d_max_candidates);
+        BT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(find_paths_fold_wave_kernel, dim3(f->num_wave), dim3(64), 0, wave_st, f->d_clusters + lanes, n, C, f->g, f->k, f->max_haps, f->d_scratch, d_extra,
+                           f->scratch_words, d_ncur + lanes, f->d_best, f->d_best_count + lanes, f->d_overflow);
+        BT_CHECK_LAUNCH();
+    }
+    if (lanes) {
+        hipLaunchKernelGGL(find_paths_search_kernel, dim3((lanes + 63) / 64, n), dim3(64), 0, st, f->d_clusters, lanes, C, f->g, d_blooms, d_seeds, f->k, f->max_haps, f->d_scratch,
+                           d_extra, f->scratch_words, d_ncur, f->d_overflow);
+        BT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(find_paths_fold_kernel, dim3((lanes + 63) / 64), dim3(64), 0, st, f->d_clusters, lanes, n, C, f->g, f->k, f->max_haps, f->d_scratch, d_extra,
+                           f->scratch_words, d_ncur, f->d_best, f->d_best_count, f->d_overflow);
+        BT_CHECK_LAUNCH();
+    }
+    if (wave_st != st) {
+        BT_HIP(hipEventRecord(f->ev_wave, wave_st));
+        BT_HIP(hipStreamWaitEvent(st, f->ev_wave, 0));
+    }
+    uint32_t ov = 0;
+    BT_HIP(hipMemcpyAsync(&ov, f->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    BT_HIP(hipStreamSynchronize(st));
+    if (ov == 1) return fail("bt_find_paths_samples: path scratch exhausted (internal sizing error)");
+    if (ov == 2) return fail("bt_find_paths_samples: more best paths than max_sample_haplotypes x num_samples");
     return BT_OK;
 }
 

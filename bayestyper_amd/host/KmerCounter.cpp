@@ -4,7 +4,10 @@
 #include "StageTimes.hpp"
 #include "Parallel.hpp"
 
+#include <sys/stat.h>
+
 #include <algorithm>
+#include <cstdlib>
 #include <functional>
 #include <future>
 #include <iostream>
@@ -298,6 +301,39 @@ void KmerCounter::checkTable(bt_table *table, const char *stage) {
 
 // ---- cluster stage ----------------------------------------------------------------------------------------------------------------
 
+FindPathsBatchPlan planFindPathsBatches(const std::vector<uint64_t> &filter_bytes, const std::vector<uint64_t> &batch_bytes, uint64_t free_bytes, uint32_t N) {
+    FindPathsBatchPlan plan;
+    const size_t S = filter_bytes.size();
+    const uint32_t cap = (uint32_t)std::min<size_t>(std::max<uint32_t>(N, 1), std::max<size_t>(batch_bytes.size(), 1));
+    auto scratch_of = [&](uint32_t m) { return m <= batch_bytes.size() && m >= 1 ? batch_bytes[m - 1] : 0; };
+    std::vector<uint64_t> filters_of;   // per batch: bytes of its filters
+    for (size_t s = 0; s < S;) {
+        uint32_t n = 1;
+        uint64_t filters = filter_bytes[s];
+        while (n < cap && s + n < S) {
+            const uint64_t next = filters + filter_bytes[s + n];
+            if (next < filters || next > free_bytes || scratch_of(n + 1) > free_bytes - next) break;
+            filters = next;
+            n++;
+        }
+        plan.sizes.push_back(n);
+        filters_of.push_back(filters);
+        s += n;
+    }
+    // the scratch of the largest batch stays allocated from its first call on: both batches' filters have to fit beside it
+    uint32_t largest = 1;
+    for (uint32_t n : plan.sizes) largest = std::max(largest, n);
+    for (size_t b = 0; b < plan.sizes.size(); b++) {
+        bool fits = b + 1 < plan.sizes.size();
+        if (fits) {
+            const uint64_t both = filters_of[b] + filters_of[b + 1];
+            fits = both >= filters_of[b] && both <= free_bytes && scratch_of(largest) <= free_bytes - both;
+        }
+        plan.prefetch_next.push_back(fits ? 1 : 0);
+    }
+    return plan;
+}
+
 void KmerCounter::findVariantClusterPaths(InferenceUnit *unit, const UnitGraphs &ug, uint16_t max_sample_haplotypes) {
     std::cout << "[" << getLocalTime() << "] Finding variant cluster paths for " << samples.size() << " sample(s) ..." << std::endl;
     PathsBatchBuilder builder;
@@ -325,34 +361,100 @@ void KmerCounter::findVariantClusterPaths(InferenceUnit *unit, const UnitGraphs 
         };
         std::future<bt_bloom *> coming;
         double load_wait_s = 0, search_s = 0;
-        for (size_t s = 0; s < samples.size(); s++) {
-            const auto t0 = std::chrono::steady_clock::now();
-            BloomHandle sample_bloom;
-            sample_bloom.h = coming.valid() ? coming.get() : load(s, ctx);
-            if (prefetch && s + 1 < samples.size()) coming = std::async(std::launch::async, load, s + 1, loader_ctx.c);
-            const auto t1 = std::chrono::steady_clock::now();
-            // prng_seed + (group index + 1) * (sample index + 1) (KmerCounter.cpp:65) + variant_cluster_idx (VariantClusterGroup.cpp:142)
-            for (uint32_t c = 0; c < C; c++)
-                seeds[c] = prng_seed + (ug.cluster_group[c] + 1u) * (uint32_t)(s + 1) + unit->variant_cluster_groups[ug.cluster_group[c]].clusters[ug.cluster_vertex[c]].cluster_idx;
-            try {
-                check(bt_find_paths_sample(fp, sample_bloom.h, seeds.data()), "bt_find_paths_sample");
-                check(bt_sync(ctx), "bt_sync");
-            } catch (...) {
-                if (coming.valid()) {   // (the loader's filter must not outlive the contexts)
-                    try {
-                        BloomHandle drop;
-                        drop.h = coming.get();
-                    } catch (...) {
-                    }
-                }
-                throw;
+        // BT_FIND_PATHS_SAMPLES = N >= 2: up to N samples per bt_find_paths_samples call (planFindPathsBatches); unset, 0 or 1: the loop over the samples below
+        const uint32_t per_call = getenv("BT_FIND_PATHS_SAMPLES") ? (uint32_t)std::strtoul(getenv("BT_FIND_PATHS_SAMPLES"), nullptr, 10) : 0;
+        std::string batches_row;
+        if (per_call >= 2) {
+            const size_t S = samples.size();
+            std::vector<uint64_t> filter_bytes(S, 0), batch_bytes(std::min<size_t>(per_call, S), 0);
+            for (size_t s = 0; s < S; s++) {   // (the filter's words are the file's bytes; a missing file is bt_bloom_load's error)
+                struct stat sb;
+                if (stat((samples[s].file + ".bloomData").c_str(), &sb) == 0) filter_bytes[s] = (uint64_t)sb.st_size;
             }
-            const auto t2 = std::chrono::steady_clock::now();
-            load_wait_s += std::chrono::duration<double>(t1 - t0).count();
-            search_s += std::chrono::duration<double>(t2 - t1).count();
+            for (size_t m = 1; m <= batch_bytes.size(); m++) check(bt_find_paths_batch_bytes(fp, (uint32_t)m, &batch_bytes[m - 1]), "bt_find_paths_batch_bytes");
+            uint64_t free_bytes = 0;
+            check(bt_ctx_info(ctx, nullptr, nullptr, &free_bytes, nullptr, 0), "bt_ctx_info");
+            const FindPathsBatchPlan plan = planFindPathsBatches(filter_bytes, batch_bytes, free_bytes, per_call);
+            struct BloomSet {
+                std::vector<bt_bloom *> v;
+                BloomSet() = default;
+                BloomSet(BloomSet &&o) : v(std::move(o.v)) { o.v.clear(); }
+                BloomSet &operator=(BloomSet &&o) {
+                    std::swap(v, o.v);
+                    return *this;
+                }
+                ~BloomSet() {
+                    for (bt_bloom *h : v) bt_bloom_destroy(h);
+                }
+            };
+            auto load_batch = [&](size_t s0, uint32_t n, bt_ctx *on) {
+                BloomSet set;
+                for (uint32_t j = 0; j < n; j++) set.v.push_back(load(s0 + j, on));
+                return set;
+            };
+            std::future<BloomSet> coming_batch;
+            size_t s0 = 0;
+            for (size_t b = 0; b < plan.sizes.size(); b++) {
+                const uint32_t n = plan.sizes[b];
+                const auto t0 = std::chrono::steady_clock::now();
+                BloomSet blooms = coming_batch.valid() ? coming_batch.get() : load_batch(s0, n, ctx);
+                if (prefetch && plan.prefetch_next[b]) coming_batch = std::async(std::launch::async, load_batch, s0 + n, plan.sizes[b + 1], loader_ctx.c);
+                const auto t1 = std::chrono::steady_clock::now();
+                seeds.resize((size_t)n * C);
+                for (uint32_t j = 0; j < n; j++)
+                    for (uint32_t c = 0; c < C; c++)
+                        seeds[(size_t)j * C + c] = prng_seed + (ug.cluster_group[c] + 1u) * (uint32_t)(s0 + j + 1) +
+                                                   unit->variant_cluster_groups[ug.cluster_group[c]].clusters[ug.cluster_vertex[c]].cluster_idx;
+                try {
+                    check(bt_find_paths_samples(fp, blooms.v.data(), n, seeds.data()), "bt_find_paths_samples");
+                    check(bt_sync(ctx), "bt_sync");
+                } catch (...) {
+                    if (coming_batch.valid()) {   // (the loader's filters must not outlive the contexts)
+                        try {
+                            BloomSet drop = coming_batch.get();
+                        } catch (...) {
+                        }
+                    }
+                    throw;
+                }
+                const auto t2 = std::chrono::steady_clock::now();
+                load_wait_s += std::chrono::duration<double>(t1 - t0).count();
+                search_s += std::chrono::duration<double>(t2 - t1).count();
+                batches_row += (b ? " + " : "") + std::to_string(n);
+                s0 += n;
+            }
+            batches_row = "    of it: samples per launch " + batches_row + " (" + std::to_string(plan.sizes.size()) + " launch(es), BT_FIND_PATHS_SAMPLES=" + std::to_string(per_call) + ")";
+        } else {
+            for (size_t s = 0; s < samples.size(); s++) {
+                const auto t0 = std::chrono::steady_clock::now();
+                BloomHandle sample_bloom;
+                sample_bloom.h = coming.valid() ? coming.get() : load(s, ctx);
+                if (prefetch && s + 1 < samples.size()) coming = std::async(std::launch::async, load, s + 1, loader_ctx.c);
+                const auto t1 = std::chrono::steady_clock::now();
+                // prng_seed + (group index + 1) * (sample index + 1) (KmerCounter.cpp:65) + variant_cluster_idx (VariantClusterGroup.cpp:142)
+                for (uint32_t c = 0; c < C; c++)
+                    seeds[c] = prng_seed + (ug.cluster_group[c] + 1u) * (uint32_t)(s + 1) + unit->variant_cluster_groups[ug.cluster_group[c]].clusters[ug.cluster_vertex[c]].cluster_idx;
+                try {
+                    check(bt_find_paths_sample(fp, sample_bloom.h, seeds.data()), "bt_find_paths_sample");
+                    check(bt_sync(ctx), "bt_sync");
+                } catch (...) {
+                    if (coming.valid()) {   // (the loader's filter must not outlive the contexts)
+                        try {
+                            BloomHandle drop;
+                            drop.h = coming.get();
+                        } catch (...) {
+                        }
+                    }
+                    throw;
+                }
+                const auto t2 = std::chrono::steady_clock::now();
+                load_wait_s += std::chrono::duration<double>(t1 - t0).count();
+                search_s += std::chrono::duration<double>(t2 - t1).count();
+            }
         }
         StageTimes::get().add("  sample Bloom filters: load, or wait for the loader thread", load_wait_s);
         StageTimes::get().add("  best-path search of every sample (device)", search_s);
+        if (!batches_row.empty()) StageTimes::get().add(batches_row, search_s);
         bt_find_paths_stats routes{};
         check(bt_find_paths_info(fp, &routes), "bt_find_paths_info");
         if (routes.num_wave_clusters > 0)   // (its time is part of the line above: the wide clusters run beside the launch of the others)

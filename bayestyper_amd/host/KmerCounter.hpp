@@ -21,6 +21,16 @@ struct BloomHandle {
     bt_bloom *h = nullptr;
     ~BloomHandle() { bt_bloom_destroy(h); }
 };
+// How findVariantClusterPaths groups the samples when BT_FIND_PATHS_SAMPLES = N >= 2: consecutive batches, one bt_find_paths_samples call each.
+struct FindPathsBatchPlan {
+    std::vector<uint32_t> sizes;          // samples per batch, in sample order (their sum is the number of samples)
+    std::vector<uint8_t> prefetch_next;   // per batch: the next batch's filters fit beside this one's, so the loader thread may load them during the search
+};
+// filter_bytes: device bytes of every sample's filter; batch_bytes[m - 1]: bt_find_paths_batch_bytes for m samples, m = 1 .. at least min(N, samples);
+// free_bytes: free device memory (bt_ctx_info) before any filter is loaded.  A batch takes the next sample while it has fewer than N and its filters with the
+// next one and the scratch of the grown batch fit; a first filter that does not fit alone still makes a batch of one, which is the per-sample route.
+FindPathsBatchPlan planFindPathsBatches(const std::vector<uint64_t> &filter_bytes, const std::vector<uint64_t> &batch_bytes, uint64_t free_bytes, uint32_t N);
+
 struct TableHandle {
     bt_table *h = nullptr;
     ~TableHandle() { bt_table_destroy(h); }

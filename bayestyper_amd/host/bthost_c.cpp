@@ -53,6 +53,15 @@ int bth_parse_kmer_lines(const char *text, unsigned long long len, unsigned long
     }
 }
 
+// planFindPathsBatches (KmerCounter.hpp): how BT_FIND_PATHS_SAMPLES = N groups S samples.  sizes / prefetch_next: [S]; returns the number of batches
+unsigned bth_plan_find_paths_batches(const uint64_t *filter_bytes, unsigned S, const uint64_t *batch_bytes, unsigned num_batch_bytes, uint64_t free_bytes, unsigned N, uint32_t *sizes,
+                                     uint8_t *prefetch_next) {
+    const FindPathsBatchPlan plan = planFindPathsBatches(std::vector<uint64_t>(filter_bytes, filter_bytes + S), std::vector<uint64_t>(batch_bytes, batch_bytes + num_batch_bytes), free_bytes, N);
+    std::copy(plan.sizes.begin(), plan.sizes.end(), sizes);
+    std::copy(plan.prefetch_next.begin(), plan.prefetch_next.end(), prefetch_next);
+    return (unsigned)plan.sizes.size();
+}
+
 // tableCheckpointManifest (TableCheckpoint.hpp) of inputs given as plain arrays; names are tab-separated.  Returns the length of the text (copied to out when it fits).
 unsigned long long bth_table_checkpoint_manifest(unsigned k, unsigned S, const char *sample_names, const uint8_t *present, const uint64_t *total_kmers, const uint64_t *suf_bytes,
                                                  const uint32_t *counter_size, const uint32_t *min_count, const uint64_t *max_count, unsigned F, const char *file_names,

@@ -161,3 +161,17 @@ class GenotypeWriter:
         if self.h:
             dll.bth_writer_free(self.h)
             self.h = None
+
+
+dll.bth_plan_find_paths_batches.restype = C.c_uint
+dll.bth_plan_find_paths_batches.argtypes = [vp, C.c_uint, vp, C.c_uint, C.c_uint64, C.c_uint, vp, vp]
+
+
+def plan_find_paths_batches(filter_bytes, batch_bytes, free_bytes, n):
+    """planFindPathsBatches (KmerCounter.hpp): how BT_FIND_PATHS_SAMPLES = n groups the samples.  filter_bytes: device bytes of every sample's filter;
+    batch_bytes[m - 1]: bt_find_paths_batch_bytes for m samples -> (samples per batch, per batch whether the next batch's filters may load during its search)"""
+    fb = np.ascontiguousarray(filter_bytes, np.uint64)
+    bb = np.ascontiguousarray(batch_bytes, np.uint64)
+    sizes, pre = np.zeros(max(len(fb), 1), np.uint32), np.zeros(max(len(fb), 1), np.uint8)
+    nb = dll.bth_plan_find_paths_batches(fb.ctypes.data, len(fb), bb.ctypes.data, len(bb), int(free_bytes), int(n), sizes.ctypes.data, pre.ctypes.data)
+    return [int(x) for x in sizes[:nb]], [bool(x) for x in pre[:nb]]

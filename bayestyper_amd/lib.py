@@ -75,6 +75,9 @@ bt_table_file_info = _sig("bt_table_file_info", [C.c_char_p, u32p, u32p, u64p, C
 bt_find_paths_create = _sig("bt_find_paths_create", [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)])
 bt_find_paths_destroy = _sig("bt_find_paths_destroy", [vp])
 bt_find_paths_sample = _sig("bt_find_paths_sample", [vp, vp, vp])
+bt_find_paths_samples = _sig("bt_find_paths_samples", [vp, C.POINTER(vp), C.c_uint32, vp])
+bt_find_paths_batch_bytes = _sig("bt_find_paths_batch_bytes", [vp, C.c_uint32, u64p])
+bt_find_paths_batch_info = _sig("bt_find_paths_batch_info", [vp, C.POINTER(C.c_uint32), u64p])
 bt_find_paths_sizes = _sig("bt_find_paths_sizes", [vp, vp, u64p])
 bt_find_paths_fetch = _sig("bt_find_paths_fetch", [vp, vp])
 bt_find_paths_info = _sig("bt_find_paths_info", [vp, vp])
@@ -520,6 +523,27 @@ class FindPaths:
     def sample(self, bloom, seeds):
         sd = np.ascontiguousarray(seeds, np.uint32)
         check(bt_find_paths_sample(self.h, bloom.h, _np_ptr(sd)))
+
+    def samples(self, blooms, seeds):
+        """several samples in one call (bt_find_paths_samples): equal to sample() per entry, in order; seeds [n, C], a None entry is passed as a null filter"""
+        n = len(blooms)
+        sd = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        if sd.size != n * self.C:
+            raise ValueError("seeds must hold n x num_clusters values")
+        hs = (vp * max(n, 1))(*[None if b is None else b.h for b in blooms])
+        check(bt_find_paths_samples(self.h, hs, n, _np_ptr(sd)))
+
+    def batch_bytes(self, n):
+        """device bytes samples() with n filters would allocate beyond what the object holds"""
+        out = C.c_uint64()
+        check(bt_find_paths_batch_bytes(self.h, n, C.byref(out)))
+        return out.value
+
+    def batch_info(self):
+        """(largest n a samples() call had, device bytes held for batches)"""
+        n, b = C.c_uint32(), C.c_uint64()
+        check(bt_find_paths_batch_info(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
 
     def best_paths(self):
         n = np.zeros(self.C, np.uint32)

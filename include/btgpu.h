@@ -424,6 +424,18 @@ int bt_find_paths_destroy(bt_find_paths *f);
  * prng_seed + (group_idx + 1) * (sample_idx + 1) + variant_cluster_idx (KmerCounter.cpp:65, VariantClusterGroup.cpp:142) — followed
  * by addPathIndices into the accumulated best paths */
 int bt_find_paths_sample(bt_find_paths *f, bt_bloom *sample_bloom, const uint32_t *h_seeds);
+/* n samples in one call, defined as exactly n calls of bt_find_paths_sample in array order (the loop of KmerCounter::findVariantClusterPaths,
+ * src/bayesTyper/KmerCounter.cpp:59-103, over VariantClusterGraph.cpp:389-798): same rows, same counts, same error codes.  h_seeds: [n * C], sample-major, the
+ * clusters in batch order.  findSamplePaths, mergePaths and filterPaths of every (sample, cluster) run at once, each sample in a scratch copy of its own;
+ * addPathIndices then folds the samples' final paths into the rows per cluster, sample 0 first.  Errors: a null argument, a null entry, n == 0, a filter of
+ * another k or on another device.  n == 1 is bt_find_paths_sample itself and allocates nothing; for n >= 2 the extra scratch copies and the per-(sample,
+ * cluster) words are allocated on first need, kept, and replaced only by a call with a larger n (an allocation that fails is an error, the object stays usable). */
+int bt_find_paths_samples(bt_find_paths *f, bt_bloom *const *sample_blooms, uint32_t n, const uint32_t *h_seeds);
+/* device bytes a bt_find_paths_samples call with n samples would allocate beyond what the object already holds (0 for n == 1); no GPU call */
+int bt_find_paths_batch_bytes(bt_find_paths *f, uint32_t n, uint64_t *bytes);
+/* largest n a bt_find_paths_samples call had so far (0: none) and the device bytes held for batches; either pointer may be NULL (KmerCounter.cpp:59-103 has
+ * no counterpart: the reference searches one sample at a time) */
+int bt_find_paths_batch_info(bt_find_paths *f, uint32_t *largest_n, uint64_t *held_bytes);
 /* best_paths_indices so far: h_num_paths[c] rows of |V_c| bytes each, clusters concatenated (bt_paths_batch::path_vertices layout) */
 int bt_find_paths_sizes(bt_find_paths *f, uint32_t *h_num_paths, uint64_t *h_total_bytes);
 int bt_find_paths_fetch(bt_find_paths *f, uint8_t *h_path_vertices);

@@ -1,15 +1,20 @@
-"""bt_find_paths_sample on a batch with wide clusters: the lane kernel alone against wide clusters on a wavefront each (DESIGN.md §7.5,
-profiles/find_paths_wide.txt).
+"""bt_find_paths_sample on a batch with wide clusters: the lane kernel alone against wide clusters on a wavefront each, and several samples per call
+(bt_find_paths_samples) against one call per sample (profiles/find_paths_wide.txt, profiles/find_paths_samples.txt).
 
   find_paths_wide.py prepare --cache DIR [--small 50000] [--wide 150,400,1000]
       generate the parts (CPU only): DIR/small.npz — clusters of 1-3 variants — and DIR/wide_<variants>.npz, one cluster each
       (synth_graphs.random_cluster, 6 sampled haplotypes, in-degree <= 3)
   find_paths_wide.py run --cache DIR [--tree CHECKOUT] [--wide 150,400] [--wave-min T[,T...]] [--runs 3] [--limit-s 20] [--label TEXT]
+                         [--repeat R] [--samples S [--batched]]
       one JSON line per (batch, threshold): the batch = small + the named wide clusters (none: the lane-only batch), one sample, fpr 0.05,
       max_sample_haplotypes 32; `runs` timed bt_find_paths_sample calls on a fresh object each (the first call of the process is a warm-up on the
       lane-only batch), their median.  --tree: import bayestyper_amd from another built checkout (the parent commit's); a build without
       BT_FIND_PATHS_WAVE_MIN ignores --wave-min.  --limit-s: a batch whose first call took longer is not repeated and ends the run (the sizes after it
       are reported as left out).
+      --repeat R: the small clusters R times over (the lane-only batch long enough to time).  --samples S: S samples with a filter of their own each (the
+      same k-mers in filters of different sizes, so their false positives differ) and a seed row each; a timed call is then the S searches of one object:
+      S bt_find_paths_sample calls, or with --batched one bt_find_paths_samples call (profiles/find_paths_samples.txt).  --check-rows counts the rows
+      after the last sample: the two routes must agree.
 Every GPU step of a measurement session is one process of this tool under its own `timeout`, chained with &&; nothing is retried."""
 import argparse
 import json
@@ -71,21 +76,29 @@ def run(args):
 
     ctx = lib.Ctx(0)
     small = load(os.path.join(args.cache, "small.npz"))
+    if args.repeat > 1:
+        small = concat([small] * args.repeat)
     wides = [load(os.path.join(args.cache, f"wide_{n}.npz")) for n in args.wide]
     whole = concat([small] + wides)
     # the sample's filter: the k-mers of the sampled haplotypes (the batch's path rows) of every cluster, wide ones included
     gp = lib.Paths(ctx, whole, K)
-    bloom = lib.Bloom.create(ctx, gp.num_windows + 1000, FPR, K, threaded=True)
-    gp.count_kmers(bloom)
+    blooms = []
+    for s in range(args.samples):
+        blooms.append(lib.Bloom.create(ctx, gp.num_windows + 1000 * (s + 1), FPR, K, threaded=True))
+        gp.count_kmers(blooms[-1])
     gp.close()
     ctx.sync()
 
     def once(flat):
-        gf = lib.FindPaths(ctx, flat, K, MAX_HAPS, 1)
-        seeds = np.arange(flat["num_clusters"], dtype=np.uint32) + 7
+        gf = lib.FindPaths(ctx, flat, K, MAX_HAPS, args.samples)
+        seeds = np.stack([np.arange(flat["num_clusters"], dtype=np.uint32) + np.uint32(7 + 1000003 * s) for s in range(args.samples)])
         ctx.sync()
         t = time.perf_counter()
-        gf.sample(bloom, seeds)
+        if args.batched:
+            gf.samples(blooms, seeds)
+        else:
+            for s in range(args.samples):
+                gf.sample(blooms[s], seeds[s])
         ctx.sync()
         dt = time.perf_counter() - t
         st = gf.info() if hasattr(gf, "info") else None
@@ -115,6 +128,8 @@ def run(args):
                    "seconds": [round(x, 4) for x in times], "median_s": round(float(np.median(times)), 4)}
             if st is not None:
                 rec.update(num_wave_clusters=st.num_wave_clusters, wave_min=st.wave_min_vertices, max_candidate_paths=st.max_candidate_paths)
+            if args.samples > 1 or args.batched:
+                rec.update(samples=args.samples, batched=bool(args.batched))
             if rows is not None:
                 rec["best_rows"] = rows
             print(json.dumps(rec), flush=True)
@@ -137,6 +152,9 @@ def main():
     ap.add_argument("--limit-s", type=float, default=20.0)
     ap.add_argument("--label", default="")
     ap.add_argument("--check-rows", action="store_true")
+    ap.add_argument("--repeat", type=int, default=1, help="the small clusters this many times over")
+    ap.add_argument("--samples", type=int, default=1, help="samples searched per timed call, a filter each")
+    ap.add_argument("--batched", action="store_true", help="one bt_find_paths_samples call instead of one bt_find_paths_sample call per sample")
     args = ap.parse_args()
     prepare(args) if args.mode == "prepare" else run(args)
 
