@@ -13,6 +13,7 @@
 // Integer / byte work, HBM random access; no MFMA.
 #include "bt_internal.hpp"
 
+#include <cerrno>
 #include <cstring>
 
 #include <algorithm>
@@ -330,11 +331,11 @@ __host__ __device__ inline void replay_kmer_set(uint32_t n, uint64_t b_init, uns
 __global__ __launch_bounds__(BLOCK) void mg_order_kernel(const uint64_t *__restrict__ kmers, const uint32_t *__restrict__ seq_pos, const uint32_t *__restrict__ goff,
                                                           const uint64_t *__restrict__ moff, const uint64_t *__restrict__ b_init, uint32_t *__restrict__ next,
                                                           uint32_t *__restrict__ map_key, uint32_t *__restrict__ map_val, uint32_t *__restrict__ time_of_seq, uint32_t G,
-                                                          unsigned k) {
+                                                          unsigned k, uint32_t wide_min) {
     const uint32_t g = blockIdx.x * BLOCK + threadIdx.x;
     if (g >= G) return;
     const uint32_t i0 = goff[g], n = goff[g + 1] - i0;
-    if (n == 0) return;
+    if (n == 0 || (wide_min && n >= wide_min)) return;   // a group of at least wide_min k-mers is mg_order_wide_kernel's (0: none is)
 #ifdef BT_MG_INSERTION_ORDER   // (test of the tests: with insertion order instead of the container's order the parity test must fail)
     for (uint32_t p = 0; p < n; ++p) time_of_seq[i0 + p] = i0 + p + 1u;
     return;
@@ -347,6 +348,253 @@ __global__ __launch_bounds__(BLOCK) void mg_order_kernel(const uint64_t *__restr
             hi = kmers[2 * pos + 1];
         },
         [&](uint32_t node, uint32_t rank) { time_of_seq[i0 + node] = i0 + rank + 1u; });   // times start at 1: 0 = "set by an earlier unit"
+}
+// ---- the same order without the insert-by-insert replay: stage by stage ----
+// The container's rules (replay_kmer_set) are uniform enough for a closed form.  Cut a group's inserts into STAGES: a stage ends where a
+// rehash happens, so a stage has one bucket count B.  Let seq be the stage's input — the list the previous stage left, front to back,
+// followed by the nodes inserted during the stage in insertion order —, t(x) a node's position in seq, b(x) = hash(x) % B and
+// first(b) = min t over the nodes of bucket b.  A node that enters an empty bucket goes to the front of the whole list, so buckets lie
+// in the list by DESCENDING first; a node that enters a non-empty bucket goes to the front of that bucket, so a bucket's nodes lie by
+// DESCENDING t; a rehash walks the old list front to back under the same two rules, which is why the old list is the head of seq.
+// The list at the end of the stage is seq sorted by (first(b(x)) descending, t(x) descending); the last stage's list is the iteration
+// order.  Every stage is data-parallel: nothing in it waits for another lane, and no result depends on the order atomics land in.
+struct MgStage {
+    uint64_t buckets;      // bucket count during the stage
+    uint32_t begin, end;   // the stage inserts nodes [begin, end); the list held the nodes [0, begin) when it began
+};
+constexpr uint32_t MG_MAX_STAGES = 33;   // the prime chain of std_next_bucket_count has 31 entries
+constexpr uint32_t MG_ERR_PROBE = 1, MG_ERR_CHAIN = 2, MG_ERR_PLACE = 4, MG_ERR_STAGES = 8;
+__host__ __device__ inline MgStage mg_stage_start(uint64_t b_init) { return MgStage{b_init, 0, 0}; }
+// The stage after `st` of a group of n nodes, from rehash to rehash: false when st was the last one (st.buckets is then the container's
+// final bucket count).  replay_kmer_set's test before insert e is "e + 1 > next_resize", with next_resize = B once B > 1 and 0 for a
+// fresh set; it then rehashes iff max(e + 1, 11 for a fresh set) >= B, which that test implies for every B >= 1.  So a fresh set goes
+// to 13 buckets before its first insert, any other set rehashes exactly before insert e = B, and a stage ends at min(n, B).
+__host__ __device__ inline bool mg_stage_next(uint32_t n, MgStage &st) {
+    if (st.end >= n) return false;
+    const uint64_t next_resize = st.buckets > 1 ? st.buckets : 0;
+    st.begin = st.end;
+    if ((uint64_t)st.begin + 1 > next_resize) st.buckets = std_next_bucket_count(st.buckets);
+    st.end = st.buckets < n ? (uint32_t)st.buckets : n;
+    return true;
+}
+
+// who orders one group: a single thread (a lane's worth of work on the host, bt_diag_kmer_set_order_staged) or a workgroup
+struct SoloTeam {   // every atomic is the plain operation
+    static constexpr uint32_t W = 1;
+    __host__ __device__ static uint32_t lane() { return 0; }
+    __host__ __device__ static void sync() {}
+    __host__ __device__ static uint32_t load(const uint32_t *p) { return *p; }
+    __host__ __device__ static uint32_t cas(uint32_t *p, uint32_t expected, uint32_t v) {
+        const uint32_t old = *p;
+        if (old == expected) *p = v;
+        return old;
+    }
+    __host__ __device__ static void min(uint32_t *p, uint32_t v) {
+        if (v < *p) *p = v;
+    }
+    __host__ __device__ static uint32_t exch(uint32_t *p, uint32_t v) {
+        const uint32_t old = *p;
+        *p = v;
+        return old;
+    }
+    __host__ __device__ static void inc(uint32_t *p) { ++*p; }
+    __host__ __device__ static uint32_t scan_excl(uint32_t v, uint32_t &total) {
+        total = v;
+        return 0;
+    }
+};
+struct BlockTeam {   // the BLOCK threads of a workgroup
+    static constexpr uint32_t W = BLOCK;
+    __device__ static uint32_t lane() { return threadIdx.x; }
+    __device__ static void sync() { __syncthreads(); }
+    __device__ static uint32_t load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // a word other lanes CAS meanwhile
+    __device__ static uint32_t cas(uint32_t *p, uint32_t expected, uint32_t v) { return atomicCAS(p, expected, v); }
+    __device__ static void min(uint32_t *p, uint32_t v) { atomicMin(p, v); }
+    __device__ static uint32_t exch(uint32_t *p, uint32_t v) { return atomicExch(p, v); }
+    __device__ static void inc(uint32_t *p) { atomicAdd(p, 1u); }
+    // exclusive prefix sum of v over the team in lane order, total = the team's sum; every lane calls it
+    __device__ static uint32_t scan_excl(uint32_t v, uint32_t &total) {
+        __shared__ uint32_t wave_sum[BLOCK / 64];
+        const uint32_t l = threadIdx.x & 63u, w = threadIdx.x >> 6;
+        uint32_t inc = v;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d, 64);
+            if (l >= d) inc += o;
+        }
+        __syncthreads();   // (the previous call's reads of wave_sum are over)
+        if (l == 63) wave_sum[w] = inc;
+        __syncthreads();
+        uint32_t base = 0;
+        total = 0;
+        for (uint32_t i = 0; i < BLOCK / 64; ++i) {
+            if (i < w) base += wave_sum[i];
+            total += wave_sum[i];
+        }
+        return base + inc - v;
+    }
+};
+
+// one group's work area of the staged order: word offsets of its arrays from the area's start, and its size
+struct MgLayout {
+    uint64_t seq_a, seq_b;   // n each: the list before and after a stage (node numbers, front to back)
+    uint64_t slot_of;        // n: map slot of the node at position t
+    uint64_t chain;          // n: next position on the bucket's chain
+    uint64_t hist;           // n: at first(b) the size of bucket b, then (after the scan) where bucket b starts in the new list
+    uint64_t map_key, map_first, map_head, map_count;   // map_cap each: bucket number, its first(b), its chain's head, its size
+    uint64_t map_cap;        // a power of two >= 2 n
+    uint64_t total;          // a multiple of four words
+};
+__host__ __device__ inline MgLayout mg_layout(uint32_t n) {
+    MgLayout l{};
+    l.map_cap = 16;
+    while (l.map_cap < 2ull * n) l.map_cap <<= 1;
+    uint64_t o = 0;
+    l.seq_a = o, o += n;
+    l.seq_b = o, o += n;
+    l.slot_of = o, o += n;
+    l.chain = o, o += n;
+    l.hist = o, o += n;
+    l.map_key = o, o += l.map_cap;
+    l.map_first = o, o += l.map_cap;
+    l.map_head = o, o += l.map_cap;
+    l.map_count = o, o += l.map_cap;
+    l.total = (o + 3) & ~3ull;
+    return l;
+}
+
+// One stage of a group of n nodes: `cur` holds the list the previous stage left in [0, st.begin); `nxt` receives the list after the
+// stage, [0, st.end).  Returns the lane's MG_ERR_* bits (0: none).  Every lane of the team runs every sync(), and every loop is bounded by
+// the stage's node count or its map size: a bound that does not hold is reported, never waited for.
+template <typename T, typename KeyFn>
+__host__ __device__ inline uint32_t mg_stage_order(uint32_t n, const MgStage &st, unsigned k, uint32_t *area, const MgLayout &l, uint32_t *cur, uint32_t *nxt, KeyFn key) {
+    uint32_t *slot_of = area + l.slot_of, *chain = area + l.chain, *hist = area + l.hist;
+    uint32_t *mkey = area + l.map_key, *mfirst = area + l.map_first, *mhead = area + l.map_head, *mcount = area + l.map_count;
+    const uint32_t m = st.end, lane = T::lane();
+    uint64_t cap = 16;   // the stage's part of the map: room for twice its nodes (<= l.map_cap, as m <= n)
+    while (cap < 2ull * m) cap <<= 1;
+    if (m > n || cap > l.map_cap || cap > (1ull << 31)) return MG_ERR_PLACE;   // (the same for every lane)
+    const uint32_t mcap = (uint32_t)cap, mmask = mcap - 1u;
+    uint32_t err = 0;
+    // 0. empty map and histogram; the stage's own nodes behind the inherited list (node e sits at position e: the list holds nodes 0..begin-1)
+    for (uint32_t i = lane; i < mcap; i += T::W) {
+        mkey[i] = SQ_NONE;
+        mfirst[i] = SQ_NONE;
+        mhead[i] = SQ_NONE;
+        mcount[i] = 0;
+    }
+    for (uint32_t t = lane; t < m; t += T::W) {
+        hist[t] = 0;
+        if (t >= st.begin) cur[t] = t;
+    }
+    T::sync();
+    // 1. every node finds (or makes) its bucket's slot, lowers first(b) to its position and pushes itself on the bucket's chain
+    for (uint32_t t = lane; t < m; t += T::W) {
+        uint64_t lo = 0, hi = 0;
+        const uint32_t node = cur[t];
+        if (node < n) key(node, lo, hi);
+        const uint32_t b = (uint32_t)(std_hash_bitset(lo, hi, k) % st.buckets);
+        uint32_t i = (b * 2654435761u) & mmask, sl = SQ_NONE;
+        for (uint32_t probes = 0; probes < mcap && node < n; ++probes) {   // (node >= n: a place an earlier stage reported and left unwritten)
+            uint32_t have = T::load(&mkey[i]);
+            if (have == SQ_NONE) have = T::cas(&mkey[i], SQ_NONE, b);
+            if (have == SQ_NONE || have == b) {
+                sl = i;
+                break;
+            }
+            i = (i + 1) & mmask;
+        }
+        slot_of[t] = sl;
+        if (sl == SQ_NONE) {
+            err |= MG_ERR_PROBE;
+            continue;
+        }
+        T::min(&mfirst[sl], t);
+        chain[t] = T::exch(&mhead[sl], t);
+        T::inc(&mcount[sl]);
+    }
+    T::sync();
+    // 2. the size of every bucket, at its first position
+    for (uint32_t i = lane; i < mcap; i += T::W)
+        if (T::load(&mkey[i]) != SQ_NONE) {   // (words the lanes wrote with atomics are read the same way)
+            const uint32_t first = T::load(&mfirst[i]);
+            if (first < m) hist[first] = T::load(&mcount[i]);
+            else err |= MG_ERR_PLACE;
+        }
+    T::sync();
+    // 3. buckets lie by descending first: a bucket starts behind all buckets with a larger first (exclusive scan from the high end, four entries per lane and round)
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < m; base += 4 * T::W) {
+        uint32_t v[4], sum = 0;
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t idx = base + 4 * lane + j;
+            v[j] = idx < m ? hist[m - 1 - idx] : 0;
+            sum += v[j];
+        }
+        uint32_t total;
+        uint32_t at = carry + T::scan_excl(sum, total);
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t idx = base + 4 * lane + j;
+            if (idx < m) hist[m - 1 - idx] = at;
+            at += v[j];
+        }
+        carry += total;
+    }
+    T::sync();
+    // 4. a node's place: its bucket's start + the nodes of its chain with a larger t (the chain is in the order the pushes landed in: walk all of it)
+    for (uint32_t t = lane; t < m; t += T::W) {
+        const uint32_t sl = slot_of[t];
+        if (sl == SQ_NONE) continue;
+        const uint32_t size = T::load(&mcount[sl]), first = T::load(&mfirst[sl]);
+        uint32_t larger = 0, p = T::load(&mhead[sl]);
+        for (uint32_t steps = 0; steps < size && p != SQ_NONE; ++steps) {
+            if (p >= m) break;
+            larger += p > t ? 1u : 0u;
+            p = chain[p];
+        }
+        if (p != SQ_NONE) err |= MG_ERR_CHAIN;
+        const uint64_t place = first < m ? (uint64_t)hist[first] + larger : m;
+        if (place < m) nxt[place] = cur[t];
+        else err |= MG_ERR_PLACE;
+    }
+    T::sync();
+    return err;
+}
+// All stages of one group of n nodes whose container starts with b_init buckets; rank_out(node, rank) as replay_kmer_set's.  `area` is the
+// group's work area (mg_layout(n)).  Returns the lane's MG_ERR_* bits.
+template <typename T, typename KeyFn, typename RankFn>
+__host__ __device__ inline uint32_t mg_staged_order(uint32_t n, uint64_t b_init, unsigned k, uint32_t *area, KeyFn key, RankFn rank_out) {
+    const MgLayout l = mg_layout(n);
+    uint32_t *cur = area + l.seq_a, *nxt = area + l.seq_b, err = 0;
+    MgStage st = mg_stage_start(b_init);
+    for (uint32_t s = 0; mg_stage_next(n, st); ++s) {
+        if (s >= MG_MAX_STAGES) return err | MG_ERR_STAGES;   // (the same for every lane)
+        err |= mg_stage_order<T>(n, st, k, area, l, cur, nxt, key);
+        uint32_t *const x = cur;
+        cur = nxt;
+        nxt = x;
+    }
+    for (uint32_t r = T::lane(); r < n; r += T::W)
+        if (cur[r] < n) rank_out(cur[r], r);
+        else err |= MG_ERR_PLACE;
+    return err;
+}
+// One workgroup per wide group (a group of at least wide_min distinct k-mers; wide_group lists them, area_off[i] = word offset of the work
+// area of the i-th).  Writes time_of_seq as mg_order_kernel does, which skips these groups.  A violated loop bound sets *err.
+__global__ __launch_bounds__(BLOCK) void mg_order_wide_kernel(const uint64_t *__restrict__ kmers, const uint32_t *__restrict__ seq_pos, const uint32_t *__restrict__ goff,
+                                                               const uint64_t *__restrict__ b_init, const uint32_t *__restrict__ wide_group,
+                                                               const uint64_t *__restrict__ area_off, uint32_t *__restrict__ areas, uint32_t *__restrict__ time_of_seq,
+                                                               uint32_t *__restrict__ err, unsigned k) {
+    const uint32_t g = wide_group[blockIdx.x];
+    const uint32_t i0 = goff[g], n = goff[g + 1] - i0;
+    const uint32_t e = mg_staged_order<BlockTeam>(
+        n, b_init[g], k, areas + area_off[blockIdx.x],
+        [&](uint32_t node, uint64_t &lo, uint64_t &hi) {
+            const uint64_t pos = seq_pos[i0 + node];
+            lo = kmers[2 * pos];
+            hi = kmers[2 * pos + 1];
+        },
+        [&](uint32_t node, uint32_t rank) { time_of_seq[i0 + node] = i0 + rank + 1u; });
+    if (e) atomicOr(err, e);
 }
 // first time of every distinct k-mer of the unit
 __global__ __launch_bounds__(BLOCK) void mg_etime_kernel(const uint64_t *__restrict__ kmers, const uint32_t *__restrict__ seq_pos, const uint32_t *__restrict__ time_of_seq,
@@ -854,6 +1102,7 @@ struct bt_paths {
     uint32_t *d_list_cluster = nullptr;
     int64_t *d_list_slots = nullptr;
     std::vector<uint64_t> cluster_text0;   // first text position of each cluster (+ L at the end)
+    bt_multigroup_stats mg_stats{};        // how the last bt_paths_count_multigroup call ordered its groups (bt_paths_multigroup_info)
     // candidates result (host)
     bool have_candidates = false;
     uint32_t S = 0;
@@ -1128,6 +1377,168 @@ int bt_paths_create(bt_ctx *ctx, const bt_paths_batch *b, uint32_t k, bt_paths *
     return BT_OK;
 }
 
+// The iteration orders of G consecutive groups of distinct k-mers (steps 2 and 3 of bt_paths_count_multigroup; all of bt_kmer_set_orders).
+// Group g holds the k-mers kmers[2 * seq[i]], i in [goff[g], goff[g + 1]) (goff: the host's copy of d_goff); the first group's container
+// starts with initial_buckets buckets, every later one with what its predecessor left.  d_time[i] receives goff[g] + rank + 1.  Groups of
+// at least wide_min k-mers (0: none) are ordered stage by stage on a workgroup each (mg_order_wide_kernel, launched first), the others by
+// one lane each (mg_order_kernel); without a wide group the launches and allocations are the lane route's alone.  Device memory goes on
+// `tmp` (the caller frees it, also after an error) and the host arrays the uploads read live in `up`, which the caller keeps until it has
+// synchronised the stream; final_buckets (optional) receives every group's bucket count afterwards.
+struct MgUploads {
+    std::vector<uint64_t> moff, binit, area_off;
+    std::vector<uint32_t> wide;   // the wide groups, in launch order
+};
+static int mg_group_orders(bt_ctx *ctx, const char *who, const uint64_t *d_kmers, const uint32_t *d_seq, const uint32_t *d_goff, const std::vector<uint32_t> &goff, uint32_t G,
+                           unsigned k, uint64_t initial_buckets, uint32_t wide_min, uint32_t *d_time, uint64_t *final_buckets, bt_multigroup_stats &stats,
+                           MgUploads &up, std::vector<void *> &tmp) {
+    hipStream_t st = ctx->stream;
+    const uint64_t n_total = goff[G];
+    stats = bt_multigroup_stats{};
+    stats.num_groups = G;
+    stats.wide_min_kmers = wide_min;
+    std::vector<uint64_t> &moff = up.moff, &binit = up.binit, &area_off = up.area_off;
+    std::vector<uint32_t> &wide = up.wide;
+    moff.assign(G + 1, 0);
+    binit.assign(G + 1, 1);
+    wide.clear();
+    {
+        uint64_t B = initial_buckets ? initial_buckets : 1;
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t n = goff[g + 1] - goff[g];
+            const bool is_wide = wide_min && n && n >= wide_min;
+            if (is_wide && n > (1u << 30)) return fail(std::string(who) + ": a group of more than 2^30 distinct path k-mers cannot take the workgroup route");
+            binit[g] = B;
+            if (is_wide) {
+                MgStage stage = mg_stage_start(B);
+                uint32_t stages = 0;
+                while (stages <= MG_MAX_STAGES && mg_stage_next(n, stage)) ++stages;
+                stats.max_stages = std::max(stats.max_stages, stages);
+                wide.push_back(g);
+            }
+            // the set keeps its bucket count across clear(); a fresh set goes to 13 buckets with its first k-mer (for the next group's order 1 and 13 are
+            // the same start: a fresh set's first insert rehashes an empty list to 13)
+            while (B < n || (n && B <= 1)) B = std_next_bucket_count(B);
+            if (B >= 0xFFFFFFFEull) return fail(std::string(who) + ": a group with more than 3.5e9 distinct path k-mers");
+            if (final_buckets) final_buckets[g] = B;
+            moff[g + 1] = moff[g] + (n && !is_wide ? pow2_at_least(2 * (uint64_t)n) : 0);   // (a wide group's bucket map is part of its work area)
+            stats.max_group_kmers = std::max(stats.max_group_kmers, n);
+        }
+    }
+    stats.num_wide_groups = (uint32_t)wide.size();
+    uint64_t *d_moff = nullptr, *d_binit = nullptr;
+    uint32_t *d_next = nullptr, *d_mk = nullptr, *d_mv = nullptr;
+    int rc = BT_OK;
+    auto A = [&](auto **q, uint64_t n) {
+        if (rc == BT_OK) rc = dev_alloc(q, n, tmp);
+    };
+    A(&d_next, n_total); A(&d_moff, G + 1); A(&d_binit, G + 1); A(&d_mk, moff[G]); A(&d_mv, moff[G]);
+    if (rc != BT_OK) return rc;
+#define MGO(call)                                                                \
+    do {                                                                         \
+        const hipError_t _e = (call);                                            \
+        if (_e != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+    MGO(hipMemcpyAsync(d_moff, moff.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
+    MGO(hipMemcpyAsync(d_binit, binit.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
+    uint32_t *d_err = nullptr;
+    if (!wide.empty()) {
+        // the largest groups first: the launch ends with its longest workgroup either way, the short ones fill in behind it
+        std::stable_sort(wide.begin(), wide.end(), [&](uint32_t a, uint32_t b) { return goff[a + 1] - goff[a] > goff[b + 1] - goff[b]; });
+        area_off.assign(wide.size(), 0);
+        uint64_t words = 0;
+        for (size_t i = 0; i < wide.size(); ++i) {
+            area_off[i] = words;
+            words += mg_layout(goff[wide[i] + 1] - goff[wide[i]]).total;
+        }
+        stats.wide_scratch_bytes = words * 4;
+        uint32_t *d_wide = nullptr, *d_areas = nullptr;
+        uint64_t *d_area_off = nullptr;
+        A(&d_wide, wide.size()); A(&d_area_off, wide.size()); A(&d_areas, words); A(&d_err, 1);
+        if (rc != BT_OK) return rc;
+        MGO(hipMemcpyAsync(d_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice, st));
+        MGO(hipMemcpyAsync(d_area_off, area_off.data(), area_off.size() * 8, hipMemcpyHostToDevice, st));
+        MGO(hipMemsetAsync(d_err, 0, 4, st));
+        hipLaunchKernelGGL(mg_order_wide_kernel, dim3((unsigned)wide.size()), dim3(BLOCK), 0, st, d_kmers, d_seq, d_goff, d_binit, d_wide, d_area_off, d_areas, d_time, d_err, k);
+    }
+    if (G) hipLaunchKernelGGL(mg_order_kernel, dim3((G + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d_kmers, d_seq, d_goff, d_moff, d_binit, d_next, d_mk, d_mv, d_time, G, k, wide_min);
+    MGO(hipGetLastError());
+    if (d_err) {
+        uint32_t err = 0;
+        MGO(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
+        MGO(hipStreamSynchronize(st));
+        if (err) return fail(std::string(who) + ": the staged k-mer order of a wide group met a violated loop bound (code " + std::to_string(err) + ")");
+    }
+#undef MGO
+    return BT_OK;
+}
+
+int bt_kmer_set_orders(bt_ctx *ctx, const uint64_t *h_kmers, const uint64_t *h_off, uint32_t G, unsigned k, uint64_t initial_buckets, uint32_t wide_min, uint32_t *h_rank,
+                       uint64_t *h_final_buckets, bt_multigroup_stats *stats) {
+    if (!ctx || !h_off || !h_rank || (!h_kmers && G && h_off[G])) return fail("bt_kmer_set_orders: null argument");
+    if (k == 0 || k > 64) return fail("bt_kmer_set_orders: k must be in 1..64");
+    std::vector<uint32_t> goff(G + 1);
+    for (uint32_t g = 0; g <= G; ++g) {
+        if (h_off[g] >= 0xFFFFFFFEull || (g && h_off[g] < h_off[g - 1]) || h_off[0] != 0) return fail("bt_kmer_set_orders: offsets must start at 0, ascend and stay below 2^32 - 2");
+        goff[g] = (uint32_t)h_off[g];
+    }
+    BT_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n_total = goff[G];
+    std::vector<void *> tmp;
+    uint64_t *d_kmers = nullptr;
+    uint32_t *d_seq = nullptr, *d_goff = nullptr, *d_time = nullptr;
+    int rc = dev_alloc(&d_kmers, 2 * n_total, tmp);
+    if (rc == BT_OK) rc = dev_alloc(&d_seq, n_total, tmp);
+    if (rc == BT_OK) rc = dev_alloc(&d_goff, G + 1, tmp);
+    if (rc == BT_OK) rc = dev_alloc(&d_time, n_total, tmp);
+    std::vector<uint32_t> seq(n_total), time(n_total);
+    std::iota(seq.begin(), seq.end(), 0u);   // group g's k-mers are h_kmers[h_off[g] .. h_off[g + 1]) themselves
+    auto hip_ok = [&](hipError_t e) {
+        if (rc == BT_OK && e != hipSuccess) rc = fail(std::string("bt_kmer_set_orders: ") + hipGetErrorString(e));
+    };
+    if (rc == BT_OK && n_total) hip_ok(hipMemcpyAsync(d_kmers, h_kmers, n_total * 16, hipMemcpyHostToDevice, st));
+    if (rc == BT_OK && n_total) hip_ok(hipMemcpyAsync(d_seq, seq.data(), n_total * 4, hipMemcpyHostToDevice, st));
+    if (rc == BT_OK) hip_ok(hipMemcpyAsync(d_goff, goff.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, st));
+    bt_multigroup_stats local{};
+    MgUploads up;
+    if (rc == BT_OK) rc = mg_group_orders(ctx, "bt_kmer_set_orders", d_kmers, d_seq, d_goff, goff, G, k, initial_buckets, wide_min, d_time, h_final_buckets, local, up, tmp);
+    if (rc == BT_OK && n_total) hip_ok(hipMemcpyAsync(time.data(), d_time, n_total * 4, hipMemcpyDeviceToHost, st));
+    hip_ok(hipStreamSynchronize(st));
+    for (void *q : tmp) (void)hipFree(q);
+    if (rc != BT_OK) return rc;
+    for (uint32_t g = 0; g < G; ++g)
+        for (uint32_t i = goff[g]; i < goff[g + 1]; ++i) h_rank[i] = time[i] - goff[g] - 1u;
+    if (stats) *stats = local;
+    return BT_OK;
+}
+
+int bt_paths_multigroup_info(bt_paths *p, bt_multigroup_stats *stats) {
+    if (!p || !stats) return fail("bt_paths_multigroup_info: null argument");
+    *stats = p->mg_stats;
+    return BT_OK;
+}
+
+int bt_diag_kmer_set_order_staged(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets) {
+    if (!h_kmers || !h_rank) return fail("bt_diag_kmer_set_order_staged: null argument");
+    if (initial_buckets == 0) initial_buckets = 1;
+    MgStage last = mg_stage_start(initial_buckets);   // the plan alone gives the bucket count
+    for (uint32_t s = 0; s <= MG_MAX_STAGES && mg_stage_next(n, last); ++s) {
+    }
+    if (last.end < n || n > (1u << 30)) return fail("bt_diag_kmer_set_order_staged: more than 2^30 k-mers");
+    if (last.buckets >= 0xFFFFFFFEull) return fail("bt_diag_kmer_set_order_staged: a bucket count of 2^32 - 2 or more (the stage code numbers buckets in 32 bits)");
+    std::vector<uint32_t> area(mg_layout(n).total);
+    const uint32_t err = mg_staged_order<SoloTeam>(
+        n, initial_buckets, k, area.data(),
+        [&](uint32_t node, uint64_t &lo, uint64_t &hi) {
+            lo = h_kmers[2 * (size_t)node];
+            hi = h_kmers[2 * (size_t)node + 1];
+        },
+        [&](uint32_t node, uint32_t rank) { h_rank[node] = rank; });
+    if (err) return fail("bt_diag_kmer_set_order_staged: a violated loop bound (code " + std::to_string(err) + ")");
+    if (h_final_buckets) *h_final_buckets = last.buckets;
+    return BT_OK;
+}
+
 int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets) {
     if (!h_kmers || !h_rank) return fail("bt_diag_kmer_set_order: null argument");
     if (initial_buckets == 0) initial_buckets = 1;
@@ -1143,7 +1554,7 @@ int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial
         [&](uint32_t node, uint32_t rank) { h_rank[node] = rank; });
     if (h_final_buckets) {
         uint64_t B = initial_buckets;
-        while (B < n) B = std_next_bucket_count(B);
+        while (B < n || (n && B <= 1)) B = std_next_bucket_count(B);   // (a fresh set has 13 buckets after its first insert)
         *h_final_buckets = B;
     }
     return BT_OK;
@@ -1252,9 +1663,9 @@ int bt_paths_count_multigroup(bt_paths *p, const uint32_t *h_cluster_group, bt_b
     for (uint32_t c = p->C; c-- > 0;) gstart[h_cluster_group[c]] = p->cluster_text0[c];
     for (uint32_t g = G; g-- > 0;)
         if (gstart[g] == p->L && g + 1 <= G) gstart[g] = gstart[g + 1];   // a group index without clusters
-    uint64_t *d_gstart = nullptr, *d_moff = nullptr, *d_binit = nullptr;
-    uint32_t *d_goff = nullptr, *d_seq = nullptr, *d_time = nullptr, *d_next = nullptr, *d_mk = nullptr, *d_mv = nullptr;
-    A(&d_gstart, G + 1); A(&d_goff, G + 1); A(&d_seq, n_total); A(&d_time, n_total); A(&d_next, n_total); A(&d_moff, G + 1); A(&d_binit, G + 1);
+    uint64_t *d_gstart = nullptr;
+    uint32_t *d_goff = nullptr, *d_seq = nullptr, *d_time = nullptr;
+    A(&d_gstart, G + 1); A(&d_goff, G + 1); A(&d_seq, n_total); A(&d_time, n_total);
     MGR(rc);
     MGH(hipMemcpyAsync(d_gstart, gstart.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(gather_u32_kernel, dim3((G + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d_rowpos, d_gstart, G + 1, d_goff);
@@ -1262,26 +1673,22 @@ int bt_paths_count_multigroup(bt_paths *p, const uint32_t *h_cluster_group, bt_b
     std::vector<uint32_t> goff(G + 1);
     MGH(hipMemcpyAsync(goff.data(), d_goff, (size_t)(G + 1) * 4, hipMemcpyDeviceToHost, st));
     MGH(hipStreamSynchronize(st));
-    std::vector<uint64_t> moff(G + 1, 0), binit(G + 1, 1);
-    {
-        uint64_t B = 1;
-        for (uint32_t g = 0; g < G; ++g) {
-            const uint64_t n = goff[g + 1] - goff[g];
-            binit[g] = B;
-            while (B < n) B = std_next_bucket_count(B);   // the set keeps its bucket count across clear()
-            if (B >= 0xFFFFFFFEull) {
-                cleanup();
-                return fail("bt_paths_count_multigroup: a group with more than 3.5e9 distinct path k-mers");
-            }
-            moff[g + 1] = moff[g] + (n ? pow2_at_least(2 * n) : 0);
+    // 3. times: every group's k-mers in its container's iteration order (the set is fresh before the unit's first group).  BT_MG_WIDE_MIN = N sends groups
+    //    of at least N distinct k-mers to a workgroup each (mg_order_wide_kernel); unset or 0: one lane per group for all of them
+    uint32_t wide_min = 0;
+    if (const char *e = getenv("BT_MG_WIDE_MIN")) {   // a decimal number below 2^32, or the call fails: a mistyped threshold must not quietly become another one
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long v = std::strtoull(e, &end, 10);
+        if (*e < '0' || *e > '9' || *end != '\0' || errno != 0 || v > 0xFFFFFFFFull) {
+            cleanup();
+            return fail(std::string("bt_paths_count_multigroup: BT_MG_WIDE_MIN must be a decimal number of k-mers below 2^32 (0: off), not '") + e + "'");
         }
+        wide_min = (uint32_t)v;
     }
-    A(&d_mk, moff[G]); A(&d_mv, moff[G]);
-    MGR(rc);
-    MGH(hipMemcpyAsync(d_moff, moff.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
-    MGH(hipMemcpyAsync(d_binit, binit.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
-    // 3. times
-    if (G) hipLaunchKernelGGL(mg_order_kernel, dim3((G + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, p->d_kmers, d_seq, d_goff, d_moff, d_binit, d_next, d_mk, d_mv, d_time, G, p->k);
+    bt_multigroup_stats mg_stats{};   // (the handle's copy is replaced once the whole call has succeeded)
+    MgUploads up;
+    MGR(mg_group_orders(p->ctx, "bt_paths_count_multigroup", p->d_kmers, d_seq, d_goff, goff, G, p->k, 1, wide_min, d_time, nullptr, mg_stats, up, tmp));
     hipLaunchKernelGGL(mg_etime_kernel, dim3(grid_for(n_total, BLOCK, maxb)), dim3(BLOCK), 0, st, p->d_kmers, d_seq, d_time, n_total, elo, ehi, etag, estate, cap - 1, etime);
     // 4. k-mers the filter reports at their first turn
     uint32_t *f1 = nullptr, *f2 = nullptr;
@@ -1329,6 +1736,7 @@ int bt_paths_count_multigroup(bt_paths *p, const uint32_t *h_cluster_group, bt_b
 #undef MGH
 #undef MGR
     if (h_num_path_kmers) *h_num_path_kmers = counters[1];
+    if (rc == BT_OK) p->mg_stats = mg_stats;
     return rc;
 }
 

@@ -498,8 +498,19 @@ void KmerCounter::countPathMultigroupKmers(bt_table *multigroup_table, bt_bloom 
     PathsHandle paths;
     check(bt_paths_create(ctx, &builder.batch(), kmer_size, &paths.h, nullptr), "bt_paths_create");
     uint64_t num_kmers = 0;
+    const auto t0 = std::chrono::steady_clock::now();
     check(bt_paths_count_multigroup(paths.h, ug.cluster_group.data(), path_bloom, multigroup_table, &num_kmers), "bt_paths_count_multigroup");
     check(bt_sync(ctx), "bt_sync");
+    // which route ordered the groups' k-mers (BT_MG_WIDE_MIN), and whether this unit has a group large enough for the choice to matter
+    bt_multigroup_stats routes{};
+    check(bt_paths_multigroup_info(paths.h, &routes), "bt_paths_multigroup_info");
+    std::string row = "  multigroup pass (device): ";
+    if (routes.num_wide_groups > 0)
+        row += std::to_string(routes.num_wide_groups) + " group(s) of >= " + std::to_string(routes.wide_min_kmers) + " k-mers ordered on a workgroup each, the others on a lane each";
+    else
+        row += "every group ordered on a lane (workgroup threshold " + (routes.wide_min_kmers ? std::to_string(routes.wide_min_kmers) + " k-mers" : std::string("off")) + ")";
+    row += "; largest group " + std::to_string(routes.max_group_kmers) + " k-mers";
+    StageTimes::get().add(row, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     checkTable(multigroup_table, "countPathMultigroupKmers");
     unit->num_path_kmers = num_kmers;
 }

@@ -453,6 +453,12 @@ class Paths:
         check(bt_paths_count_multigroup(self.h, _np_ptr(cg), bloom.h, table.h, C.byref(n)))
         return n.value
 
+    def multigroup_info(self):
+        """how the last count_multigroup call ordered its groups (bt_paths_multigroup_info; the switch is BT_MG_WIDE_MIN)"""
+        st = MultigroupStats()
+        check(bt_paths_multigroup_info(self.h, C.byref(st)))
+        return st.as_dict()
+
     def classify(self, table, mg_bloom):
         n = np.zeros(self.C, np.uint32)
         ex = np.zeros(self.C, np.uint8)
@@ -679,6 +685,27 @@ bt_diag_genotype_text = _sig("bt_diag_genotype_text", [vp, C.c_uint64, vp, C.c_u
 bt_diag_format_g6 = _sig("bt_diag_format_g6", [vp, C.c_uint64, vp, vp])
 bt_diag_genotype_cluster = _sig("bt_diag_genotype_cluster", [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p])
 bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
+bt_diag_kmer_set_order_staged = _sig("bt_diag_kmer_set_order_staged", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
+bt_kmer_set_orders = _sig("bt_kmer_set_orders", [vp, vp, vp, C.c_uint32, C.c_uint, C.c_uint64, C.c_uint32, vp, vp, vp])
+bt_paths_multigroup_info = _sig("bt_paths_multigroup_info", [vp, vp])
+
+
+class MultigroupStats(C.Structure):   # include/btgpu.h: bt_multigroup_stats
+    _fields_ = [(n, C.c_uint32) for n in ("num_groups", "num_wide_groups", "wide_min_kmers", "max_group_kmers", "max_stages")] + [("wide_scratch_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def kmer_set_orders(ctx, groups, k, initial_buckets=1, wide_min=0):
+    """bt_kmer_set_orders: groups = arrays [n_g, 2] of distinct packed k-mers in insertion order -> (ranks per group, bucket count after each group, stats)"""
+    off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.uint64)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(g, np.uint64).reshape(-1, 2) for g in groups]) if len(groups) else np.zeros((0, 2), np.uint64))
+    rank = np.zeros(max(int(off[-1]), 1), np.uint32)
+    final = np.zeros(max(len(groups), 1), np.uint64)
+    stats = MultigroupStats()
+    check(bt_kmer_set_orders(ctx.h, _np_ptr(flat) if len(flat) else None, _np_ptr(off), len(groups), k, initial_buckets, wide_min, _np_ptr(rank), _np_ptr(final), C.byref(stats)))
+    return [rank[int(off[g]):int(off[g + 1])] for g in range(len(groups))], final[:len(groups)], stats.as_dict()
 
 
 bt_noise_model_create = _sig("bt_noise_model_create", [vp, C.c_uint32, vp, C.POINTER(vp)])

@@ -362,6 +362,26 @@ int bt_paths_count_kmers(bt_paths *p, bt_bloom *path_bloom);
  * depends on thread timing): groups in index order, a group's k-mers in the iteration order of the std::unordered_set<std::bitset<2k>>
  * (libstdc++) the reference collects them in and reuses from group to group.  Afterwards every path k-mer is in the filter. */
 int bt_paths_count_multigroup(bt_paths *p, const uint32_t *h_cluster_group, bt_bloom *path_bloom, bt_table *multigroup_table, uint64_t *h_num_path_kmers);
+/* How the iteration orders of KmerCounter.cpp:105-159 (the unordered_set of a group's path k-mers, :111-119) are computed on the device.  A group of at
+ * least wide_min_kmers distinct path k-mers is ordered by a workgroup of its own, stage by stage (a stage = the inserts between two rehashes; the list after a
+ * stage has a closed form), every other group by one lane that replays the container insert by insert; the orders are the same.  The threshold is
+ * BT_MG_WIDE_MIN, read at every bt_paths_count_multigroup call: unset or 0 = one lane per group for every group, N = groups of at least N distinct k-mers
+ * take a workgroup (1 = every non-empty group); anything but a decimal number below 2^32 fails the call.  The values describe the last call that SUCCEEDED.
+ * max_group_kmers: the largest group; max_stages: the most stages a wide group ran (0 without one);
+ * wide_scratch_bytes: device memory of the wide groups' work areas (0 without one). */
+typedef struct {
+    uint32_t num_groups, num_wide_groups, wide_min_kmers, max_group_kmers, max_stages;
+    uint64_t wide_scratch_bytes;
+} bt_multigroup_stats;
+/* the last bt_paths_count_multigroup call of this handle (all zero before the first); KmerCounter.cpp:105-159 has no counterpart */
+int bt_paths_multigroup_info(bt_paths *p, bt_multigroup_stats *stats);
+/* The container orders of KmerCounter.cpp:105-159 alone, by the routine bt_paths_count_multigroup runs: G consecutive groups of DISTINCT packed k-mers
+ * (2 x u64 each; group g = h_kmers[2 * h_off[g] .. 2 * h_off[g + 1]), in insertion order) go through one std::unordered_set<std::bitset<2k>> that starts
+ * with initial_buckets buckets (1 = freshly constructed) and is clear()ed between groups, so that every group inherits its predecessor's bucket count.
+ * h_rank[i] = position of k-mer i in its group's iteration order, h_final_buckets[g] (optional) = the bucket count after group g — both as
+ * bt_diag_kmer_set_order defines them; groups of at least wide_min k-mers (0 = none) take the workgroup route; stats is optional. */
+int bt_kmer_set_orders(bt_ctx *ctx, const uint64_t *h_kmers, const uint64_t *h_off, uint32_t G, unsigned k, uint64_t initial_buckets, uint32_t wide_min, uint32_t *h_rank,
+                       uint64_t *h_final_buckets, bt_multigroup_stats *stats);
 /* VariantClusterGraph::classifyPathKmers for every cluster (VariantClusterGraph.cpp:848-939): per distinct path k-mer of a
  * cluster the maximum over its paths of the (saturating) per-path multiplicity -> table update as bt_table_classify_batch.
  * h_num_path_kmers[c] = distinct k-mers of cluster c (num_path_kmers), h_has_excluded[c] = has_excluded_kmers. */
@@ -748,8 +768,13 @@ int bt_diag_format_g6(const double *h_values, uint64_t n, char *h_text16, int32_
 /* Host-side run of the container replay behind bt_paths_count_multigroup: n DISTINCT k-mers (2 x u64 each) are inserted, in the given
  * order, into an emulated libstdc++ std::unordered_set<std::bitset<2k>> that starts with `initial_buckets` buckets (1 = freshly
  * constructed; a set that was clear()ed keeps its bucket count); h_rank[i] = position of k-mer i in the set's iteration order,
- * *h_final_buckets = its bucket count afterwards.  (CPU tests compare it with the real container.) */
+ * *h_final_buckets = its bucket count afterwards: 13 for a fresh set that received at least one k-mer, as the real container reports (earlier versions
+ * reported 1 for n = 1; the ranks were never affected).  (CPU tests compare it with the real container.) */
 int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets);
+/* The same result by the staged order the workgroup route of bt_paths_count_multigroup runs (KmerCounter.cpp:105-159), on the host without a GPU: the same
+ * __host__ __device__ code with a team of one thread.  The bucket count comes from the stage plan alone.  initial_buckets (and the count the set grows to)
+ * must stay below 2^32 - 2, as on the device route: an error otherwise. */
+int bt_diag_kmer_set_order_staged(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets);
 
 #ifdef __cplusplus
 }
