@@ -15,6 +15,7 @@
 #endif
 #include "bt_genotypes.hpp"
 #include "bt_gibbs_kernel.hpp"
+#include "bt_gibbs_timeline.hpp"
 #include "bt_internal.hpp"
 
 #include <algorithm>
@@ -31,16 +32,16 @@ using namespace bt;
 namespace bt {
 // defined in bt_gibbs_simple_kernel.hip
 hipError_t launch_gibbs_simple_kernel(unsigned grid, uint32_t lds, hipStream_t st, const TileDesc *tiles, uint8_t *pool, const GParams *P, int op, uint32_t a0, uint32_t a1,
-                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list);
+                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list, TimelineDev *tl);
 hipError_t prepare_gibbs_simple_kernel(int max_lds);
 // defined in bt_gibbs_hot_kernel.hip
 hipError_t launch_gibbs_hot_kernel(unsigned grid, unsigned block, uint32_t lds, hipStream_t st, const TileDesc *tiles, uint8_t *pool, const GParams *P, int op, uint32_t a0, uint32_t a1,
-                                   unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list);
+                                   unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list, TimelineDev *tl);
 hipError_t prepare_gibbs_hot_kernel(int max_lds);
 hipError_t occupancy_gibbs_hot_kernel(int *blocks_per_cu, int block, uint32_t lds);
 // defined in bt_gibbs_single_kernel.hip
 hipError_t launch_gibbs_single_kernel(unsigned grid, unsigned block, uint32_t lds, hipStream_t st, const TileDesc *tiles, uint8_t *pool, const GParams *P, int op, uint32_t a0, uint32_t a1,
-                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list);
+                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list, TimelineDev *tl);
 hipError_t prepare_gibbs_single_kernel(int max_lds);
 hipError_t occupancy_gibbs_single_kernel(int *blocks_per_cu, int block, uint32_t lds);
 // defined in bt_gibbs_chain_kernel.hip
@@ -59,6 +60,14 @@ namespace {
 __global__ __launch_bounds__(LANES * 8, GIBBS_WAVES) void gibbs_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const GParams *__restrict__ Pg, int op,
                                                        uint32_t arg0, uint32_t arg1, unsigned long long *__restrict__ hist, TraceCfg tr, const uint32_t *__restrict__ tile_list) {
     gibbs_body<false>(tiles, pool, Pg, op, arg0, arg1, hist, tr, tile_list);
+}
+// the stamped sibling (bt_gibbs_timeline_*; launched for the sampling operations only): the same body between two clock reads; every return of the body comes back here
+__global__ __launch_bounds__(LANES * 8, GIBBS_WAVES) void gibbs_kernel_tl(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const GParams *__restrict__ Pg, int op,
+                                                          uint32_t arg0, uint32_t arg1, unsigned long long *__restrict__ hist, TraceCfg tr, const uint32_t *__restrict__ tile_list,
+                                                          TimelineDev *__restrict__ tl) {
+    TimelineDev *rec = timeline_start(tl, tile_list);
+    gibbs_body<false>(tiles, pool, Pg, op, arg0, arg1, hist, tr, tile_list);
+    timeline_end(rec);
 }
 
 // per (cluster, sample): most frequently sampled diplotype and its frequency -> the compact posterior summary that is
@@ -630,6 +639,7 @@ struct bt_gibbs {
         // wavefront a slot (tile, LDS offset) of d_pack, pack_lds bytes of LDS per workgroup
         uint32_t *d_pack = nullptr;
         uint32_t pack_wgs = 0, pack_waves = 1, pack_lds = 0;
+        std::vector<uint32_t> h_pack;     // the slot list on the host (bt_gibbs_timeline_fetch: which tile a wavefront of the launch was handed)
         hipStream_t stream = nullptr;     // nullptr: the context's stream
         hipEvent_t done = nullptr;
         hipEvent_t ready = nullptr;       // recorded on the class's stream right before its launch: the next class waits for it (launch(): start order)
@@ -657,6 +667,14 @@ struct bt_gibbs {
     uint64_t text_cap = 0, text_index_cap = 0;
     std::vector<uint32_t> h_var_off;   // [C+1] first variant of every cluster among the launch's variants
     uint64_t trace_words = 0;
+    // bt_gibbs_timeline_*: one TimelineDev per wavefront of every recorded launch, launches x waves records
+    struct Timeline {
+        TimelineDev *d = nullptr;
+        uint32_t max_launches = 0, launches = 0, dropped = 0;
+        uint64_t waves = 0;          // wavefronts of one launch over all classes (empty pack slots included)
+        std::vector<uint8_t> ops;    // the operation of every recorded launch
+        uint64_t bytes = 0;
+    } tl;
     // bt_gibbs_noise_iteration: pinned staging of the histogram (device -> host) and of the noise table (host -> device), device histogram
     uint64_t *h_pin_hist = nullptr, *d_iter_hist = nullptr;
     double *h_pin_noise = nullptr;
@@ -849,6 +867,14 @@ __global__ __launch_bounds__(256) void ucache_prefill_kernel(const TileDesc *__r
 // every call that enqueues on the sampler's stream would queue behind a resident chain's launch — which is itself waiting for the host
 inline bool chain_in_flight(const bt_gibbs *g) { return g->nc.active && g->nc.launched; }
 
+// launch timeline: wavefronts a sampling launch of the class has (grid x wavefronts per workgroup, as launch() launches it), and the kernel it runs
+inline uint64_t class_waves(const bt_gibbs::LaunchClass &c) {
+    if (c.simple) return c.tiles.size();
+    if (c.hot) return (uint64_t)c.pack_wgs * c.pack_waves;   // (c.single implies c.hot)
+    return (uint64_t)c.tiles.size() * c.split;
+}
+inline uint8_t class_kernel(const bt_gibbs::LaunchClass &c) { return c.simple ? 2 : (c.single ? 3 : (c.hot ? 1 : 0)); }
+
 int launch(bt_gibbs *g, int op, uint32_t a0, uint32_t a1, unsigned long long *hist) {
     if (!g->lut_set && (op == OP_RUN || op == OP_SWEEP)) return fail("bt_gibbs: count-model LUTs not set (bt_gibbs_set_lut)");
     if (g->nc.active && g->nc.launched) return fail("bt_gibbs: a resident noise chain is in progress (bt_gibbs_noise_chain_end)");
@@ -858,6 +884,17 @@ int launch(bt_gibbs *g, int op, uint32_t a0, uint32_t a1, unsigned long long *hi
     const bool wide = (op == OP_NOISE && a0 != 0) || (op == OP_INIT_CHAIN && a1 != 0);
     TraceCfg tr{g->trace_sweeps, g->d_trace_counter, g->d_trace};
     const bool fork = g->classes.size() > 1;
+    // launch timeline: a sampling launch takes a slot of records while slots remain and runs the stamped siblings; anything else launches what it always did
+    // (the launches of a noise chain, resident or launch by launch, are never recorded)
+    TimelineDev *tl = nullptr;
+    if (g->tl.d && !g->nc.active && (op == OP_RUN || op == OP_SWEEP || op == OP_INIT_CHAIN)) {
+        if (g->tl.launches < g->tl.max_launches) {
+            tl = g->tl.d + (uint64_t)g->tl.launches * g->tl.waves;
+            g->tl.ops.push_back((uint8_t)op);
+            g->tl.launches += 1;
+        } else
+            g->tl.dropped += 1;
+    }
     if (fork) BT_HIP(hipEventRecord(g->ev_fork, g->ctx->stream));
     // BT_GIBBS_ORDER (tuning): "hot_first" = the class of the two-haplotype tiles (gibbs_simple_kernel, on the context's stream) starts when the other classes'
     // launches are through; unset = all classes start together
@@ -894,15 +931,19 @@ int launch(bt_gibbs *g, int op, uint32_t a0, uint32_t a1, unsigned long long *hi
             hipLaunchKernelGGL(gibbs_noise_kernel, dim3(grid), dim3(LANES * c.split), (size_t)g->S * 1024, st, (const TileDesc *)g->d_tiles, g->d_pool, (const GParams *)g->d_params, a0, hist,
                                (const uint32_t *)c.d_tiles, (uint32_t)c.tiles.size());
         } else if (c.simple && (op == OP_RUN || op == OP_SWEEP || op == OP_INIT_CHAIN))
-            BT_HIP(launch_gibbs_simple_kernel((unsigned)c.tiles.size(), c.lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_tiles));
+            BT_HIP(launch_gibbs_simple_kernel((unsigned)c.tiles.size(), c.lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_tiles, tl));
         else if (c.single && (op == OP_RUN || op == OP_SWEEP || op == OP_INIT_CHAIN))
-            BT_HIP(launch_gibbs_single_kernel(c.pack_wgs, LANES * c.pack_waves, c.pack_lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_pack));
+            BT_HIP(launch_gibbs_single_kernel(c.pack_wgs, LANES * c.pack_waves, c.pack_lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_pack, tl));
         else if (c.hot && (op == OP_RUN || op == OP_SWEEP || op == OP_INIT_CHAIN))
-            BT_HIP(launch_gibbs_hot_kernel(c.pack_wgs, LANES * c.pack_waves, c.pack_lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_pack));
+            BT_HIP(launch_gibbs_hot_kernel(c.pack_wgs, LANES * c.pack_waves, c.pack_lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr, (const uint32_t *)c.d_pack, tl));
+        else if (tl)
+            hipLaunchKernelGGL(gibbs_kernel_tl, dim3((unsigned)c.tiles.size()), dim3(LANES * c.split), c.lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr,
+                               (const uint32_t *)c.d_tiles, tl);
         else
             hipLaunchKernelGGL(gibbs_kernel, dim3((unsigned)c.tiles.size()), dim3(LANES * c.split), c.lds, st, g->d_tiles, g->d_pool, g->d_params, op, a0, a1, hist, tr,
                                (const uint32_t *)c.d_tiles);
         BT_CHECK_LAUNCH();
+        if (tl) tl += class_waves(c);   // the next class's records
         if (wide && c.num_fill) {
             hipLaunchKernelGGL(nan_fill_kernel, dim3(c.num_fill), dim3(256), 0, st, g->d_pool, (const FillChunk *)c.d_fill);
             BT_CHECK_LAUNCH();
@@ -2202,6 +2243,7 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
             c.pack_wgs = pack(bestW, bestT, &slots, &top);
             c.pack_waves = bestW;
             c.pack_lds = top;
+            c.h_pack = slots;
             BT_TRYHIP(hipMalloc(reinterpret_cast<void **>(&c.d_pack), slots.size() * 4));
             g->allocs.push_back(c.d_pack);
             BT_TRYHIP(staged_upload(ctx, c.d_pack, slots.data(), slots.size() * 4));
@@ -2215,6 +2257,7 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
             }
         }
         BT_TRYHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gibbs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHotBudget));
+        BT_TRYHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gibbs_kernel_tl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHotBudget));
         BT_TRYHIP(prepare_gibbs_simple_kernel((int)kHotBudget));
         BT_TRYHIP(prepare_gibbs_hot_kernel((int)kHotBudget));
         BT_TRYHIP(prepare_gibbs_single_kernel((int)kHotBudget));
@@ -2343,6 +2386,7 @@ int bt_gibbs_destroy(bt_gibbs *g) {
     const auto t_rel1 = std::chrono::steady_clock::now();
     if (g->d_trace) (void)hipFree(g->d_trace);
     if (g->d_trace_counter) (void)hipFree(g->d_trace_counter);
+    if (g->tl.d) (void)hipFree(g->tl.d);
     if (g->d_wire) (void)hipFree(g->d_wire);
     if (g->d_geno) (void)hipFree(g->d_geno);
     if (g->d_text) (void)hipFree(g->d_text);
@@ -3305,6 +3349,125 @@ int bt_gibbs_trace_fetch(bt_gibbs *g, uint32_t *h_trace, uint64_t max_words, uin
         BT_HIP(hipMemcpy(&n0, g->d_trace_counter + (size_t)g->group_tile[0] * LANES + g->group_lane[0], 4, hipMemcpyDeviceToHost));
         *num_sweeps_recorded = n0;
     }
+    return BT_OK;
+}
+
+// ---- launch timeline (include/btgpu.h) ----------------------------------------------------------------------------
+static_assert(sizeof(bt_gibbs_timeline_record) == 48 && sizeof(TimelineDev) == 32, "timeline record layouts");
+static uint32_t timeline_tick_khz(const bt_gibbs *g) {   // rate of wall_clock64(), as bt_gibbs_noise_chain_begin reads it
+    int wall_khz = 0;
+    if (hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, g->ctx->device) != hipSuccess || wall_khz <= 0) wall_khz = 100000;
+    return (uint32_t)wall_khz;
+}
+// records of one launch that bt_gibbs_timeline_fetch hands out: every wavefront but the empty slots of a packed launch
+static uint64_t timeline_records_per_launch(const bt_gibbs *g) {
+    uint64_t n = 0;
+    for (const auto &c : g->classes) {
+        if (c.hot && !c.simple) {
+            for (size_t s = 0; s < c.h_pack.size(); s += 2) n += c.h_pack[s] != 0xFFFFFFFFu ? 1 : 0;
+        } else
+            n += class_waves(c);
+    }
+    return n;
+}
+
+int bt_gibbs_timeline_enable(bt_gibbs *g, uint32_t max_launches) {
+    if (!g) return fail("bt_gibbs_timeline_enable: null handle");
+    if (chain_in_flight(g)) return fail("bt_gibbs_timeline_enable: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
+    BT_HIP(hipSetDevice(g->ctx->device));
+    BT_HIP(hipStreamSynchronize(g->ctx->stream));
+    if (g->tl.d) {
+        BT_HIP(hipFree(g->tl.d));
+        g->device_bytes -= g->tl.bytes;
+    }
+    g->tl = bt_gibbs::Timeline{};
+    if (max_launches == 0) return BT_OK;
+    uint64_t waves = 0;
+    for (const auto &c : g->classes) waves += class_waves(c);
+    const uint64_t bytes = (uint64_t)max_launches * waves * sizeof(TimelineDev);
+    if (waves == 0 || bytes > (1ull << 34)) return fail("bt_gibbs_timeline_enable: more than 16 GiB of records asked for");
+    TimelineDev *d = nullptr;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d), bytes));
+    const hipError_t e = hipMemset(d, 0, bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(std::string("bt_gibbs_timeline_enable: ") + hipGetErrorString(e));
+    }
+    g->tl.d = d;
+    g->tl.max_launches = max_launches;
+    g->tl.waves = waves;
+    g->tl.bytes = bytes;
+    g->device_bytes += bytes;
+    return BT_OK;
+}
+
+int bt_gibbs_timeline_sizes(bt_gibbs *g, uint64_t *records, uint32_t *launches, uint32_t *dropped, uint32_t *tick_khz) {
+    if (!g) return fail("bt_gibbs_timeline_sizes: null handle");
+    if (records) *records = g->tl.d ? (uint64_t)g->tl.launches * timeline_records_per_launch(g) : 0;
+    if (launches) *launches = g->tl.launches;
+    if (dropped) *dropped = g->tl.dropped;
+    if (tick_khz) *tick_khz = timeline_tick_khz(g);
+    return BT_OK;
+}
+
+int bt_gibbs_timeline_fetch(bt_gibbs *g, bt_gibbs_timeline_record *h_out, uint64_t capacity, uint64_t *n) {
+    if (!g || !n) return fail("bt_gibbs_timeline_fetch: null argument");
+    if (chain_in_flight(g)) return fail("bt_gibbs_timeline_fetch: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
+    const uint64_t need = g->tl.d ? (uint64_t)g->tl.launches * timeline_records_per_launch(g) : 0;
+    *n = need;
+    if (need == 0) return BT_OK;
+    if (!h_out || capacity < need) return fail("bt_gibbs_timeline_fetch: buffer too small");
+    BT_HIP(hipSetDevice(g->ctx->device));
+    BT_HIP(hipStreamSynchronize(g->ctx->stream));
+    std::vector<TimelineDev> raw((size_t)g->tl.launches * g->tl.waves);
+    BT_HIP(hipMemcpy(raw.data(), g->tl.d, raw.size() * sizeof(TimelineDev), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> tile_groups(g->ntiles, 0);
+    for (uint32_t gi = 0; gi < g->G; ++gi) tile_groups[g->group_tile[gi]] += 1;
+    // everything is checked before anything is written
+    std::vector<bt_gibbs_timeline_record> out;
+    out.reserve(need);
+    for (uint32_t l = 0; l < g->tl.launches; ++l) {
+        uint64_t at = (uint64_t)l * g->tl.waves;
+        for (size_t ci = 0; ci < g->classes.size(); ++ci) {
+            const auto &c = g->classes[ci];
+            const bool packed = c.hot && !c.simple;
+            const uint32_t wpt = packed || c.simple ? 1u : c.split;   // wavefronts per tile (a packed workgroup's wavefronts run a tile each)
+            const uint64_t nw = class_waves(c);
+            for (uint64_t s = 0; s < nw; ++s, ++at) {
+                const uint32_t plan = packed ? c.h_pack[2 * s] : c.tiles[s / wpt];
+                const TimelineDev &d = raw[at];
+                if (d.tile != plan) {
+                    char buf[256];
+                    snprintf(buf, sizeof buf, "bt_gibbs_timeline_fetch: launch %u class %zu slot %llu: the wavefront reported tile %u, the plan has tile %u (start tick %llu)", l, ci,
+                             (unsigned long long)s, d.tile, plan, d.start_tick);
+                    return fail(buf);
+                }
+                if (plan == 0xFFFFFFFFu) continue;   // a slot of the last workgroups without a tile
+                bt_gibbs_timeline_record r{};
+                r.start_tick = d.start_tick;
+                r.end_tick = d.end_tick;
+                r.hw_id = d.hw_id;
+                r.xcc_id = d.xcc_id;
+                r.tile = d.tile;
+                r.wave = (uint32_t)(s % wpt);
+                r.launch = l;
+                r.launch_class = (uint16_t)ci;
+                r.kernel = class_kernel(c);
+                r.op = g->tl.ops[l];
+                r.groups = tile_groups[plan];
+                r.lds_bytes = tile_lds_bytes(g->tiles[plan]);
+                out.push_back(r);
+            }
+        }
+    }
+    if (out.size() != need) return fail("bt_gibbs_timeline_fetch: internal: record count differs from the plan's");
+    std::memcpy(h_out, out.data(), out.size() * sizeof(bt_gibbs_timeline_record));
+    return BT_OK;
+}
+
+int bt_gibbs_timeline_summary(const bt_gibbs_timeline_record *r, uint64_t n, uint32_t launch, uint32_t launch_class, bt_gibbs_timeline_summary_t *out) {
+    if (!out || (n && !r)) return fail("bt_gibbs_timeline_summary: null argument");
+    bt::timeline_summary(r, n, launch, launch_class, out);
     return BT_OK;
 }
 

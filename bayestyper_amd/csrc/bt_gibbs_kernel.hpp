@@ -386,4 +386,30 @@ __device__ __forceinline__ void gibbs_body(const TileDesc *__restrict__ tiles, u
     if (whole)
         for (uint32_t v = 0; v < nvert; ++v) hot_swap(env, v, false);
 }
+
+// ---- launch timeline (bt_gibbs_timeline_*): what the stamped siblings of the four sampling kernels (suffix _tl) write ----------------------------
+// One record per wavefront of a launch, written by its lane 0 with plain stores: the wall clock before and after the body, the raw HW_ID and XCC_ID
+// registers and the tile the wavefront is about to run (the body's own expression).  No kernel code reads the records and no output value depends on
+// them; the unstamped kernels execute none of this (launch() picks a sibling only while a timeline is on and has room).
+struct TimelineDev {   // 32 bytes
+    unsigned long long start_tick, end_tick;   // wall_clock64(); end_tick 0: the wavefront never reached its end stamp
+    uint32_t hw_id, xcc_id, tile, pad;
+};
+// slot of a wavefront within its launch class: blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64 (one-wavefront workgroups, the wavefronts of a split
+// tile, the slots of a packed workgroup)
+__device__ __forceinline__ TimelineDev *timeline_start(TimelineDev *__restrict__ recs, const uint32_t *__restrict__ tile_list) {
+    TimelineDev *r = recs + (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if ((threadIdx.x & 63u) == 0) {
+        r->tile = kPacked ? ((const uint32_t BT_CAS *)tile_list)[2u * pack_slot()] : (tile_list ? tile_list[blockIdx.x] : blockIdx.x);   // gibbs_body's expression
+        r->hw_id = __builtin_amdgcn_s_getreg(4 | (31 << 11));     // HW_REG_HW_ID, bits 0..31
+        r->xcc_id = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_REG_XCC_ID
+        r->start_tick = (unsigned long long)wall_clock64();
+    }
+    return r;
+}
+// (the record's address is kept across the body; computing it again at the end from the launch geometry was tried and left gibbs_kernel_tl with gibbs_kernel's
+// own scratch size, but made gibbs_hot_kernel_tl and gibbs_single_kernel_tl spill more: DESIGN.md §4.1b)
+__device__ __forceinline__ void timeline_end(TimelineDev *r) {
+    if ((threadIdx.x & 63u) == 0) r->end_tick = (unsigned long long)wall_clock64();
+}
 }  // namespace bt

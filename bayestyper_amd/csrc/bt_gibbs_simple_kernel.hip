@@ -15,12 +15,21 @@ __global__ __launch_bounds__(LANES, GIBBS_SIMPLE_WAVES) void gibbs_simple_kernel
                                                                                   const uint32_t *__restrict__ tile_list) {
     gibbs_body<true>(tiles, pool, Pg, op, arg0, arg1, hist, tr, tile_list);
 }
+// the stamped sibling (bt_gibbs_timeline_*): the same body between two clock reads; every return of the body comes back here
+__global__ __launch_bounds__(LANES, GIBBS_SIMPLE_WAVES) void gibbs_simple_kernel_tl(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const GParams *__restrict__ Pg,
+                                                                                     int op, uint32_t arg0, uint32_t arg1, unsigned long long *__restrict__ hist, TraceCfg tr,
+                                                                                     const uint32_t *__restrict__ tile_list, TimelineDev *__restrict__ tl) {
+    TimelineDev *rec = timeline_start(tl, tile_list);
+    gibbs_body<true>(tiles, pool, Pg, op, arg0, arg1, hist, tr, tile_list);
+    timeline_end(rec);
+}
 }  // namespace
 
 namespace bt {
 hipError_t launch_gibbs_simple_kernel(unsigned grid, uint32_t lds, hipStream_t st, const TileDesc *tiles, uint8_t *pool, const GParams *P, int op, uint32_t a0, uint32_t a1,
-                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list) {
-    hipLaunchKernelGGL(gibbs_simple_kernel, dim3(grid), dim3(LANES), lds, st, tiles, pool, P, op, a0, a1, hist, tr, tile_list);
+                                      unsigned long long *hist, TraceCfg tr, const uint32_t *tile_list, TimelineDev *tl) {
+    if (tl) hipLaunchKernelGGL(gibbs_simple_kernel_tl, dim3(grid), dim3(LANES), lds, st, tiles, pool, P, op, a0, a1, hist, tr, tile_list, tl);
+    else hipLaunchKernelGGL(gibbs_simple_kernel, dim3(grid), dim3(LANES), lds, st, tiles, pool, P, op, a0, a1, hist, tr, tile_list);
     return hipGetLastError();
 }
 #ifdef BT_PROF
@@ -34,6 +43,7 @@ hipError_t simple_prof_read(unsigned long long *h_out32, int reset) {   // this 
 }
 #endif
 hipError_t prepare_gibbs_simple_kernel(int max_lds) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(gibbs_simple_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gibbs_simple_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(gibbs_simple_kernel_tl), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
 }
 }  // namespace bt

@@ -82,6 +82,19 @@ struct GpuSampler : GibbsSampler {
     }
     void sweep(uint32_t n, bool collect) override { check(bt_gibbs_sweep(g, n, collect ? 1 : 0), "bt_gibbs_sweep"); }
     void run() override { check(bt_gibbs_run(g), "bt_gibbs_run"); }
+    bool timelineEnable(uint32_t max_launches) override {
+        check(bt_gibbs_timeline_enable(g, max_launches), "bt_gibbs_timeline_enable");
+        return true;
+    }
+    bool timeline(std::vector<bt_gibbs_timeline_record> *records, uint32_t *tick_khz, uint32_t *dropped) override {
+        uint64_t n = 0, got = 0;
+        uint32_t launches = 0;
+        check(bt_gibbs_timeline_sizes(g, &n, &launches, dropped, tick_khz), "bt_gibbs_timeline_sizes");
+        records->resize(n);
+        check(bt_gibbs_timeline_fetch(g, records->data(), n, &got), "bt_gibbs_timeline_fetch");
+        records->resize(got);
+        return true;
+    }
     void sync() override {
         if (getenv("BT_STAGE_TIMES")) check(bt_sync(ctx), "bt_sync");
     }
@@ -495,11 +508,102 @@ void InferenceEngine::runDefault(const GibbsBatchData &batch, const CountDistrib
     }
     num_launches += 1;
     sampler->setLut(cd.genomicTable().data(), cd.noiseTable().data());
+    // BT_GIBBS_TIMELINE: a slot per launch of the schedule (BT_GIBBS_STEPWISE: a chain start and up to two sweep launches per chain)
+    const bool stepwise = getenv("BT_GIBBS_STEPWISE") && atoi(getenv("BT_GIBBS_STEPWISE")) != 0;
+    const bool timeline = !timeline_path.empty() && sampler->timelineEnable(stepwise ? 3 * std::max(1u, opt.chains) : 1u);
     stage.reset(new StageScope("Gibbs: sampling launch (20 x 350 sweeps)"));
     sampler->run();
     sampler->sync();
     stage.reset();
+    if (timeline) writeTimeline(sampler.get(), batch);
     handOver(sampler, batch, collect);
+}
+
+// BT_GIBBS_TIMELINE: one JSON object per recorded launch of this sampler, appended to the file; times in seconds (ticks / tick_khz)
+void InferenceEngine::writeTimeline(Sampler *sampler, const GibbsBatchData &batch) {
+    std::vector<bt_gibbs_timeline_record> rec;
+    uint32_t khz = 0, dropped = 0;
+    if (!sampler->timeline(&rec, &khz, &dropped) || khz == 0) return;
+    static const char *kernel_names[4] = {"gibbs_kernel", "gibbs_hot_kernel", "gibbs_simple_kernel", "gibbs_single_kernel"};
+    static const char *op_names[3] = {"run", "init_chain", "sweep"};
+    const double per_tick = 1.0 / (1e3 * (double)khz);
+    uint32_t g_lo = 0xFFFFFFFFu, g_hi = 0, launches = 0, classes = 0;
+    for (uint32_t gi : batch.group_index) g_lo = std::min(g_lo, gi), g_hi = std::max(g_hi, gi);
+    for (const auto &r : rec) launches = std::max(launches, r.launch + 1), classes = std::max<uint32_t>(classes, r.launch_class + 1u);
+    std::ofstream out(timeline_path, std::ios::app);
+    if (!out) throw std::runtime_error("BT_GIBBS_TIMELINE: cannot append to " + timeline_path);
+    out.precision(9);
+    auto summary_json = [&](std::ostream &os, const bt_gibbs_timeline_summary_t &s) {
+        const uint64_t span = s.last_end - s.first_start;
+        os << "\"records\": " << s.records << ", \"unfinished\": " << s.unfinished << ", \"makespan_s\": " << span * per_tick << ", \"busy_s\": " << s.busy_ticks * per_tick
+           << ", \"mean_live\": " << (span ? (double)s.busy_ticks / (double)span : 0.0) << ", \"peak_live\": " << s.peak_live
+           << ", \"median_end_s\": " << (s.records ? (s.median_end - s.first_start) * per_tick : 0.0) << ", \"idle_after_median_s\": " << s.idle_after_median_ticks * per_tick
+           << ", \"idle_after_median_share\": " << (span && s.peak_live ? (double)s.idle_after_median_ticks / ((double)s.peak_live * (double)span) : 0.0);
+    };
+    for (uint32_t l = 0; l < launches; l++) {
+        bt_gibbs_timeline_summary_t all{};
+        if (bt_gibbs_timeline_summary(rec.data(), rec.size(), l, ~0u, &all) != BT_OK) throw std::runtime_error(std::string("bt_gibbs_timeline_summary: ") + bt_last_error());
+        std::vector<size_t> mine;
+        for (size_t i = 0; i < rec.size(); i++)
+            if (rec[i].launch == l) mine.push_back(i);
+        if (mine.empty()) continue;
+        const uint8_t op = rec[mine[0]].op;
+        out << "{\"groups\": [" << g_lo << ", " << g_hi << "], \"num_groups\": " << batch.numGroups() << ", \"launch\": " << l << ", \"op\": \"" << (op < 3 ? op_names[op] : "?")
+            << "\", \"tick_khz\": " << khz << ", \"dropped\": " << dropped << ", \"summary\": {";
+        summary_json(out, all);
+        out << "}, \"classes\": [";
+        bool first = true;
+        for (uint32_t c = 0; c < classes; c++) {
+            bt_gibbs_timeline_summary_t cs{};
+            if (bt_gibbs_timeline_summary(rec.data(), rec.size(), l, c, &cs) != BT_OK) throw std::runtime_error(std::string("bt_gibbs_timeline_summary: ") + bt_last_error());
+            if (cs.records + cs.unfinished == 0) continue;
+            uint32_t lds = 0, kernel = 0;
+            uint64_t waves = 0;
+            for (size_t i : mine)
+                if (rec[i].launch_class == c) lds = std::max(lds, rec[i].lds_bytes), kernel = rec[i].kernel, waves += 1;
+            out << (first ? "" : ", ") << "{\"class\": " << c << ", \"kernel\": \"" << kernel_names[kernel & 3] << "\", \"wavefronts\": " << waves << ", \"lds_bytes\": " << lds
+                << ", \"start_s\": " << (cs.records ? (cs.first_start - all.first_start) * per_tick : 0.0) << ", ";
+            summary_json(out, cs);
+            out << "}";
+            first = false;
+        }
+        out << "], \"longest\": [";
+        std::vector<size_t> by_len = mine;
+        auto len = [&](size_t i) { return rec[i].end_tick > rec[i].start_tick ? rec[i].end_tick - rec[i].start_tick : 0; };
+        std::stable_sort(by_len.begin(), by_len.end(), [&](size_t a, size_t b) { return len(a) > len(b); });
+        auto record_json = [&](const bt_gibbs_timeline_record &r) {
+            out << "{\"tile\": " << r.tile << ", \"wave\": " << r.wave << ", \"class\": " << r.launch_class << ", \"kernel\": \"" << kernel_names[r.kernel & 3] << "\", \"start_s\": "
+                << (r.start_tick - all.first_start) * per_tick << ", \"seconds\": " << (r.end_tick > r.start_tick ? (r.end_tick - r.start_tick) * per_tick : 0.0) << ", \"groups\": " << r.groups
+                << ", \"lds_bytes\": " << r.lds_bytes << ", \"hw_id\": " << r.hw_id << ", \"xcc_id\": " << r.xcc_id << "}";
+        };
+        for (size_t k = 0; k < std::min<size_t>(10, by_len.size()); k++) {
+            out << (k ? ", " : "");
+            record_json(rec[by_len[k]]);
+        }
+        out << "]";
+        if (timeline_raw) {
+            out << ", \"records\": [";
+            for (size_t k = 0; k < mine.size(); k++) {
+                const auto &r = rec[mine[k]];
+                out << (k ? ", " : "") << "[" << r.start_tick << ", " << r.end_tick << ", " << r.hw_id << ", " << r.xcc_id << ", " << r.tile << ", " << r.wave << ", " << r.launch_class << ", "
+                    << (unsigned)r.kernel << ", " << r.groups << ", " << r.lds_bytes << "]";
+            }
+            out << "]";
+        }
+        out << "}\n";
+        if (getenv("BT_STAGE_TIMES") && all.records) {
+            const uint64_t span = all.last_end - all.first_start;
+            const auto &last = rec[all.last_record];
+            std::ostringstream row;
+            row.precision(4);
+            row << "  Gibbs timeline, groups " << g_lo << ".." << g_hi << ", launch " << l << " (" << (op < 3 ? op_names[op] : "?") << "): " << all.records << " wavefronts, mean " << (span ? (double)all.busy_ticks / (double)span : 0.0)
+                << " / peak " << all.peak_live << " live, idle after the median end " << all.idle_after_median_ticks * per_tick << " s ("
+                << (span && all.peak_live ? 100.0 * (double)all.idle_after_median_ticks / ((double)all.peak_live * (double)span) : 0.0) << " % of peak x makespan), last tile " << last.tile
+                << " of class " << last.launch_class << " (" << kernel_names[last.kernel & 3] << ")";
+            StageTimes::get().add(row.str(), span * per_tick);
+        }
+    }
+    if (!out.flush()) throw std::runtime_error("BT_GIBBS_TIMELINE: writing " + timeline_path + " failed");
 }
 
 // a finished launch's collected samples -> the caller; the sampler is released (its HBM is free before the next one is built)

@@ -109,6 +109,10 @@ struct GibbsSampler {
                               uint32_t * /*not_covered*/) {
         return false;
     }
+    // the launch timeline (bt_gibbs_timeline_*): room for the wavefront records of max_launches sampling launches / the records of the launches since;
+    // false: not supported
+    virtual bool timelineEnable(uint32_t /*max_launches*/) { return false; }
+    virtual bool timeline(std::vector<bt_gibbs_timeline_record> * /*records*/, uint32_t * /*tick_khz*/, uint32_t * /*dropped*/) { return false; }
 };
 typedef std::function<std::unique_ptr<GibbsSampler>(const bt_gibbs_params &, const GibbsBatchData &)> SamplerFactory;
 
@@ -163,6 +167,12 @@ class InferenceEngine {
     void recordNoiseRows(bool on) { record_rows = on; }
     const std::vector<double> &noiseRows() const { return noise_rows; }
     void setQuiet(bool q) { quiet = q; }
+    // BT_GIBBS_TIMELINE=<file> (one process): every default-mode sampling launch runs its stamped kernels and appends one JSON object per launch to the
+    // file (raw: with the wavefront records); BT_STAGE_TIMES gets a row per launch.  Empty path (the default): nothing is allocated, launched or printed differently.
+    void setTimelineFile(std::string path, bool raw) {
+        timeline_path = std::move(path);
+        timeline_raw = raw;
+    }
 
   private:
     typedef GibbsSampler Sampler;
@@ -194,6 +204,9 @@ class InferenceEngine {
     void runNoiseChain(Sampler *sampler, CountDistribution *cd, uint32_t chain, uint32_t first_collect_iteration, std::ostream &out,
                        const std::function<void(uint32_t iteration, const std::vector<double> &rates)> &each);
     bool record_rows = false, quiet = false;
+    std::string timeline_path;
+    bool timeline_raw = false;
+    void writeTimeline(Sampler *sampler, const GibbsBatchData &batch);
     bool pending_noise = false;   // the count distribution holds a noise table the sampler has not been given yet
     std::vector<double> noise_rows;
 };

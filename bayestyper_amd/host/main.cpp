@@ -529,6 +529,16 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         names[s] = samples[s].name;
     }
     InferenceEngine inference_engine(ctx.h, gender, names, gibbs);
+    // BT_GIBBS_TIMELINE=<file> (one process): when every wavefront of a default-mode sampling launch started and ended (bt_gibbs_timeline_*), one JSON object
+    // per launch appended to the file; BT_GIBBS_TIMELINE_RAW=1 adds the records themselves
+    if (const char *tl = getenv("BT_GIBBS_TIMELINE")) {
+        if (*tl && comm) {
+            if (rank == 0) std::cout << "BT_GIBBS_TIMELINE is ignored in a run of several ranks" << std::endl;
+        } else if (*tl) {
+            const char *raw = getenv("BT_GIBBS_TIMELINE_RAW");
+            inference_engine.setTimelineFile(tl, raw && *raw && std::strcmp(raw, "0") != 0);
+        }
+    }
     // this rank's groups: the whole unit, or its share (ascending unit-wide group indices; LPT on a cost proxy, the same on every rank)
     std::vector<std::vector<uint32_t>> rank_groups;
     std::vector<uint32_t> unit_clusters, unit_variants;   // per group of the WHOLE unit (estimateNoise selects its groups from them on every rank alike)

@@ -668,6 +668,10 @@ bt_gibbs_genotypes = _sig("bt_gibbs_genotypes", [vp, vp, C.POINTER(vp), u64p])
 bt_gibbs_trace_enable = _sig("bt_gibbs_trace_enable", [vp, C.c_uint32])
 bt_gibbs_trace_fetch = _sig("bt_gibbs_trace_fetch", [vp, vp, C.c_uint64, u64p])
 bt_gibbs_posterior_summary = _sig("bt_gibbs_posterior_summary", [vp, vp])
+bt_gibbs_timeline_enable = _sig("bt_gibbs_timeline_enable", [vp, C.c_uint32])
+bt_gibbs_timeline_sizes = _sig("bt_gibbs_timeline_sizes", [vp, u64p, u32p, u32p, u32p])
+bt_gibbs_timeline_fetch = _sig("bt_gibbs_timeline_fetch", [vp, vp, C.c_uint64, u64p])
+bt_gibbs_timeline_summary = _sig("bt_gibbs_timeline_summary", [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp])
 bt_gibbs_device_bytes = _sig("bt_gibbs_device_bytes", [vp, u64p])
 bt_gibbs_source_create = _sig("bt_gibbs_source_create", [vp, C.c_uint32, vp, C.POINTER(vp)])
 bt_gibbs_source_create_from_paths = _sig("bt_gibbs_source_create_from_paths", [vp, C.c_uint32, vp, vp, C.POINTER(vp)])
@@ -688,6 +692,26 @@ bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uin
 bt_diag_kmer_set_order_staged = _sig("bt_diag_kmer_set_order_staged", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
 bt_kmer_set_orders = _sig("bt_kmer_set_orders", [vp, vp, vp, C.c_uint32, C.c_uint, C.c_uint64, C.c_uint32, vp, vp, vp])
 bt_paths_multigroup_info = _sig("bt_paths_multigroup_info", [vp, vp])
+
+
+# include/btgpu.h: bt_gibbs_timeline_record (48 bytes) and bt_gibbs_timeline_summary_t
+TIMELINE_RECORD = np.dtype([("start_tick", np.uint64), ("end_tick", np.uint64), ("hw_id", np.uint32), ("xcc_id", np.uint32), ("tile", np.uint32), ("wave", np.uint32),
+                            ("launch", np.uint32), ("launch_class", np.uint16), ("kernel", np.uint8), ("op", np.uint8), ("groups", np.uint32), ("lds_bytes", np.uint32)])
+assert TIMELINE_RECORD.itemsize == 48
+TIMELINE_KERNELS = ("general", "hot", "simple", "single")   # bt_gibbs_timeline_record::kernel
+_TIMELINE_SUMMARY_FIELDS = ("records", "unfinished", "first_start", "last_end", "busy_ticks", "peak_live", "median_end", "idle_after_median_ticks", "last_record")
+
+
+def timeline_summary(records, launch=None, launch_class=None):
+    """bt_gibbs_timeline_summary (host only, exact integer ticks) of a TIMELINE_RECORD array -> dict; last_record is None when no record is selected"""
+    records = np.ascontiguousarray(records, TIMELINE_RECORD)
+    out = np.zeros(len(_TIMELINE_SUMMARY_FIELDS), np.uint64)
+    check(bt_gibbs_timeline_summary(_np_ptr(records) if len(records) else None, len(records), 0xFFFFFFFF if launch is None else int(launch),
+                                    0xFFFFFFFF if launch_class is None else int(launch_class), _np_ptr(out)))
+    d = {k: int(v) for k, v in zip(_TIMELINE_SUMMARY_FIELDS, out)}
+    if d["last_record"] == 0xFFFFFFFFFFFFFFFF:
+        d["last_record"] = None
+    return d
 
 
 class MultigroupStats(C.Structure):   # include/btgpu.h: bt_multigroup_stats
@@ -1043,6 +1067,24 @@ class Gibbs:
         b = C.c_uint64()
         check(bt_gibbs_device_bytes(self.h, C.byref(b)))
         return b.value
+
+    def timeline_enable(self, n):
+        """bt_gibbs_timeline_enable: room for the wavefront records of n sampling launches (0: off)"""
+        check(bt_gibbs_timeline_enable(self.h, n))
+
+    def timeline_sizes(self):
+        """-> (records, launches, dropped, tick_khz)"""
+        r, l, d, k = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(bt_gibbs_timeline_sizes(self.h, C.byref(r), C.byref(l), C.byref(d), C.byref(k)))
+        return r.value, l.value, d.value, k.value
+
+    def timeline(self):
+        """bt_gibbs_timeline_fetch -> (TIMELINE_RECORD array, tick_khz, dropped)"""
+        n, _, dropped, khz = self.timeline_sizes()
+        rec = np.zeros(n, TIMELINE_RECORD)
+        got = C.c_uint64()
+        check(bt_gibbs_timeline_fetch(self.h, _np_ptr(rec) if n else None, n, C.byref(got)))
+        return rec[: got.value], khz, dropped
 
     def trace_enable(self, n):
         check(bt_gibbs_trace_enable(self.h, n))

@@ -709,8 +709,49 @@ int bt_gibbs_posterior_summary(bt_gibbs *g, uint32_t *d_out);
  * h_trace[(sweep*C + c)*S + s] = h1 | h2 << 16.  Pass max_sweeps = 0 to switch tracing off. */
 int bt_gibbs_trace_enable(bt_gibbs *g, uint32_t max_sweeps);
 int bt_gibbs_trace_fetch(bt_gibbs *g, uint32_t *h_trace, uint64_t max_words, uint64_t *num_sweeps_recorded);
-/* device bytes held by this batch (state + inputs) */
+/* device bytes held by this batch (state + inputs + the timeline's records while it is on) */
 int bt_gibbs_device_bytes(bt_gibbs *g, uint64_t *bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * Launch timeline (diagnostics, opt-in): when every wavefront of a sampling launch started and ended, and where it ran.
+ * While a timeline is on and has room, a launch of bt_gibbs_run / bt_gibbs_sweep / bt_gibbs_init_chain runs the STAMPED sibling of each
+ * sampling kernel (gibbs_*_kernel_tl): the same body between two reads of the wall clock, lane 0 of every wavefront writing one record
+ * into a buffer nothing else reads.  With the timeline off (the default) no stamp executes and the launches are what they always were.
+ * The noise tally, the fill kernels and the launches of a noise chain (bt_gibbs_noise_chain_begin .. _end) are never stamped.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bt_gibbs_timeline_record {     /* 48 bytes */
+    uint64_t start_tick, end_tick;   /* wall_clock64(); end_tick 0: the wavefront never reached its end stamp */
+    uint32_t hw_id, xcc_id;          /* raw HW_ID / XCC_ID registers, undecoded */
+    uint32_t tile, wave;             /* tile of the sampler, wavefront within the tile */
+    uint32_t launch;                 /* 0-based, counted over recorded launches since enable */
+    uint16_t launch_class;           /* index of the launch class (hungriest first, the two-haplotype class last) */
+    uint8_t kernel;                  /* 0 general, 1 hot, 2 simple, 3 single */
+    uint8_t op;                      /* 0 bt_gibbs_run, 1 bt_gibbs_init_chain, 2 bt_gibbs_sweep */
+    uint32_t groups;                 /* groups the tile holds, lockstep copies not counted */
+    uint32_t lds_bytes;              /* the tile's own LDS need */
+} bt_gibbs_timeline_record;
+typedef struct bt_gibbs_timeline_summary_t {
+    uint64_t records, unfinished;    /* selected records with / without an end stamp; everything below is over the former */
+    uint64_t first_start, last_end;
+    uint64_t busy_ticks;             /* sum of (end - start) */
+    uint64_t peak_live;              /* max over t of live(t), live(t) = records with start <= t < end */
+    uint64_t median_end;             /* end tick of the ceil(records / 2)-th record in ascending end order */
+    uint64_t idle_after_median_ticks;/* sum over the ticks t of [median_end, last_end) of (peak_live - live(t)) */
+    uint64_t last_record;            /* lowest index among the records with end = last_end (~0: no record) */
+} bt_gibbs_timeline_summary_t;
+/* room for max_launches launches (x the wavefronts of one launch over all launch classes), zero-filled; counters reset.  0: off, buffer released.
+ * Each launch of a sampling operation takes one slot while slots remain (BT_GIBBS_STEPWISE: every launch of a bt_gibbs_run); later ones
+ * run unstamped and are counted in `dropped`. */
+int bt_gibbs_timeline_enable(bt_gibbs *g, uint32_t max_launches);
+/* records bt_gibbs_timeline_fetch would hand out now, launches recorded, launches dropped, rate of the tick in kHz.  Any pointer may be NULL. */
+int bt_gibbs_timeline_sizes(bt_gibbs *g, uint64_t *records, uint32_t *launches, uint32_t *dropped, uint32_t *tick_khz);
+/* waits for the sampler's stream, then h_out[0 .. *n): the recorded launches in order, within a launch the classes in order, within a class the
+ * wavefronts in slot order (slot = blockIdx.x * wavefronts per workgroup + wavefront of the workgroup; the empty slots of a packed launch are left out).
+ * tile is what the wavefront reported, checked against the host's plan for its slot: a difference is an error, never a guess.  A capacity that is too
+ * small is an error and nothing is written.  With the timeline off *n = 0. */
+int bt_gibbs_timeline_fetch(bt_gibbs *g, bt_gibbs_timeline_record *h_out, uint64_t capacity, uint64_t *n);
+/* host only, no GPU, exact (integer ticks): the summary of the records with the given launch and launch class (~0u: all) */
+int bt_gibbs_timeline_summary(const bt_gibbs_timeline_record *r, uint64_t n, uint32_t launch, uint32_t launch_class, bt_gibbs_timeline_summary_t *out);
 
 /* ------------------------------------------------------------------------------------------
  * The noise half of CountDistribution on the device (src/bayesTyper/CountDistribution.cpp:163-200 sampleNoiseParameters /
