@@ -136,9 +136,16 @@ std::string GenotypeWriter::vcfText(const std::string &genome_filename, const st
 
 uint32_t GenotypeWriter::finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
                                   const std::string &genotype_options_header) {
+    return finalise(output_prefix, gzip_output, genome_filename, graph_options_header, genotype_options_header, GzWriter());
+}
+
+uint32_t GenotypeWriter::finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
+                                  const std::string &genotype_options_header, const GzWriter &gz_writer) {
     const std::string text = vcfText(genome_filename, graph_options_header, genotype_options_header);
     const std::string filename = output_prefix + (gzip_output ? ".vcf.gz" : ".vcf");
-    if (gzip_output) {
+    if (gzip_output && gz_writer) {
+        gz_writer(filename, text);
+    } else if (gzip_output) {
         gzFile f = gzopen(filename.c_str(), "wb");
         if (!f) throw std::runtime_error("Unable to write file " + filename);
         const bool ok = text.empty() || gzwrite(f, text.data(), (unsigned)text.size()) == (int)text.size();

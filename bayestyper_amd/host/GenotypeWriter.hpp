@@ -4,6 +4,7 @@
 // lines sorted by contig (genome order) and position; the header names every non-decoy contig.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -55,6 +56,11 @@ class GenotypeWriter {
     std::string vcfText(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header);
     uint32_t finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
                       const std::string &genotype_options_header);
+    // the same with the .vcf.gz written by gz_writer(filename, text) instead of the single gzwrite stream (one thread, texts below 2 GiB): the device route
+    // (writeGzFileOnDevice, 64-bit sizes).  An empty gz_writer, or gzip_output false, is the call above.
+    using GzWriter = std::function<void(const std::string &filename, const std::string &text)>;
+    uint32_t finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
+                      const std::string &genotype_options_header, const GzWriter &gz_writer);
 
   private:
     GenotypedVariant formatLine(const ClusterAnnotation &where, const VariantInfo &variant_info, const char *quality_filter_stats, size_t qfs_len, const char *cover, size_t cover_len,

@@ -3,10 +3,12 @@
 #include <vector>
 #include <fstream>
 #include "Parallel.hpp"
+#include "btgpu.h"
 
 #include <zlib.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 
@@ -71,6 +73,16 @@ void writeGzFile(const std::string &filename, const std::string &content, unsign
         at += n;
     }
     if (gzclose(f) != Z_OK || !ok) throw std::runtime_error("Error while writing " + filename);
+}
+
+bool gzipOnDevice() {
+    const char *e = getenv("BT_GZIP_ON_DEVICE");
+    return e && std::strcmp(e, "1") == 0;
+}
+const char *const kGzipOnDeviceRoute = "gzip on the device (bt_gzip_save)";
+void writeGzFileOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &content, unsigned threads) {
+    if (bt_gzip_save(ctx, filename.c_str(), (const uint8_t *)content.data(), content.size(), std::max(1u, threads), nullptr) != BT_OK)
+        throw std::runtime_error(std::string("bt_gzip_save: ") + bt_last_error());
 }
 
 std::vector<uint64_t> parseKmerLines(const std::string &text, size_t begin, uint32_t k, unsigned threads) {

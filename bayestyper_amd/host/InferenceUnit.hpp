@@ -12,6 +12,8 @@
 
 #include "VariantFileParser.hpp"
 
+struct bt_ctx;   // include/btgpu.h
+
 namespace bthost {
 
 struct InferenceUnit {
@@ -29,6 +31,11 @@ struct InferenceUnit {
 
 // gzip text/binary files (the reference's boost::iostreams gzip filters)
 void writeGzFile(const std::string &filename, const std::string &content, unsigned threads = 1);   // one gzip member whatever the thread count (large contents: 4 MB pieces of one deflate stream, compressed on `threads` threads)
+// BT_GZIP_ON_DEVICE=1: the gz outputs of `cluster` (parameter_kmers.fa.gz, intercluster_regions.txt.gz) and of `genotype -z` (the VCF) are compressed on the
+// device (bt_gzip_save, include/btgpu.h): one gzip member, 64-bit sizes, bytes that do not depend on the thread count.
+bool gzipOnDevice();
+extern const char *const kGzipOnDeviceRoute;   // how the stage table names the route
+void writeGzFileOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &content, unsigned threads = 1);
 std::string readGzFile(const std::string &filename);   // also reads uncompressed files
 // The k-mers of a text of one k-mer per line from offset `begin` on (parameter_kmers.fa.gz after its header line), [lo, hi] per k-mer in the packing of
 // Nucleotide::ntToBit (symbol i in bits 2i, 2i+1); the lines are cut among `threads` threads when they all have k symbols (what the cluster stage writes).

@@ -200,7 +200,12 @@ int runCluster(int argc, char *const argv[], unsigned kmer_size) {
     std::cout << "\n\n" << stamp() << "Writing inter-cluster regions ..." << std::endl;
     const std::string intercluster_regions_dir_prefix = cluster_data_dir + "/" + intercluster_regions_file_prefix;
     variant_file_parser.sortInterclusterRegions();
-    writeGzFile(intercluster_regions_dir_prefix + ".txt.gz", variant_file_parser.interclusterRegionsText());
+    const bool gzip_on_device = gzipOnDevice();   // BT_GZIP_ON_DEVICE=1: both gz outputs through bt_gzip_save
+    if (gzip_on_device) {
+        StageScope sub(std::string("  inter-cluster regions: ") + kGzipOnDeviceRoute);
+        writeGzFileOnDevice(ctx.h, intercluster_regions_dir_prefix + ".txt.gz", variant_file_parser.interclusterRegionsText(), clampThreads(options.getUInt("threads")));
+    } else
+        writeGzFile(intercluster_regions_dir_prefix + ".txt.gz", variant_file_parser.interclusterRegionsText());
     std::cout << stamp() << "Wrote " << variant_file_parser.getInterclusterRegions().size() << " regions to " << intercluster_regions_dir_prefix << ".txt.gz\n" << std::endl;
 
     // parameter k-mers: non-path k-mers of the inter-cluster regions, a Bernoulli(fraction) sample of them (main.cpp:319-341)
@@ -227,7 +232,11 @@ int runCluster(int argc, char *const argv[], unsigned kmer_size) {
             fasta += "\n";
             if (++num_parameter_kmers == max_parameter_kmers) break;
         }
-        writeGzFile(cluster_data_dir + "/" + parameter_kmers_file_prefix + ".fa.gz", fasta, clampThreads(options.getUInt("threads")));
+        if (gzip_on_device) {
+            sub.reset(new StageScope(std::string("  parameter k-mers: ") + kGzipOnDeviceRoute));
+            writeGzFileOnDevice(ctx.h, cluster_data_dir + "/" + parameter_kmers_file_prefix + ".fa.gz", fasta, clampThreads(options.getUInt("threads")));
+        } else
+            writeGzFile(cluster_data_dir + "/" + parameter_kmers_file_prefix + ".fa.gz", fasta, clampThreads(options.getUInt("threads")));
     }
     std::cout << stamp() << "Wrote " << num_parameter_kmers << " kmers to " << cluster_data_dir << "/" << parameter_kmers_file_prefix << ".fa.gz" << std::endl;
 
@@ -813,8 +822,17 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         return 0;
     }
 
-    st.reset(new StageScope("write VCF (sort + output)"));
-    const uint32_t num_genotyped_variants = genotype_writer.finalise(output_prefix, options.getBool("gzip-output"), options.getString("genome-file"), unit.cluster_options_header, options.getHeader());
+    // BT_GZIP_ON_DEVICE=1 with -z: the .vcf.gz goes through bt_gzip_save on this rank's context, and the stage's row says so (without -z the switch does nothing)
+    const bool gzip_on_device = options.getBool("gzip-output") && gzipOnDevice();
+    st.reset(new StageScope(gzip_on_device ? std::string("write VCF (sort + output), ") + kGzipOnDeviceRoute : std::string("write VCF (sort + output)")));
+    GenotypeWriter::GzWriter gz_writer;
+    if (gzip_on_device) {
+        const unsigned gz_threads = clampThreads(options.getUInt("threads"));
+        bt_ctx *gz_ctx = ctx.h;
+        gz_writer = [gz_ctx, gz_threads](const std::string &filename, const std::string &text) { writeGzFileOnDevice(gz_ctx, filename, text, gz_threads); };
+    }
+    const uint32_t num_genotyped_variants =
+        genotype_writer.finalise(output_prefix, options.getBool("gzip-output"), options.getString("genome-file"), unit.cluster_options_header, options.getHeader(), gz_writer);
     std::cout << "\n" << stamp() << "Out of " << unit.num_variants << " variants:\n" << std::endl;
     std::cout << "\t- " << num_genotyped_variants << " were genotyped" << std::endl;
     std::cout << "\t- " << unit.num_variants - num_genotyped_variants << " were skipped (unsupported)" << std::endl;

@@ -951,6 +951,63 @@ def genotype_text(ctx, d_words, num_words):
         d_index.free()
 
 
+class DeflateStats(C.Structure):   # include/btgpu.h: bt_deflate_stats
+    _fields_ = [(n, C.c_uint64) for n in ("pieces", "stored_pieces", "literals", "matches", "matched_bytes", "bytes_in", "bytes_out")] + [
+        (n, C.c_double) for n in ("seconds_h2d", "seconds_kernels", "seconds_d2h", "seconds_host")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+bt_deflate_bound = _sig("bt_deflate_bound", [C.c_uint64, u64p])
+bt_deflate = _sig("bt_deflate", [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, u64p, C.POINTER(DeflateStats)])
+bt_gzip_save = _sig("bt_gzip_save", [vp, C.c_char_p, vp, C.c_uint64, C.c_uint32, C.POINTER(DeflateStats)])
+bt_diag_deflate = _sig("bt_diag_deflate", [vp, C.c_uint64, C.c_int, vp, C.c_uint64, u64p, C.POINTER(DeflateStats)])
+
+
+def _bytes_array(data):
+    return np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+
+
+def deflate_bound(n):
+    """bt_deflate_bound: the largest raw deflate stream bt_deflate / bt_diag_deflate produce for n bytes"""
+    cap = C.c_uint64()
+    check(bt_deflate_bound(n, C.byref(cap)))
+    return cap.value
+
+
+def diag_deflate(data, last=True):
+    """bt_diag_deflate: the device's compressor run on the host (a team of one thread) -> (raw deflate stream as bytes, stats dictionary)"""
+    a = _bytes_array(data)
+    out, n, st = np.zeros(deflate_bound(a.size), np.uint8), C.c_uint64(), DeflateStats()
+    check(bt_diag_deflate(_np_ptr(a) if a.size else None, a.size, int(bool(last)), _np_ptr(out), out.size, C.byref(n), C.byref(st)))
+    return out[:n.value].tobytes(), st.as_dict()
+
+
+def deflate(ctx, data, last=True):
+    """bt_deflate over a host buffer: uploaded, compressed on the device, downloaded -> (raw deflate stream as bytes, stats dictionary)"""
+    a = _bytes_array(data)
+    cap = deflate_bound(a.size)
+    d_in, d_out = DeviceBuffer(ctx, a.size), DeviceBuffer(ctx, cap)
+    try:
+        if a.size:
+            d_in.upload(a)
+        n, st = C.c_uint64(), DeflateStats()
+        check(bt_deflate(ctx.h, d_in.ptr if a.size else None, a.size, int(bool(last)), d_out.ptr, cap, C.byref(n), C.byref(st)))
+        return d_out.download(np.uint8, n.value).tobytes(), st.as_dict()
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+def gzip_save(ctx, path, data, threads=1):
+    """bt_gzip_save: data -> the file `path`, one gzip member compressed on the device -> stats dictionary"""
+    a = _bytes_array(data)
+    st = DeflateStats()
+    check(bt_gzip_save(ctx.h, os.fsencode(path), _np_ptr(a) if a.size else None, a.size, threads, C.byref(st)))
+    return st.as_dict()
+
+
 def parse_genotype_text(text, index):
     """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
     dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer

@@ -817,6 +817,35 @@ int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial
  * must stay below 2^32 - 2, as on the device route: an error otherwise. */
 int bt_diag_kmer_set_order_staged(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets);
 
+/* ------------------------------------------------------------------------------------------
+ * Deflate on the device (RFC 1951) and gzip files written through it (opt-in: BT_GZIP_ON_DEVICE=1 in the executables).
+ * Replaces the gzip stream of GenotypeWriter.cpp (the reference's bgzip/boost gzip_compressor over the VCF text; here GenotypeWriter::finalise's single
+ * gzwrite) and the gz outputs of main.cpp (parameter_kmers.fa.gz, intercluster_regions.txt.gz; here writeGzFile), which run on host threads.
+ * The input is cut into pieces of 64 KiB; no piece carries history from the one before it; each becomes a dynamic-Huffman block (or stored blocks when
+ * those are not larger) closed on a byte boundary by an empty stored block, so the pieces laid end to end are ONE raw deflate stream and the bytes are a
+ * function of the content alone (bayestyper_amd/csrc/bt_deflate.hpp holds the compressor, one text for the kernels and the host).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bt_deflate_stats {
+    uint64_t pieces, stored_pieces;            /* pieces of the content; those written as stored blocks */
+    uint64_t literals, matches, matched_bytes; /* tokens of all pieces (the stored ones included); literals + matched_bytes = bytes_in */
+    uint64_t bytes_in, bytes_out;              /* bytes_out: the deflate stream (bt_gzip_save: without the 18 bytes of header and trailer) */
+    double seconds_h2d, seconds_kernels, seconds_d2h, seconds_host;   /* bt_gzip_save only: device time of the copies in, the kernels and the copies out
+                                                                         (event pairs, summed over the slabs; they overlap), host time of CRC-32 + file writes */
+} bt_deflate_stats;
+/* the largest stream bt_deflate / bt_diag_deflate can produce for n bytes: 65551 per full piece, len + 10 (len + 5 for an empty content) for the rest */
+int bt_deflate_bound(uint64_t n, uint64_t *capacity);
+/* d_in [n] -> d_out: a raw deflate stream, ended by a final block when `last` is non-zero (otherwise it ends on a byte boundary and another call's
+ * output continues it).  capacity must be at least bt_deflate_bound(n): a smaller one is an error, checked before anything is launched, and nothing is
+ * written past it.  *h_out_bytes = the stream's length; stats may be NULL.  Complete on return. */
+int bt_deflate(bt_ctx *ctx, const uint8_t *d_in, uint64_t n, int last, uint8_t *d_out, uint64_t capacity, uint64_t *h_out_bytes, bt_deflate_stats *stats);
+/* h_data [n] -> the file `path` as ONE gzip member: writeGzFile's 10-byte header, the stream, CRC-32 and n mod 2^32.  The content goes through the device
+ * in slabs (32 MiB; BT_GZIP_SLAB_BYTES overrides, rounded up to a multiple of the piece size) staged in pinned memory: copy in, kernels and copy out of
+ * slab i run while the host computes slab i's CRC-32 (on `threads` threads, combined as crc32_combine does) and writes slab i - 1.  Written as
+ * <path>.tmp and renamed when complete.  The bytes do not depend on the slab size or the thread count.  64-bit sizes throughout. */
+int bt_gzip_save(bt_ctx *ctx, const char *path, const uint8_t *h_data, uint64_t n, uint32_t threads, bt_deflate_stats *stats);
+/* Host-side run of bt_deflate (the same __host__ __device__ code with a team of one thread, no GPU): the same bytes, the same capacity rule. */
+int bt_diag_deflate(const uint8_t *h_in, uint64_t n, int last, uint8_t *h_out, uint64_t capacity, uint64_t *out_bytes, bt_deflate_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
