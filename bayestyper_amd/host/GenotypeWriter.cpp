@@ -121,15 +121,21 @@ std::string GenotypeWriter::generateHeader(const std::string &genome_filename, c
     return h.str();
 }
 
-std::string GenotypeWriter::vcfText(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header) {
+std::string GenotypeWriter::vcfText(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header, LineTable *line_table) {
     std::ostringstream os;
     os << generateHeader(genome_filename, graph_options_header, genotype_options_header);
+    if (line_table) *line_table = LineTable();
     for (size_t c = 0; c < chromosomes.size(); c++) {   // contigs in genome order, variants by position (:452-470)
         auto it = genotyped_variants.find(chromosomes.name(c));
         if (it == genotyped_variants.end()) continue;
         std::sort(it->second.begin(), it->second.end(), [](const GenotypedVariant &a, const GenotypedVariant &b) { return a.position < b.position; });
-        for (auto &gv : it->second)
-            os << it->first << "\t" << gv.position << "\t" << gv.variant_id << "\t" << chromosomes.sequence(c).substr(gv.position - 1, gv.max_ref_length) << "\t" << gv.genotypes << "\n";
+        if (line_table && !it->second.empty()) line_table->contigs.push_back(it->first);
+        for (auto &gv : it->second) {
+            const uint64_t line_begin = line_table ? (uint64_t)os.tellp() : 0;
+            const std::string ref = chromosomes.sequence(c).substr(gv.position - 1, gv.max_ref_length);
+            os << it->first << "\t" << gv.position << "\t" << gv.variant_id << "\t" << ref << "\t" << gv.genotypes << "\n";
+            if (line_table) line_table->lines.push_back(TabixLine{(uint32_t)(line_table->contigs.size() - 1), gv.position, ref.size(), line_begin, (uint64_t)os.tellp() - line_begin});
+        }
     }
     return os.str();
 }
@@ -155,6 +161,16 @@ uint32_t GenotypeWriter::finalise(const std::string &output_prefix, bool gzip_ou
         if (!f.is_open()) throw std::runtime_error("Unable to write file " + filename);
         f << text;
     }
+    uint32_t n = 0;
+    for (auto &c : genotyped_variants) n += (uint32_t)c.second.size();
+    return n;
+}
+
+uint32_t GenotypeWriter::finalise(const std::string &output_prefix, const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header,
+                                  const IndexedGzWriter &indexed_writer) {
+    LineTable line_table;
+    const std::string text = vcfText(genome_filename, graph_options_header, genotype_options_header, &line_table);
+    indexed_writer(output_prefix + ".vcf.gz", text, line_table);
     uint32_t n = 0;
     for (auto &c : genotyped_variants) n += (uint32_t)c.second.size();
     return n;

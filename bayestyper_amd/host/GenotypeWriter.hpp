@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "Genotypes.hpp"
+#include "TabixIndex.hpp"
 #include "VariantFileParser.hpp"
 
 namespace bthost {
@@ -53,7 +54,13 @@ class GenotypeWriter {
     void append(const std::string &chrom_name, GenotypedVariant &&variant) { genotyped_variants[chrom_name].push_back(std::move(variant)); }
     std::string generateHeader(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header) const;   // :494-551
     // header + sorted lines (finalise :352-492); the file variant writes <output_prefix>.vcf or .vcf.gz and returns the number of variants
-    std::string vcfText(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header);
+    // line_table (optional): what a tabix index is built from (TabixIndex.hpp) — the names of the contigs that have lines, in the text's order, and per data
+    // line its contig, POS, len(REF), first byte in the text and length.  The text is the same with or without it.
+    struct LineTable {
+        std::vector<std::string> contigs;
+        std::vector<TabixLine> lines;
+    };
+    std::string vcfText(const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header, LineTable *line_table = nullptr);
     uint32_t finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
                       const std::string &genotype_options_header);
     // the same with the .vcf.gz written by gz_writer(filename, text) instead of the single gzwrite stream (one thread, texts below 2 GiB): the device route
@@ -61,6 +68,10 @@ class GenotypeWriter {
     using GzWriter = std::function<void(const std::string &filename, const std::string &text)>;
     uint32_t finalise(const std::string &output_prefix, bool gzip_output, const std::string &genome_filename, const std::string &graph_options_header,
                       const std::string &genotype_options_header, const GzWriter &gz_writer);
+    // the same with the .vcf.gz and its index written by indexed_writer(filename, text, line_table): the BGZF route (writeBgzfVcfOnDevice)
+    using IndexedGzWriter = std::function<void(const std::string &filename, const std::string &text, const LineTable &line_table)>;
+    uint32_t finalise(const std::string &output_prefix, const std::string &genome_filename, const std::string &graph_options_header, const std::string &genotype_options_header,
+                      const IndexedGzWriter &indexed_writer);
 
   private:
     GenotypedVariant formatLine(const ClusterAnnotation &where, const VariantInfo &variant_info, const char *quality_filter_stats, size_t qfs_len, const char *cover, size_t cover_len,

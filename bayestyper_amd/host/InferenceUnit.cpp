@@ -8,6 +8,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -83,6 +84,29 @@ const char *const kGzipOnDeviceRoute = "gzip on the device (bt_gzip_save)";
 void writeGzFileOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &content, unsigned threads) {
     if (bt_gzip_save(ctx, filename.c_str(), (const uint8_t *)content.data(), content.size(), std::max(1u, threads), nullptr) != BT_OK)
         throw std::runtime_error(std::string("bt_gzip_save: ") + bt_last_error());
+}
+
+bool vcfBgzf() {
+    const char *e = getenv("BT_VCF_BGZF");
+    return e && std::strcmp(e, "1") == 0;
+}
+const char *const kBgzfOnDeviceRoute = "BGZF on the device (bt_bgzf_save)";
+std::string writeBgzfVcfOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &text, const std::vector<std::string> &contigs, const std::vector<TabixLine> &lines,
+                                 unsigned threads) {
+    uint64_t capacity = 0, blocks = 0;
+    if (bt_bgzf_bound(text.size(), &capacity, &blocks) != BT_OK) throw std::runtime_error(std::string("bt_bgzf_bound: ") + bt_last_error());
+    std::vector<uint64_t> block_offsets(blocks + 1);
+    if (bt_bgzf_save(ctx, filename.c_str(), (const uint8_t *)text.data(), text.size(), std::max(1u, threads), block_offsets.data(), block_offsets.size(), nullptr) != BT_OK)
+        throw std::runtime_error(std::string("bt_bgzf_save: ") + bt_last_error());
+    std::string tbi, warning;
+    const std::string index_filename = filename + ".tbi";
+    if (!buildTabixIndex(contigs, block_offsets, lines, tbi, warning)) {
+        std::remove(index_filename.c_str());   // (an index of an earlier run would not belong to this file)
+        return warning;
+    }
+    if (bt_bgzf_save(ctx, index_filename.c_str(), (const uint8_t *)tbi.data(), tbi.size(), 1, nullptr, 0, nullptr) != BT_OK)
+        throw std::runtime_error(std::string("bt_bgzf_save: ") + bt_last_error());
+    return std::string();
 }
 
 std::vector<uint64_t> parseKmerLines(const std::string &text, size_t begin, uint32_t k, unsigned threads) {

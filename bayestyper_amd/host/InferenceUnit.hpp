@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "TabixIndex.hpp"
 #include "VariantFileParser.hpp"
 
 struct bt_ctx;   // include/btgpu.h
@@ -36,6 +37,13 @@ void writeGzFile(const std::string &filename, const std::string &content, unsign
 bool gzipOnDevice();
 extern const char *const kGzipOnDeviceRoute;   // how the stage table names the route
 void writeGzFileOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &content, unsigned threads = 1);
+// BT_VCF_BGZF=1 with `genotype -z`: the VCF is written as BGZF on the device (bt_bgzf_save) — the blocked gzip that tabix and bcftools read in regions — and
+// its tabix index (TabixIndex.hpp, itself BGZF) as <filename>.tbi.  When no index can be built (a coordinate of 2^29 or above) the VCF is written, the
+// reason is returned and no .tbi is written; otherwise the result is empty.
+bool vcfBgzf();
+extern const char *const kBgzfOnDeviceRoute;   // how the stage table names the route
+std::string writeBgzfVcfOnDevice(bt_ctx *ctx, const std::string &filename, const std::string &text, const std::vector<std::string> &contigs, const std::vector<TabixLine> &lines,
+                                 unsigned threads = 1);
 std::string readGzFile(const std::string &filename);   // also reads uncompressed files
 // The k-mers of a text of one k-mer per line from offset `begin` on (parameter_kmers.fa.gz after its header line), [lo, hi] per k-mer in the packing of
 // Nucleotide::ntToBit (symbol i in bits 2i, 2i+1); the lines are cut among `threads` threads when they all have k symbols (what the cluster stage writes).

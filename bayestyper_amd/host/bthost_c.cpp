@@ -18,6 +18,7 @@
 #include "KmerCounter.hpp"
 #include "Sample.hpp"
 #include "TableCheckpoint.hpp"
+#include "TabixIndex.hpp"
 #include "VariantClusterGraph.hpp"
 #include "VariantFileParser.hpp"
 
@@ -700,6 +701,14 @@ int bth_writer_add_cluster(void *h, uint32_t group, uint32_t vertex, unsigned S,
 unsigned long long bth_writer_text(void *h, const char *genome_filename, const char *graph_options_header, const char *genotype_options_header, char *buf, unsigned long long cap) {
     return copy_out(((WriterHandle *)h)->writer->vcfText(genome_filename, graph_options_header, genotype_options_header), buf, cap);
 }
+// the line table of that text (GenotypeWriter::LineTable): one row "<contig name>\t<contig index>\t<POS>\t<len(REF)>\t<offset>\t<length>" per data line
+unsigned long long bth_writer_line_table(void *h, const char *genome_filename, const char *graph_options_header, const char *genotype_options_header, char *buf, unsigned long long cap) {
+    GenotypeWriter::LineTable t;
+    ((WriterHandle *)h)->writer->vcfText(genome_filename, graph_options_header, genotype_options_header, &t);
+    std::ostringstream os;
+    for (const TabixLine &l : t.lines) os << t.contigs[l.contig] << "\t" << l.contig << "\t" << l.pos << "\t" << l.ref_length << "\t" << l.offset << "\t" << l.length << "\n";
+    return copy_out(os.str(), buf, cap);
+}
 // writes <output_prefix>.vcf[.gz]; returns the number of genotyped variants or -1
 long long bth_writer_finalise(void *h, const char *output_prefix, int gzip_output, const char *genome_filename, const char *graph_options_header,
                               const char *genotype_options_header, char *err, unsigned err_len) {
@@ -945,5 +954,26 @@ unsigned long long bth_chromosome_ploidy(void *stage, const char *ploidy_filenam
         return 0;
     }
 }
+
+// buildTabixIndex (TabixIndex.hpp): contig_names tab-separated (an empty string: none), block_offsets [num_offsets], lines [5 * num_lines] = contig index,
+// POS, len(REF), offset, length per line.  Returns the size of the index (copied into buf when cap is large enough), or -1 with the warning in err.
+long long bth_tabix_index(const char *contig_names, const unsigned long long *block_offsets, unsigned long long num_offsets, const unsigned long long *lines, unsigned long long num_lines,
+                          char *buf, unsigned long long cap, char *err, unsigned err_len) {
+    std::vector<std::string> contigs;
+    for (const char *p = contig_names; *p;) {
+        const char *e = std::strchr(p, '\t');
+        contigs.emplace_back(p, e ? (size_t)(e - p) : std::strlen(p));
+        p = e ? e + 1 : p + std::strlen(p);
+    }
+    std::vector<TabixLine> table;
+    for (unsigned long long i = 0; i < num_lines; i++) table.push_back(TabixLine{(uint32_t)lines[5 * i], lines[5 * i + 1], lines[5 * i + 2], lines[5 * i + 3], lines[5 * i + 4]});
+    std::string tbi, warning;
+    if (!buildTabixIndex(contigs, std::vector<uint64_t>(block_offsets, block_offsets + num_offsets), table, tbi, warning)) {
+        stage_error(std::runtime_error(warning), err, err_len);
+        return -1;
+    }
+    return (long long)copy_out(tbi, buf, cap);
+}
+uint32_t bth_tabix_reg2bin(unsigned long long beg, unsigned long long end) { return tabixReg2bin(beg, end); }
 
 }  // extern "C"

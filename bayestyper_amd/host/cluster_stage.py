@@ -116,6 +116,8 @@ dll.bth_writer_free.argtypes = [vp]
 dll.bth_writer_add_cluster.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp, C.c_ulonglong, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, C.c_char_p, C.c_uint]
 dll.bth_writer_text.restype = C.c_ulonglong
 dll.bth_writer_text.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ulonglong]
+dll.bth_writer_line_table.restype = C.c_ulonglong
+dll.bth_writer_line_table.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ulonglong]
 dll.bth_writer_finalise.restype = C.c_longlong
 dll.bth_writer_finalise.argtypes = [vp, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint]
 
@@ -149,6 +151,22 @@ class GenotypeWriter:
         buf = C.create_string_buffer(int(n) + 1)
         dll.bth_writer_text(self.h, *args, buf, n)
         return buf.raw[:n].decode()
+
+    def line_table(self, genome_filename="genome.fa", graph_options_header="", genotype_options_header=""):
+        """the line table of text() (GenotypeWriter::LineTable, what the tabix index is built from) -> (the names of the contigs that have lines, in the text's
+        order; rows (contig index, POS, len(REF), offset of the line's first byte in the text, length of the line))"""
+        args = [genome_filename.encode(), graph_options_header.encode(), genotype_options_header.encode()]
+        n = dll.bth_writer_line_table(self.h, *args, None, 0)
+        buf = C.create_string_buffer(int(n) + 1)
+        dll.bth_writer_line_table(self.h, *args, buf, n)
+        contigs, rows = [], []
+        for row in buf.raw[:n].decode().split("\n")[:-1]:
+            f = row.split("\t")
+            if int(f[1]) == len(contigs):
+                contigs.append(f[0])
+            assert contigs[int(f[1])] == f[0]
+            rows.append(tuple(int(x) for x in f[1:]))
+        return contigs, rows
 
     def finalise(self, output_prefix, gzip_output=False, genome_filename="genome.fa", graph_options_header="", genotype_options_header=""):
         n = dll.bth_writer_finalise(self.h, output_prefix.encode(), int(gzip_output), genome_filename.encode(), graph_options_header.encode(), genotype_options_header.encode(),

@@ -822,17 +822,29 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         return 0;
     }
 
-    // BT_GZIP_ON_DEVICE=1 with -z: the .vcf.gz goes through bt_gzip_save on this rank's context, and the stage's row says so (without -z the switch does nothing)
-    const bool gzip_on_device = options.getBool("gzip-output") && gzipOnDevice();
-    st.reset(new StageScope(gzip_on_device ? std::string("write VCF (sort + output), ") + kGzipOnDeviceRoute : std::string("write VCF (sort + output)")));
-    GenotypeWriter::GzWriter gz_writer;
-    if (gzip_on_device) {
-        const unsigned gz_threads = clampThreads(options.getUInt("threads"));
-        bt_ctx *gz_ctx = ctx.h;
-        gz_writer = [gz_ctx, gz_threads](const std::string &filename, const std::string &text) { writeGzFileOnDevice(gz_ctx, filename, text, gz_threads); };
+    // BT_GZIP_ON_DEVICE=1 with -z: the .vcf.gz goes through bt_gzip_save on this rank's context, and the stage's row says so (without -z the switch does nothing).
+    // BT_VCF_BGZF=1 with -z: the .vcf.gz is BGZF written through bt_bgzf_save, with its tabix index beside it; it takes precedence over the switch above.
+    const bool vcf_bgzf = options.getBool("gzip-output") && vcfBgzf();
+    const bool gzip_on_device = options.getBool("gzip-output") && !vcf_bgzf && gzipOnDevice();
+    st.reset(new StageScope(vcf_bgzf         ? std::string("write VCF (sort + output), ") + kBgzfOnDeviceRoute
+                            : gzip_on_device ? std::string("write VCF (sort + output), ") + kGzipOnDeviceRoute
+                                             : std::string("write VCF (sort + output)")));
+    const unsigned gz_threads = clampThreads(options.getUInt("threads"));
+    bt_ctx *gz_ctx = ctx.h;
+    uint32_t num_genotyped_variants = 0;
+    if (vcf_bgzf) {
+        num_genotyped_variants = genotype_writer.finalise(
+            output_prefix, options.getString("genome-file"), unit.cluster_options_header, options.getHeader(),
+            [gz_ctx, gz_threads](const std::string &filename, const std::string &text, const GenotypeWriter::LineTable &table) {
+                const std::string warning = writeBgzfVcfOnDevice(gz_ctx, filename, text, table.contigs, table.lines, gz_threads);
+                if (!warning.empty()) std::cerr << "\nWARNING: no tabix index written for " << filename << ": " << warning << "\n" << std::endl;
+            });
+    } else {
+        GenotypeWriter::GzWriter gz_writer;
+        if (gzip_on_device) gz_writer = [gz_ctx, gz_threads](const std::string &filename, const std::string &text) { writeGzFileOnDevice(gz_ctx, filename, text, gz_threads); };
+        num_genotyped_variants =
+            genotype_writer.finalise(output_prefix, options.getBool("gzip-output"), options.getString("genome-file"), unit.cluster_options_header, options.getHeader(), gz_writer);
     }
-    const uint32_t num_genotyped_variants =
-        genotype_writer.finalise(output_prefix, options.getBool("gzip-output"), options.getString("genome-file"), unit.cluster_options_header, options.getHeader(), gz_writer);
     std::cout << "\n" << stamp() << "Out of " << unit.num_variants << " variants:\n" << std::endl;
     std::cout << "\t- " << num_genotyped_variants << " were genotyped" << std::endl;
     std::cout << "\t- " << unit.num_variants - num_genotyped_variants << " were skipped (unsupported)" << std::endl;

@@ -1008,6 +1008,61 @@ def gzip_save(ctx, path, data, threads=1):
     return st.as_dict()
 
 
+bt_bgzf_bound = _sig("bt_bgzf_bound", [C.c_uint64, u64p, u64p])
+bt_bgzf = _sig("bt_bgzf", [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, u64p, vp, C.POINTER(DeflateStats)])
+bt_bgzf_save = _sig("bt_bgzf_save", [vp, C.c_char_p, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(DeflateStats)])
+bt_diag_bgzf = _sig("bt_diag_bgzf", [vp, C.c_uint64, C.c_int, vp, C.c_uint64, u64p, vp, C.POINTER(DeflateStats)])
+bt_diag_crc32 = _sig("bt_diag_crc32", [vp, C.c_uint64, C.POINTER(C.c_uint32)])
+
+
+def bgzf_bound(n):
+    """bt_bgzf_bound -> (the largest BGZF stream bt_bgzf / bt_diag_bgzf produce for n bytes, EOF block included; the number of data blocks)"""
+    cap, blocks = C.c_uint64(), C.c_uint64()
+    check(bt_bgzf_bound(n, C.byref(cap), C.byref(blocks)))
+    return cap.value, blocks.value
+
+
+def diag_bgzf(data, eof=True):
+    """bt_diag_bgzf: the device's BGZF writer run on the host (a team of one thread) -> (stream as bytes, block offsets [blocks + 1] as a list, stats)"""
+    a = _bytes_array(data)
+    cap, blocks = bgzf_bound(a.size)
+    out, offs, n, st = np.zeros(cap, np.uint8), np.zeros(blocks + 1, np.uint64), C.c_uint64(), DeflateStats()
+    check(bt_diag_bgzf(_np_ptr(a) if a.size else None, a.size, int(bool(eof)), _np_ptr(out), out.size, C.byref(n), _np_ptr(offs), C.byref(st)))
+    return out[:n.value].tobytes(), [int(o) for o in offs], st.as_dict()
+
+
+def diag_crc32(data):
+    """bt_diag_crc32: the blocks' CRC-32 routine run on the host -> zlib's crc32 of data"""
+    a = _bytes_array(data)
+    crc = C.c_uint32()
+    check(bt_diag_crc32(_np_ptr(a) if a.size else None, a.size, C.byref(crc)))
+    return crc.value
+
+
+def bgzf(ctx, data, eof=True):
+    """bt_bgzf over a host buffer: uploaded, written as BGZF on the device, downloaded -> (stream as bytes, block offsets as a list, stats)"""
+    a = _bytes_array(data)
+    cap, blocks = bgzf_bound(a.size)
+    d_in, d_out = DeviceBuffer(ctx, a.size), DeviceBuffer(ctx, cap)
+    try:
+        if a.size:
+            d_in.upload(a)
+        offs, n, st = np.zeros(blocks + 1, np.uint64), C.c_uint64(), DeflateStats()
+        check(bt_bgzf(ctx.h, d_in.ptr if a.size else None, a.size, int(bool(eof)), d_out.ptr, cap, C.byref(n), _np_ptr(offs), C.byref(st)))
+        return d_out.download(np.uint8, n.value).tobytes(), [int(o) for o in offs], st.as_dict()
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+def bgzf_save(ctx, path, data, threads=1):
+    """bt_bgzf_save: data -> the file `path`, BGZF written on the device, EOF block included -> (block offsets in the file as a list, stats)"""
+    a = _bytes_array(data)
+    offs, st = np.zeros(bgzf_bound(a.size)[1] + 1, np.uint64), DeflateStats()
+    check(bt_bgzf_save(ctx.h, os.fsencode(path), _np_ptr(a) if a.size else None, a.size, threads, _np_ptr(offs), offs.size, C.byref(st)))
+    return [int(o) for o in offs], st.as_dict()
+
+
 def parse_genotype_text(text, index):
     """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
     dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer

@@ -846,6 +846,32 @@ int bt_gzip_save(bt_ctx *ctx, const char *path, const uint8_t *h_data, uint64_t 
 /* Host-side run of bt_deflate (the same __host__ __device__ code with a team of one thread, no GPU): the same bytes, the same capacity rule. */
 int bt_diag_deflate(const uint8_t *h_in, uint64_t n, int last, uint8_t *h_out, uint64_t capacity, uint64_t *out_bytes, bt_deflate_stats *stats);
 
+/* ------------------------------------------------------------------------------------------
+ * BGZF on the device (SAM specification section 4.1: a series of self-contained gzip members of at most 64 KiB, the format tabix and bcftools index),
+ * opt-in: BT_VCF_BGZF=1 with `bayesTyper genotype -z`.  Replaces the bgzip pass a user runs over the unit's VCF before tabix / bcftools concat.
+ * The content is cut into blocks of 65280 input bytes (htslib's size; the last one shorter, none for an empty content).  A block is 18 bytes of header
+ * (1f 8b 08 04, mtime 0, XFL 0, OS ff, XLEN 6, "BC" 02 00, BSIZE = the block's size - 1), the payload — the piece compressor above with the final bit
+ * set, a complete raw deflate stream of at most 65290 bytes — then the CRC-32 of the block's input, computed by the wavefront that compressed it, and its
+ * length.  bayestyper_amd/csrc/bt_bgzf.hpp holds the block's code, one text for the kernels and the host.  bt_deflate_stats: pieces = blocks,
+ * bytes_out = the payloads without the 26 bytes of framing per block and without the EOF block.
+ * ---------------------------------------------------------------------------------------- */
+/* the largest stream for n bytes, the 28 bytes of the EOF block included (len + 36 per block), and the number of data blocks */
+int bt_bgzf_bound(uint64_t n, uint64_t *capacity, uint64_t *blocks);
+/* d_in [n] -> d_out: the data blocks, then with `eof` non-zero the canonical 28-byte EOF block (a constant, not the compressor's empty piece).
+ * h_block_offsets [blocks + 1] (may be NULL): the byte offset of every block; the last entry is the EOF block's offset, or the stream's end without one.
+ * capacity must be at least bt_bgzf_bound(n): a smaller one is an error, checked before anything is launched, and nothing is written past it.
+ * *h_out_bytes = the stream's length; stats may be NULL.  Complete on return. */
+int bt_bgzf(bt_ctx *ctx, const uint8_t *d_in, uint64_t n, int eof, uint8_t *d_out, uint64_t capacity, uint64_t *h_out_bytes, uint64_t *h_block_offsets, bt_deflate_stats *stats);
+/* h_data [n] -> the file `path` as BGZF with its EOF block: bt_gzip_save's slab pipeline with a slab that is a multiple of 65280 (default 515 blocks,
+ * about 32 MiB; BT_BGZF_SLAB_BYTES overrides, rounded up), without a host CRC (`threads` is accepted for symmetry and unused), and with
+ * h_block_offsets [blocks + 1] (may be NULL; offsets_capacity entries of room, an error when too few) relative to the file.  Written as <path>.tmp and
+ * renamed when complete.  The bytes do not depend on the slab size or on `threads`.  64-bit sizes throughout. */
+int bt_bgzf_save(bt_ctx *ctx, const char *path, const uint8_t *h_data, uint64_t n, uint32_t threads, uint64_t *h_block_offsets, uint64_t offsets_capacity, bt_deflate_stats *stats);
+/* Host-side run of bt_bgzf (the same __host__ __device__ code with a team of one thread, no GPU): the same bytes and offsets, the same capacity rule. */
+int bt_diag_bgzf(const uint8_t *h_in, uint64_t n, int eof, uint8_t *h_out, uint64_t capacity, uint64_t *out_bytes, uint64_t *h_block_offsets, bt_deflate_stats *stats);
+/* Host-side run of the blocks' CRC-32 routine: zlib's crc32 of h_in [n] (contents longer than a block: per block, joined as crc32_combine does). */
+int bt_diag_crc32(const uint8_t *h_in, uint64_t n, uint32_t *crc);
+
 #ifdef __cplusplus
 }
 #endif
