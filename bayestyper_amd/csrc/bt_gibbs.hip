@@ -961,6 +961,7 @@ inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 inline uint32_t tile_lds_bytes(const TileDesc &d) { return d.lds_all ? d.hot_bytes * d.nvm : d.hot_bytes; }
 // a cluster's [S][D] tables are dense up to 256 MB per tile (64 MB when the batch would not fit the GPU otherwise): a hashed table far
 // smaller than the set of live (sample, diplotype) pairs thrashes (256 candidates x 10 samples: 12x slower than dense)
+constexpr uint32_t kBulkSubsetDefault = 1;      // BT_GIBBS_BULK_SUBSET when the variable is not set (on: profiles/chain_start_subset.txt)
 constexpr uint32_t kMinTileWidth = 4;           // groups per wavefront of the narrowest tiles (the other lanes run copies)
 constexpr uint32_t kLightLds = 24576;            // tiles above this are "heavy" (they get fewer wavefronts per tile)
 // upper LDS bounds of the launch classes: at most four, the streams of more classes than hardware queues would run one after another
@@ -1348,6 +1349,11 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
     P.max_hvk = params->max_haplotype_variant_kmers;
     P.noise_seeding = params->noise_seeding;
     P.rate = (double)params->kmer_subsampling_rate;
+    // the chain starts of a schedule draw the k-mer subset across a group's lockstep copies (sample_kmer_subset): BT_GIBBS_BULK_SUBSET=0/1, read once here
+    {
+        const char *e = getenv("BT_GIBBS_BULK_SUBSET");
+        P.bulk_subset = e ? (atoi(e) != 0 ? 1u : 0u) : kBulkSubsetDefault;
+    }
     for (uint32_t s = 0; s < S; ++s) P.gender[s] = params->gender[s] ? 1 : 0;
 
 #define BT_TRY(x)                \
@@ -3603,6 +3609,20 @@ int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint6
             return fail("bt_diag_rng: unknown kind");
     }
     return BT_OK;
+}
+
+// n Bernoulli draws after `discard` words of a ring generator (block form), taken three ways: one rng_bernoulli call after another, rng_bernoulli_bulk's
+// host form (a team of one), and the direct-form generator as the stream's own reference — each followed by eight more words.  ahead != 0: the next block
+// is twisted ahead first where the position allows it (MtRing::twist_ahead).  h_flags: [3][n], h_tail: [3][8], h_state: [2][4] = {position, flags, ring
+// head, unread ring words} of the first two.
+int bt_diag_bulk_bernoulli(uint32_t seed, uint64_t discard, uint32_t n, double p, uint32_t ring_cap, int ahead, uint8_t *h_flags, uint32_t *h_tail, uint32_t *h_state) {
+#ifdef BT_RNG_BULK
+    if ((n && !h_flags) || !h_tail || !h_state) return fail("bt_diag_bulk_bernoulli: null argument");
+    if (ring_cap < 8 || ring_cap > 64 || (ring_cap & (ring_cap - 1u))) return fail("bt_diag_bulk_bernoulli: ring_cap must be a power of two in 8 .. 64");
+    return bulk_bernoulli_check(seed, discard, n, p, ring_cap, ahead, h_flags, h_tail, h_state), BT_OK;
+#else
+    return fail("bt_diag_bulk_bernoulli: this build has no block-form generator");
+#endif
 }
 
 }  // extern "C"

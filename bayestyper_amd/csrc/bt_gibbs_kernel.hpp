@@ -17,7 +17,7 @@ struct TraceCfg {
     uint32_t *buf;         // tile blocks of [max_sweeps][nvm][S][64]
 };
 
-__device__ BT_NOINLINE void group_init_chain(Env env, uint32_t chain, uint32_t nvert, uint32_t nsrc, uint32_t gindex) {
+__device__ BT_NOINLINE void group_init_chain(Env env, uint32_t chain, uint32_t nvert, uint32_t nsrc, uint32_t gindex, bool bulk) {
     const Tile t = make_tile(env);
     const GParams BT_CAS &P = env_params(env);
     const uint32_t gseed = P.noise_seeding ? P.seed + (gindex + 1u) * (chain + 1u) : P.seed + (gindex + 1u);
@@ -31,7 +31,7 @@ __device__ BT_NOINLINE void group_init_chain(Env env, uint32_t chain, uint32_t n
         }
         PROF_DECL;
         if (!make_vx(make_tile(ev), v).sc()[SC_CONSTRUCTED]) genotyper_construct(ev, v, gseed + c.cid());   // VariantClusterGroup.cpp:179-182
-        genotyper_reset(ev, v);
+        genotyper_reset(ev, v, bulk);
         if (swap) hot_swap(env, v, false);
     }
     // shuffleBranchOrdering (VariantClusterGroup.cpp:208-218)
@@ -295,7 +295,7 @@ __device__ __forceinline__ void gibbs_body(const TileDesc *__restrict__ tiles, u
         for (uint32_t chain = 0; chain < nchains; ++chain) {
             if (is_run) {
                 PROF_DECL;
-                group_init_chain(env, chain, nvert, nsrc, gindex);
+                group_init_chain(env, chain, nvert, nsrc, gindex, P.bulk_subset != 0);
                 PROF(15);
             }
             if constexpr (SIMPLE_ONLY) {
@@ -339,7 +339,7 @@ __device__ __forceinline__ void gibbs_body(const TileDesc *__restrict__ tiles, u
         if (!simple && (is_run || n_collect))
             for (uint32_t v = 0; v < nvert; ++v) flush_vertex(env, v);   // hot arrays: LDS when resident, else HBM (both valid)
     } else if (op == OP_INIT_CHAIN) {
-        group_init_chain(env, arg0, nvert, nsrc, gindex);
+        group_init_chain(env, arg0, nvert, nsrc, gindex, false);   // (stepwise driving keeps the sequential chain start)
         // stepwise driving (the noise drivers, tests): the launch is followed by nan_fill_kernel, and the first sweep by ucache_prefill_kernel — at a
         // chain start every haplotype has a non-zero frequency, so the first sweep asks for the whole table: the whole GPU computes it instead of the
         // tile's own lanes

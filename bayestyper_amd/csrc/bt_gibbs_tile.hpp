@@ -203,6 +203,7 @@ struct GParams {
     const double BT_GAS *lgamma_int;   // lgamma(n) for integer n in [0, lgamma_n): computed on the host (libm), gathered on the device
     const double BT_GAS *gamma_a2;     // 1 / sqrt(9 (n - 1/3)) for integer n in [1, gamma_n): Marsaglia-Tsang's a2 for alpha = an observation count + 1
     uint32_t lgamma_n, gamma_n;
+    uint32_t bulk_subset;              // BT_GIBBS_BULK_SUBSET: the chain starts of OP_RUN draw the k-mer subset across a group's lockstep copies (sample_kmer_subset)
 };
 
 extern __shared__ __attribute__((aligned(16))) uint8_t bt_lds_raw[];
@@ -821,11 +822,24 @@ __device__ inline bool is_max_hv_kmer(const Vx &c, uint32_t k, uint32_t maxk) {
     }
     return is_max;
 }
-__device__ inline void sample_kmer_subset(const Vx &c, const GParams BT_CAS &P) {
+// bulk (BT_GIBBS_BULK_SUBSET, tiles with lockstep copies): the group's copies share the chain start instead of replaying it — the Bernoulli draws of
+// both lists are taken `copies` at a time (rng_bernoulli_bulk: the same words of the same stream), the counters and caches are cleared in parts, and
+// the max-haplotype filter, whose outcome depends on the k-mers before, runs on the first copy alone together with the CSR offsets of the subset.
+__device__ inline void sample_kmer_subset(const Vx &c, const GParams BT_CAS &P, bool bulk) {
     const uint32_t Vm = c.d().Vm;
     TPtr<uint32_t> hv = c.hvcount();
-    for (uint32_t h = 0; h < c.H; ++h)
-        for (uint32_t v = 0; v < c.V; ++v) hv[(uint32_t)h * Vm + v] = 0;
+#ifdef BT_RNG_BULK
+    bulk = bulk && c.t.copies > 1u;
+#else
+    bulk = false;
+#endif
+    if (bulk) {
+        for (uint32_t h = c.t.part; h < c.H; h += c.t.copies)
+            for (uint32_t v = 0; v < c.V; ++v) hv[(uint32_t)h * Vm + v] = 0;
+    } else {
+        for (uint32_t h = 0; h < c.H; ++h)
+            for (uint32_t v = 0; v < c.V; ++v) hv[(uint32_t)h * Vm + v] = 0;
+    }
     uint32_t nsu = 0, nsm = 0;
     MtRing rng = c.rng(0);
     TPtr<uint32_t> uniq = c.uniq(), usub = c.usub(), multi = c.multi(), msub = c.msub();
@@ -838,18 +852,59 @@ __device__ inline void sample_kmer_subset(const Vx &c, const GParams BT_CAS &P) 
     rng_shuffle_u32(rng, uniq, nu);
     PROF(8);
     uint32_t nu_sel = 0, nm_sel = 0;
-    for (uint32_t i = 0; i < nu; ++i)
-        if (rng_bernoulli(rng, P.rate)) usub[nu_sel++] = uniq[i];
-    rng_shuffle_u32(rng, multi, c.nm);
-    for (uint32_t i = 0; i < c.nm; ++i)
-        if (rng_bernoulli(rng, P.rate)) msub[nm_sel++] = multi[i];
-    for (uint32_t i = 0; i < nu_sel; ++i) {
-        const uint32_t k = usub[i];
-        if (!is_max_hv_kmer(c, k, P.max_hvk)) usub[nsu++] = k;
-    }
-    for (uint32_t i = 0; i < nm_sel; ++i) {
-        const uint32_t k = msub[i];
-        if (!is_max_hv_kmer(c, k, P.max_hvk)) msub[nsm++] = k;
+#ifdef BT_RNG_BULK
+    if (bulk) {
+        const MtTeamCopies team(c.t.part, c.t.copies);
+        // a step's selected k-mers go to the subset in index order: the running count plus the selected lanes of the group below this one
+        rng_bernoulli_bulk(rng, nu, P.rate, team, [&](uint32_t i, bool sel, unsigned long long b) {
+            if (sel) usub[nu_sel + team.below(b)] = uniq[i];
+            nu_sel += (uint32_t)__popcll(b);
+        });
+        rng_shuffle_u32(rng, multi, c.nm);
+        rng_bernoulli_bulk(rng, c.nm, P.rate, team, [&](uint32_t i, bool sel, unsigned long long b) {
+            if (sel) msub[nm_sel + team.below(b)] = multi[i];
+            nm_sel += (uint32_t)__popcll(b);
+        });
+        copies_sync();   // the cleared counters and both lists are complete
+        SPtrF<uint32_t, LANES> sc = c.sc();
+        if (c.t.part == 0) {
+            TPtr<uint32_t> so = c.skv_off();
+            uint32_t ne = 0;
+            so[0] = 0;
+            for (uint32_t i = 0; i < nu_sel; ++i) {
+                const uint32_t k = usub[i];
+                if (!is_max_hv_kmer(c, k, P.max_hvk)) {
+                    usub[nsu++] = k;
+                    ne += c.kv_off(k + 1) - c.kv_off(k);
+                    so[nsu] = ne;
+                }
+            }
+            for (uint32_t i = 0; i < nm_sel; ++i) {
+                const uint32_t k = msub[i];
+                if (!is_max_hv_kmer(c, k, P.max_hvk)) msub[nsm++] = k;
+            }
+            sc[SC_NSUB_U] = nsu;
+            sc[SC_NSUB_M] = nsm;
+        }
+        copies_sync();
+        nsu = sc[SC_NSUB_U];
+        nsm = sc[SC_NSUB_M];
+    } else
+#endif
+    {
+        for (uint32_t i = 0; i < nu; ++i)
+            if (rng_bernoulli(rng, P.rate)) usub[nu_sel++] = uniq[i];
+        rng_shuffle_u32(rng, multi, c.nm);
+        for (uint32_t i = 0; i < c.nm; ++i)
+            if (rng_bernoulli(rng, P.rate)) msub[nm_sel++] = multi[i];
+        for (uint32_t i = 0; i < nu_sel; ++i) {
+            const uint32_t k = usub[i];
+            if (!is_max_hv_kmer(c, k, P.max_hvk)) usub[nsu++] = k;
+        }
+        for (uint32_t i = 0; i < nm_sel; ++i) {
+            const uint32_t k = msub[i];
+            if (!is_max_hv_kmer(c, k, P.max_hvk)) msub[nsm++] = k;
+        }
     }
     PROF(9);
     mt_close(rng);
@@ -862,12 +917,14 @@ __device__ inline void sample_kmer_subset(const Vx &c, const GParams BT_CAS &P) 
         TPtr<uint32_t> so = c.skv_off(), sb = c.skv_bits();
         TPtr<uint16_t> sv = c.skv_var();
         const uint32_t HWm = c.d().HWm, HW = (c.H + 31) / 32;
-        uint32_t ne = 0;
-        so[0] = 0;
-        for (uint32_t i = 0; i < nsu; ++i) {   // CSR offsets first (sequential, every copy of the group computes the same values)
-            const uint32_t k = usub[i];
-            ne += c.kv_off(k + 1) - c.kv_off(k);
-            so[i + 1] = ne;
+        if (!bulk) {   // (bulk: the first copy wrote them with the filter)
+            uint32_t ne = 0;
+            so[0] = 0;
+            for (uint32_t i = 0; i < nsu; ++i) {   // CSR offsets first (sequential, every copy of the group computes the same values)
+                const uint32_t k = usub[i];
+                ne += c.kv_off(k + 1) - c.kv_off(k);
+                so[i + 1] = ne;
+            }
         }
         for (uint32_t i = c.t.part; i < nsu; i += c.t.copies) {   // k-mer i is copied by copy i % copies (lockstep: iteration j handles j*copies + part)
             const uint32_t k = usub[i];
@@ -915,25 +972,26 @@ __device__ inline void sample_kmer_subset(const Vx &c, const GParams BT_CAS &P) 
     sc[SC_NSUB_U] = nsu;
     sc[SC_NSUB_M] = nsm;
     TPtr<uint8_t> smm = c.smm(), oth = c.oth();
-    for (uint32_t i = 0; i < nsm * P.S; ++i) {
+    for (uint32_t i = bulk ? c.t.part : 0u, step = bulk ? c.t.copies : 1u; i < nsm * P.S; i += step) {
         smm[i] = 0;
         oth[i] = 0;
     }
     for (uint32_t s = 0; s < P.S; ++s) c.mgen()[s] += 1;   // a new k-mer subset invalidates the multicluster cache
     SPtrF<uint8_t, LANES> upd = c.ksc_upd();
-    for (uint32_t s = 0; s < P.S; ++s) {
+    for (uint32_t s = bulk ? c.t.part : 0u, step = bulk ? c.t.copies : 1u; s < P.S; s += step) {
         upd[s] = 1;
         for (uint32_t e = 0; e < KSC_WAYS; ++e) c.ksc_key(s)[e] = KSC_NOKEY;   // ... and the kept k-mer-stats caches (collect_sample_body)
         c.ksc_key(s)[KSC_WAYS] = 0;
     }
+    if (bulk) copies_sync();   // (every copy reads what the others cleared)
 }
 
 // ---- VariantClusterGenotyper::reset (VariantClusterGenotyper.cpp:113-129) ----
-__device__ BT_NOINLINE void genotyper_reset(Env env, uint32_t vtx) {
+__device__ BT_NOINLINE void genotyper_reset(Env env, uint32_t vtx, bool bulk) {
     const Vx c = make_vx(make_tile(env), vtx);
     const GParams BT_CAS &P = env_params(env);
     c.sc()[SC_USE_MULTI] = 0;
-    sample_kmer_subset(c, P);
+    sample_kmer_subset(c, P, bulk);
     cache_clear(c, P, true);
     freq_reset(c);   // HaplotypeFrequencyDistribution::reset (counts are 0 here, as the reference asserts)
 }

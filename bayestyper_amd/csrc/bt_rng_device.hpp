@@ -308,6 +308,14 @@ __device__ static __noinline__ void mt_twist_for(bool want, uint32_t BT_GAS *st,
         todo &= ~__ballot(want && (uint64_t)(uintptr_t)st == (((uint64_t)hi << 32) | lo));
     }
 }
+#else
+// host form (a team of one, the bt_diag_* entry points): the same block, word by word
+inline void mt_twist_block(const uint32_t *old, uint32_t *nw) {
+    for (uint32_t i = 0; i < MT_N; ++i) nw[i] = mt_twist(old[i], i + 1u < MT_N ? old[i + 1u] : nw[0], i < MT_N - MT_M ? old[i + MT_M] : nw[i - (MT_N - MT_M)]);
+}
+inline void mt_twist_for(bool want, uint32_t *st, uint32_t cur) {
+    if (want) mt_twist_block(st + (cur ? MT_BUF : 0u), st + (cur ? 0u : MT_BUF));
+}
 #endif
 template <class RP>   // RP: pointer-like (operator[](uint32_t) -> uint32_t&) to the ring block
 struct MtRingT {
@@ -321,10 +329,10 @@ struct MtRingT {
 #ifdef BT_DIAG_FAKE_MT
     uint32_t fake_ctr = 0;
 #endif
-#if defined(BT_MT_BLOCK) && defined(__HIP_DEVICE_COMPILE__) && !defined(BT_DIAG_FAKE_MT)
-    __device__ inline uint32_t BT_GAS *cur_buf() const { return st + ((flags & MT_F_CUR) ? MT_BUF : 0u); }
+#if defined(BT_MT_BLOCK) && !defined(BT_DIAG_FAKE_MT)
+    BT_HD uint32_t BT_GAS *cur_buf() const { return st + ((flags & MT_F_CUR) ? MT_BUF : 0u); }
     // lanes with `at_end` set have read their whole block: the next one is made if it was not made ahead, then the buffers change roles
-    __device__ inline void next_block(bool at_end) {
+    BT_HD void next_block(bool at_end) {
         mt_twist_for(at_end && !(flags & MT_F_READY), st, (flags & MT_F_CUR) ? 1u : 0u);
         if (at_end) {
             flags = (flags ^ MT_F_CUR) & ~MT_F_READY;
@@ -332,14 +340,14 @@ struct MtRingT {
         }
     }
     // at a convergent point: lanes past MT_AHEAD words of their block get the next block made now
-    __device__ inline void twist_ahead() {
+    BT_HD void twist_ahead() {
         const bool want = pos >= MT_AHEAD && !(flags & MT_F_READY);
         if (bt_wave_any(want)) {
             mt_twist_for(want, st, (flags & MT_F_CUR) ? 1u : 0u);
             if (want) flags |= MT_F_READY;
         }
     }
-    __device__ inline void chunk(bool go) {
+    BT_HD void chunk(bool go) {
         if (bt_wave_any(go && pos == MT_N)) next_block(go && pos == MT_N);
         if (go) {
             const MtQuad z = *(const MtQuad BT_GAS *)(cur_buf() + pos);
@@ -353,7 +361,7 @@ struct MtRingT {
         }
     }
     template <unsigned NB>
-    __device__ inline void batch(uint32_t want) {
+    BT_HD void batch(uint32_t want) {
         // up to NB quads of the current block with all loads in flight (a batch does not cross the end of a block: what is missing follows chunk by chunk)
         if (bt_wave_any(avail < want && pos == MT_N)) next_block(avail < want && pos == MT_N);
         uint32_t nc = avail < want ? (want - avail + 3u) >> 2 : 0u;
@@ -378,15 +386,15 @@ struct MtRingT {
                 pos += 4u;
             }
     }
-    __device__ inline void fill_to(uint32_t want) {
+    BT_HD void fill_to(uint32_t want) {
         while (bt_wave_any(avail < want)) chunk(avail < want);
     }
     template <unsigned NB>
-    __device__ inline void fill_batched(uint32_t want) {
+    BT_HD void fill_batched(uint32_t want) {
         if (bt_wave_any(avail < want)) batch<NB>(want);
         fill_to(want);
     }
-    __device__ inline void topup() {
+    BT_HD void topup() {
         twist_ahead();
         fill_batched<4>(cap - 3u);
     }
@@ -605,6 +613,139 @@ BT_HD uint32_t rng_uniform_int(G &st, uint32_t range) {
 
 template <class G>
 BT_HD bool rng_bernoulli(G &st, double p) { return rng_canonical(st) < p; }
+
+#if defined(BT_MT_BLOCK) && !defined(BT_DIAG_FAKE_MT)
+#define BT_RNG_BULK 1
+// ---- n consecutive rng_bernoulli(m, p) calls at once, by a TEAM of lanes that hold the same block-form generator -----------------------------------
+// Draw i reads words 2i and 2i + 1 of the stream from where the generator stands, whatever the outcomes, so the draws do not depend on one another:
+// the team's lane `rank` takes the draws i = rank (mod size) and reads their words where they are — the first `avail` of them in the ring, the rest
+// in the current block and the blocks after it, which the existing cooperative twist makes one at a time (two buffers: block k + 1 replaces block
+// k - 1, so the draws are taken block by block, a draw with the block of its SECOND word).  Then the generator is left exactly where the n calls
+// would have left it.  They refill an empty ring (fewer than two words) to min(cap - 3, 16) words, chunk by chunk, so with a0 words in the ring
+//     the first a0 / 2 draws produce nothing, every `per` draws after them `add` words: add = 4 * ceil((min(cap - 3, 16) - a0 % 2) / 4), per = add / 2
+// which gives the words produced, the blocks entered (each is a twist unless it was made ahead), the position, the ring's head and its unread words —
+// those are written where the chunks would have put them (ring index = head + stream index); the ring's dead entries are not reproduced.
+// emit(i, selected, ballot) is called once per step of `size` draws by every lane of the team: i is the lane's draw (selected is false beyond the
+// last one), ballot the team's selected lanes.  Teams of a wavefront run the loops together, each bounded by its own n and block count.
+struct MtTeamOne {   // the sequential form: host code, and a lane on its own
+    BT_HD uint32_t rank() const { return 0u; }
+    BT_HD uint32_t size() const { return 1u; }
+    BT_HD unsigned long long ballot(bool f) const { return f ? 1ull : 0ull; }
+    BT_HD uint32_t below(unsigned long long) const { return 0u; }
+    BT_HD bool any(bool f) const { return f; }
+    BT_HD void sync() const {}
+};
+struct MtTeamCopies {   // the lockstep copies of a narrow tile's group: the lanes g + k * (64 / copies) of the wavefront, k the copy's part
+    uint32_t part, copies;
+    unsigned long long gmask, lower;   // the team's lanes; the lanes below this one
+    __device__ inline MtTeamCopies(uint32_t part_, uint32_t copies_) : part(part_), copies(copies_) {
+        const uint32_t lane = threadIdx.x & 63u, width = 64u / copies_;
+        unsigned long long m = 0;
+        for (uint32_t k = 0; k < copies_; ++k) m |= 1ull << (lane % width + k * width);
+        gmask = m;
+        lower = (1ull << lane) - 1ull;
+    }
+    __device__ inline uint32_t rank() const { return part; }
+    __device__ inline uint32_t size() const { return copies; }
+    __device__ inline unsigned long long ballot(bool f) const { return __ballot(f) & gmask; }
+    __device__ inline uint32_t below(unsigned long long b) const { return (uint32_t)__popcll(b & lower); }
+    __device__ inline bool any(bool f) const { return bt_wave_any(f); }
+    __device__ inline void sync() const {   // what the sibling lanes stored is visible (same wavefront: program order + L1 write-through)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+};
+template <class G, class T, class F>
+BT_HD void rng_bernoulli_bulk(G &m, uint32_t n, double p, const T &team, F &&emit) {
+    const uint32_t a0 = m.avail, h0 = m.head, p0 = m.pos, mask = m.cap - 1u, cur0 = (m.flags & MT_F_CUR) ? 1u : 0u;
+    const bool ready0 = (m.flags & MT_F_READY) != 0;
+    uint32_t produced = 0;
+    if (n > (a0 >> 1)) {
+        const uint32_t want = m.cap - 3u < 16u ? m.cap - 3u : 16u;
+        const uint32_t add = ((want - (a0 & 1u) + 3u) >> 2) << 2, per = add >> 1;
+        produced = (n - (a0 >> 1) + per - 1u) / per * add;
+    }
+    const uint32_t blocks = produced ? (p0 + produced - 1u) / MT_N : 0u;   // blocks entered: the words read lie in blocks 0 (the current one) .. blocks
+    // tempered word j of the stream (its block and the one before are in the two buffers)
+    auto word = [&](uint32_t j) -> uint32_t {
+        if (j < a0) return m.ring[(h0 + j) & mask];
+        const uint32_t q = p0 + (j - a0), k = q / MT_N;
+        return mt_temper(m.st[(((cur0 + k) & 1u) ? MT_BUF : 0u) + (q - k * MT_N)]);
+    };
+    uint32_t lo = 0;
+    for (uint32_t k = 0; team.any(k <= blocks); ++k) {
+        const bool live = k <= blocks;
+        if (k) mt_twist_for(live && !(k == 1u && ready0), m.st, (cur0 + k - 1u) & 1u);
+        // draws whose second word lies in block k or before: 2i + 1 < a0 + 624 (k + 1) - p0
+        uint32_t hi = (a0 + MT_N * (k + 1u) - p0) >> 1;
+        hi = hi < n ? hi : n;
+        for (uint32_t base = lo; team.any(live && base < hi); base += team.size()) {
+            const uint32_t i = base + team.rank();
+            const bool in = live && i < hi;
+            bool sel = false;
+            if (in) {
+                double sum = (double)word(2u * i);
+                sum += (double)word(2u * i + 1u) * 4294967296.0;
+                double u = sum / 18446744073709551616.0;
+                if (u >= 1.0) u = 0.99999999999999988897769753748434595763683319091796875;   // (rng_canonical)
+                sel = u < p;
+            }
+            const unsigned long long b = team.ballot(sel);
+            if (live && base < hi) emit(i, sel, b);
+        }
+        if (live) lo = hi;
+    }
+    // the unread words the refills would have left in the ring, beyond those that were there
+    const uint32_t end = a0 + produced;
+    for (uint32_t j = (2u * n > a0 ? 2u * n : a0) + team.rank(); j < end; j += team.size()) m.ring[(h0 + j) & mask] = word(j);
+    team.sync();
+    m.head = (h0 + 2u * n) & mask;
+    m.avail = end - 2u * n;
+    m.pos = p0 + produced - blocks * MT_N;
+    if (blocks) m.flags = (cur0 ^ (blocks & 1u)) ? MT_F_CUR : 0u;
+}
+// host check behind bt_diag_bulk_bernoulli (and a stand-alone program under a host sanitizer): n draws after `discard` words of a block-form ring generator,
+// taken by one rng_bernoulli call after another (form 0), by the bulk routine's team of one (1) and by the direct-form generator (2), each followed
+// by eight more words.  flags [3][n], tail [3][8], state [2][4] = {position, flags, ring head, unread ring words} of forms 0 and 1.
+__host__ inline void bulk_bernoulli_check(uint32_t seed, uint64_t discard, uint32_t n, double p, uint32_t ring_cap, int ahead, uint8_t *flags, uint32_t *tail, uint32_t *state) {
+    typedef SPtrF<uint32_t, 1> RP;
+    uint32_t *st0 = new uint32_t[2 * MT_BUF](), *ring0 = new uint32_t[ring_cap + MT_RING_HDR]();
+    uint32_t *st = new uint32_t[2 * MT_BUF], *ring = new uint32_t[ring_cap + MT_RING_HDR], *dst = new uint32_t[MT_WORDS];
+    mt_ring_seed(st0, RP{ring0, 0u, 0u}, ring_cap, seed);
+    {
+        MtRing m = mt_ring_open(st0, RP{ring0, 0u, 0u}, ring_cap);
+        for (uint64_t i = 0; i < discard; ++i) (void)m.next();
+        if (ahead) m.twist_ahead();
+        mt_close(m);
+    }
+    for (uint32_t form = 0; form < 2; ++form) {
+        for (uint32_t i = 0; i < 2 * MT_BUF; ++i) st[i] = st0[i];
+        for (uint32_t i = 0; i < ring_cap + MT_RING_HDR; ++i) ring[i] = ring0[i];
+        MtRing m = mt_ring_open(st, RP{ring, 0u, 0u}, ring_cap);
+        uint8_t *f = flags + (size_t)form * n;
+        if (form == 0) {
+            for (uint32_t i = 0; i < n; ++i) f[i] = rng_bernoulli(m, p) ? 1 : 0;
+        } else {
+            for (uint32_t i = 0; i < n; ++i) f[i] = 0xFF;
+            const MtTeamOne team;
+            rng_bernoulli_bulk(m, n, p, team, [&](uint32_t i, bool sel, unsigned long long) { f[i] = sel ? 1 : 0; });
+        }
+        state[4 * form] = m.pos, state[4 * form + 1] = m.flags, state[4 * form + 2] = m.head, state[4 * form + 3] = m.avail;
+        for (uint32_t k = 0; k < 8; ++k) tail[8 * form + k] = m.next();
+    }
+    mt_seed(dst, seed);
+    Mt d = mt_open(dst);
+    for (uint64_t i = 0; i < discard; ++i) (void)d.next();
+    for (uint32_t i = 0; i < n; ++i) flags[2 * (size_t)n + i] = rng_bernoulli(d, p) ? 1 : 0;
+    for (uint32_t k = 0; k < 8; ++k) tail[16 + k] = d.next();
+    delete[] st0;
+    delete[] ring0;
+    delete[] st;
+    delete[] ring;
+    delete[] dst;
+}
+#endif
 
 // std::shuffle over a uint32 array in caller memory
 template <class G, typename Arr>

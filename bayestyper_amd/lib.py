@@ -682,6 +682,7 @@ bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, v
 bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
+bt_diag_bulk_bernoulli = _sig("bt_diag_bulk_bernoulli", [C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_int, vp, vp, vp])
 bt_genotype_text_sizes = _sig("bt_genotype_text_sizes", [vp, vp, C.c_uint64, u64p, u64p])
 bt_genotype_text = _sig("bt_genotype_text", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p])
 bt_gibbs_genotype_text = _sig("bt_gibbs_genotype_text", [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u32p])

@@ -793,6 +793,11 @@ int bt_diag_uset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *v
  * 2 gamma(shape=a, scale=b) with one persistent distribution object, 3 uniform_int(0, a), 4 bernoulli(float a),
  * 5 std::shuffle of 0..a-1 (h_out gets the permutation as doubles, n ignored) */
 int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint64_t n, double *h_out);
+/* n Bernoulli(p) draws after `discard` words of a block-form ring generator seeded like std::mt19937(seed), taken three ways: call by call (form 0), by the
+ * bulk routine the Gibbs chain start uses, as a team of one (1), and by the direct-form generator (2), each followed by eight more words.  ahead != 0: the
+ * next block is twisted ahead first where the position allows it.  h_flags [3][n], h_tail [3][8], h_state [2][4] = {position in block, buffer flags, ring head,
+ * unread ring words} of forms 0 and 1.  All three must agree. */
+int bt_diag_bulk_bernoulli(uint32_t seed, uint64_t discard, uint32_t n, double p, uint32_t ring_cap, int ahead, uint8_t *h_flags, uint32_t *h_tail, uint32_t *h_state);
 /* Host-side run of the genotype summaries behind bt_gibbs_genotypes for ONE cluster given in host arrays (what bt_gibbs_result_fetch returns for it, entries
  * in that call's order; stats [(s * A_total + allele_base(v) + a) * 12]; ploidy [S] of the cluster's group): h_words receives the string bt_gibbs_genotypes
  * would produce for a launch of this one cluster, *num_words its length (an error when capacity is smaller; *num_words is set first). */
