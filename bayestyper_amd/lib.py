@@ -66,6 +66,9 @@ bt_table_insert_batch = _sig("bt_table_insert_batch", [vp, vp, C.c_uint64, C.c_i
 bt_table_find_batch = _sig("bt_table_find_batch", [vp, vp, C.c_uint64, vp])
 bt_table_read_slots = _sig("bt_table_read_slots", [vp, vp, C.c_uint64, vp, vp])
 bt_table_export = _sig("bt_table_export", [vp, vp, vp, vp, C.c_uint64, u64p])
+bt_table_count_row_bytes = _sig("bt_table_count_row_bytes", [vp, u32p])
+bt_table_export_count_rows = _sig("bt_table_export_count_rows", [vp, vp, C.c_uint64, u64p])
+bt_table_merge_count_rows = _sig("bt_table_merge_count_rows", [vp, vp, C.c_uint64])
 bt_table_record_bytes = _sig("bt_table_record_bytes", [vp, u32p])
 bt_table_pack = _sig("bt_table_pack", [vp, vp, C.c_uint64, u64p])
 bt_table_unpack = _sig("bt_table_unpack", [vp, vp, C.c_uint64])
@@ -93,6 +96,7 @@ bt_paths_candidates_fetch_small = _sig("bt_paths_candidates_fetch_small", [vp, v
 bt_table_count_parameter_kmers = _sig("bt_table_count_parameter_kmers", [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_float])
 bt_table_kmer_stats = _sig("bt_table_kmer_stats", [vp, vp, vp, vp, vp, vp, vp])
 bt_table_count_intercluster = _sig("bt_table_count_intercluster", [vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32])
+bt_table_count_intercluster_regions = _sig("bt_table_count_intercluster_regions", [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp])
 bt_table_classify_batch = _sig("bt_table_classify_batch", [vp, vp, vp, vp, C.c_uint64, vp])
 bt_kmc_scan_create = _sig("bt_kmc_scan_create", [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.POINTER(vp)])
 bt_kmc_scan_create_bins = _sig("bt_kmc_scan_create_bins", [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)])
@@ -100,6 +104,8 @@ bt_kmc_scan_make_bloom = _sig("bt_kmc_scan_make_bloom", [vp, vp, vp, C.c_uint64,
 bt_kmc_scan_destroy = _sig("bt_kmc_scan_destroy", [vp])
 bt_kmc_scan_set_count_range = _sig("bt_kmc_scan_set_count_range", [vp, C.c_uint32, C.c_uint64])
 bt_kmc_scan_run = _sig("bt_kmc_scan_run", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, vp])
+bt_kmc_scan_run_host = _sig("bt_kmc_scan_run_host", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp])
+bt_kmc_scan_run_file = _sig("bt_kmc_scan_run_file", [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp])
 bt_kmc_scan_decode = _sig("bt_kmc_scan_decode", [vp, vp, C.c_uint64, C.c_uint64, vp, vp])
 bt_kmer_stats_num_bins = _sig("bt_kmer_stats_num_bins", [C.c_uint32], C.c_uint64)
 bt_kmc_scan_kmer_stats = _sig("bt_kmc_scan_kmer_stats", [vp, vp, C.c_uint64, C.c_uint64, vp, vp])
@@ -322,6 +328,16 @@ class Table:
         self.ctx.sync()
         d.free()
 
+    def count_intercluster_regions(self, bloom, seq_bytes, starts, lens, decoy, female, male):
+        """bt_table_count_intercluster_regions: every region of one sequence (uploaded here) in one launch"""
+        d = self.ctx.to_device(np.frombuffer(seq_bytes, dtype=np.uint8))
+        a = [np.ascontiguousarray(starts, np.uint64), np.ascontiguousarray(lens, np.uint64)] + [np.ascontiguousarray(x, np.uint8) for x in (decoy, female, male)]
+        assert all(len(x) == len(a[0]) for x in a)
+        try:
+            check(bt_table_count_intercluster_regions(self.h, bloom.h, d.ptr, len(a[0]), *[_np_ptr(x) for x in a]))
+        finally:
+            d.free()
+
     def classify(self, mg_bloom, packed, mult):
         packed = np.ascontiguousarray(packed, dtype=np.uint64)
         mult = np.ascontiguousarray(mult, dtype=np.uint8)
@@ -362,6 +378,40 @@ class Table:
         check(bt_table_export(self.h, _np_ptr(kmers), _np_ptr(counts), _np_ptr(meta), max(n, 1), C.byref(w)))
         n = w.value
         return kmers[:n], counts[:n], meta[:n]
+
+    def read_slots(self, slots):
+        """bt_table_read_slots of slots found with find() -> (counts (n,S) u8, meta (n,4) u8); a slot outside the table reads as zeros"""
+        slots = np.ascontiguousarray(slots, dtype=np.int64)
+        n = len(slots)
+        counts = np.zeros((max(n, 1), self.num_samples), np.uint8)
+        meta = np.zeros((max(n, 1), 4), np.uint8)
+        check(bt_table_read_slots(self.h, _np_ptr(slots), n, _np_ptr(counts), _np_ptr(meta)))
+        return counts[:n], meta[:n]
+
+    def count_row_bytes(self):
+        """bytes of a count row: 16 key + the counts padded to a multiple of four"""
+        rb = C.c_uint32()
+        check(bt_table_count_row_bytes(self.h, C.byref(rb)))
+        return rb.value
+
+    def export_count_rows(self):
+        """bt_table_export_count_rows -> (DeviceBuffer of count rows, number of rows); the caller frees the buffer"""
+        n = C.c_uint64()
+        check(bt_table_export_count_rows(self.h, None, 0, C.byref(n)))
+        buf = self.ctx.buffer(max(n.value, 1) * self.count_row_bytes())
+        try:
+            check(bt_table_export_count_rows(self.h, buf.ptr, max(n.value, 1), C.byref(n)))
+        except BtError:
+            buf.free()
+            raise
+        return buf, n.value
+
+    def merge_count_rows(self, buf_or_ptr, n):
+        """bt_table_merge_count_rows of n count rows in device memory (a DeviceBuffer or a device address); asynchronous"""
+        if isinstance(buf_or_ptr, DeviceBuffer):
+            assert int(n) * self.count_row_bytes() <= buf_or_ptr.nbytes
+            buf_or_ptr = buf_or_ptr.ptr
+        check(bt_table_merge_count_rows(self.h, buf_or_ptr, int(n)))
 
     def record_bytes(self):
         """bytes of a packed record: 16 key + 4 meta + the counts padded to a multiple of four"""
@@ -595,6 +645,20 @@ class KmcScan:
     def run(self, bloom, table, sample_idx, d_records_ptr, first_record, n, d_hits_ptr=None):
         check(bt_kmc_scan_run(self.h, bloom.h, table.h, sample_idx, d_records_ptr, first_record, n, d_hits_ptr))
 
+    def run_file(self, bloom, table, sample_idx, suf_path, first_record, n, chunk_records=0, payload_offset=4):
+        """bt_kmc_scan_run_file: records [first_record, first_record + n) streamed from the .kmc_suf file -> Bloom hits (blocking)"""
+        hits = C.c_uint64()
+        check(bt_kmc_scan_run_file(self.h, bloom.h, table.h, sample_idx, os.fsencode(suf_path), payload_offset, first_record, n, chunk_records, C.byref(hits)))
+        return hits.value
+
+    def run_host(self, bloom, table, sample_idx, records, first_record, n, chunk_records=0):
+        """bt_kmc_scan_run_host: `records` (uint8 host array) starts at record first_record -> Bloom hits (blocking)"""
+        records = np.ascontiguousarray(records, dtype=np.uint8)
+        assert records.nbytes >= int(n) * self.rec_size
+        hits = C.c_uint64()
+        check(bt_kmc_scan_run_host(self.h, bloom.h, table.h, sample_idx, _np_ptr(records), first_record, n, chunk_records, C.byref(hits)))
+        return hits.value
+
     def decode(self, payload, first_record, n):
         d = self.ctx.to_device(np.frombuffer(payload, dtype=np.uint8))
         ok = self.ctx.buffer(16 * max(n, 1))
@@ -679,6 +743,7 @@ bt_gibbs_source_fetch = _sig("bt_gibbs_source_fetch", [vp, vp, vp])
 bt_gibbs_source_destroy = _sig("bt_gibbs_source_destroy", [vp])
 bt_gibbs_source_device_bytes = _sig("bt_gibbs_source_device_bytes", [vp, u64p])
 bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)])
+bt_gibbs_state_bytes = _sig("bt_gibbs_state_bytes", [vp, vp, vp, u64p])
 bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])

@@ -25,6 +25,15 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_every_declared_symbol_is_bound_with_argtypes():
+    """bayestyper_amd.lib declares the argument types of every entry point of include/btgpu.h: an entry point without a binding is one no test can reach
+    (ctypes would pass every argument as a C int)"""
+    from bayestyper_amd import lib
+
+    unbound = [s for s in header_symbols() if getattr(lib._lib, s).argtypes is None]
+    assert not unbound, unbound
+
+
 def test_comm_library_exports_every_declared_symbol():
     """libbtcomm.so (the RCCL exchange steps) exports what include/btcomm.h declares; libbtgpu.so itself carries no RCCL dependency"""
     syms = header_symbols("btcomm.h")

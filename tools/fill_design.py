@@ -69,7 +69,7 @@ kernel_table = f"""| Kernel | Work per launch | Bound | Algorithmic bytes (SURVE
 | `bt_paths_*` kernels | every k-mer window of every best path of every cluster of a unit | HBM random access (atomic find-or-insert into two open-addressing indexes) | per window: 1 B text + 17 B k-mer + 2×(20–28 B index entry) + ≈21+S B table probe | {gs['clusters']} clusters, {e(gs['kmer_windows'])} windows: enumerate {e(gs['enumerate_windows_per_sec'])} windows/s, Bloom insert {e(gs['bloom_insert_windows_per_sec'])}/s, classify {e(gs['classify_windows_per_sec'])}/s, candidates {e(gs['candidates_windows_per_sec'])}/s (host wall-clock, fetch to host arrays included) |
 | `mg_order_kernel` + the multigroup kernels | one lane per group replays the group's `unordered_set`; the rest one lane per k-mer | latency (sequential container replay per group) / HBM random access | ≈ 60 B per distinct (group, k-mer) | {e(gs.get('multigroup_windows_per_sec', 0))} windows/s for 50 000 single-cluster groups; counters: @@MG_ORDER@@ |
 | `find_paths_kernel` | per sample: the best-path search of every cluster of a unit, one lane per cluster | latency of dependent accesses + random probes into the sample Bloom filter | per vertex nucleotide and live path: one Bloom probe chain | {e(gs['find_sample_paths_clusters_per_sec'])} clusters/s per sample; counters: @@FIND_PATHS@@ |
-| `kmer_stats_kernel`, `summary_kernel`, `bloom_*`, `table_*`, `intercluster_kernel`, `classify_kernel`, `kmers_from_sequence_kernel`, `export_count_rows_kernel`, `merge_count_rows_kernel` | one slot / k-mer / position / row per lane, grid-stride | HBM stream or random access | 4 + spad + 4 B per slot; 8 B per (cluster, sample); ≈3 B/position; 21+S B per path k-mer; 16 + spad B per count row | parity-tested |"""
+| `kmer_stats_kernel`, `summary_kernel`, `bloom_*`, `table_*`, `intercluster_kernel`, `intercluster_regions_kernel`, `classify_kernel`, `kmers_from_sequence_kernel`, `export_count_rows_kernel`, `merge_count_rows_kernel` | one slot / k-mer / position / row per lane, grid-stride | HBM stream or random access | 4 + spad + 4 B per slot; 8 B per (cluster, sample); ≈3 B/position; 21+S B per path k-mer; 16 + spad B per count row | parity-tested (the two count-row kernels: `tests/test_count_rows_gpu.py` against numpy, `tests/test_sharded_scan_gpu.py` against the oracle's one-rank table; `intercluster_regions_kernel`: `tests/test_intercluster_regions_gpu.py`) |"""
 
 issue_p = os.path.join(P, f"{tag}_issue.json")
 issue = json.load(open(issue_p))["gibbs"] if os.path.exists(issue_p) else None
