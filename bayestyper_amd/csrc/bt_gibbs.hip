@@ -962,6 +962,7 @@ inline uint32_t tile_lds_bytes(const TileDesc &d) { return d.lds_all ? d.hot_byt
 // a cluster's [S][D] tables are dense up to 256 MB per tile (64 MB when the batch would not fit the GPU otherwise): a hashed table far
 // smaller than the set of live (sample, diplotype) pairs thrashes (256 candidates x 10 samples: 12x slower than dense)
 constexpr uint32_t kBulkSubsetDefault = 1;      // BT_GIBBS_BULK_SUBSET when the variable is not set (on: profiles/chain_start_subset.txt)
+constexpr uint32_t kTeamApplyDefault = 1;       // BT_GIBBS_TEAM_APPLY when the variable is not set (profiles/team_apply.txt)
 constexpr uint32_t kMinTileWidth = 4;           // groups per wavefront of the narrowest tiles (the other lanes run copies)
 constexpr uint32_t kLightLds = 24576;            // tiles above this are "heavy" (they get fewer wavefronts per tile)
 // upper LDS bounds of the launch classes: at most four, the streams of more classes than hardware queues would run one after another
@@ -1353,6 +1354,11 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
     {
         const char *e = getenv("BT_GIBBS_BULK_SUBSET");
         P.bulk_subset = e ? (atoi(e) != 0 ? 1u : 0u) : kBulkSubsetDefault;
+    }
+    // a visit's per-sample bookkeeping is dealt to the teams / copies of a narrow tile's group (sample_diplotypes, prepare_nested): BT_GIBBS_TEAM_APPLY=0/1, read once here
+    {
+        const char *e = getenv("BT_GIBBS_TEAM_APPLY");
+        P.team_apply = e ? (atoi(e) != 0 ? 1u : 0u) : kTeamApplyDefault;
     }
     for (uint32_t s = 0; s < S; ++s) P.gender[s] = params->gender[s] ? 1 : 0;
 

@@ -57,7 +57,9 @@ __device__ BT_NOINLINE void prepare_nested(Env env, uint32_t v_parent, uint32_t 
     TPtr<uint32_t> ndcl = c.a<uint32_t>(A_NDCL, d.NDm > 1 ? d.NDm : 1), ndvo = c.a<uint32_t>(A_NDVOFF, d.NDm + 1);
     TPtr<uint16_t> ndv = c.a<uint16_t>(A_NDVAR, d.NDVm > 1 ? d.NDVm : 1);
     TPtr<uint32_t> pver = c.nver(), cver = cc.nver();
-    for (uint32_t s = 0; s < P.S; ++s) {
+    // (team_apply: the samples are independent — everything below is read and written at (s, ...) — so copy p of the group prepares the samples p, p + copies, ...)
+    const bool deal = t.copies > 1u && P.team_apply != 0;
+    for (uint32_t s = deal ? t.part : 0u; s < P.S; s += deal ? t.copies : 1u) {
         // The child's nested info of a sample is a function of the parent's diplotype, k-mer-stats cache and own nested info of that sample:
         // nothing to do while the parent's version of them is the one this info was prepared from.
         const uint32_t pv = pver[s];
@@ -107,6 +109,7 @@ __device__ BT_NOINLINE void prepare_nested(Env env, uint32_t v_parent, uint32_t 
         cc.nest_ploidy()[s] = ploidy;
         cc.nest_n()[s] = (uint8_t)n;
     }
+    if (deal) copies_sync();
 }
 
 __device__ __forceinline__ void visit_vertex(const Env &env_in, const Tile &t, const GParams BT_CAS &P, uint32_t v, bool collect, TPtr<uint32_t> trace_row, bool tracing) {

@@ -204,6 +204,7 @@ struct GParams {
     const double BT_GAS *gamma_a2;     // 1 / sqrt(9 (n - 1/3)) for integer n in [1, gamma_n): Marsaglia-Tsang's a2 for alpha = an observation count + 1
     uint32_t lgamma_n, gamma_n;
     uint32_t bulk_subset;              // BT_GIBBS_BULK_SUBSET: the chain starts of OP_RUN draw the k-mer subset across a group's lockstep copies (sample_kmer_subset)
+    uint32_t team_apply;               // BT_GIBBS_TEAM_APPLY: the per-sample bookkeeping of a visit is dealt to the teams / copies of a narrow tile's group instead of replayed by each (sample_diplotypes)
 };
 
 extern __shared__ __attribute__((aligned(16))) uint8_t bt_lds_raw[];
@@ -229,7 +230,8 @@ struct Tile {
     // Narrow tiles leave most lanes of their wavefront idle.  Instead, 64 / width ("copies") threads run the SAME group: identical
     // program, identical loads, identical stores to identical addresses (SIMT lockstep makes every read-modify-write of the copies
     // read before any of them writes) — which costs nothing — and the phases that are data-parallel inside one group (the dense
-    // table fill, the compact subset copies) are divided among the copies by `part`.
+    // table fill, the compact subset copies; GParams::team_apply: a visit's per-sample bookkeeping and its loops over the haplotypes) are
+    // divided among the copies by `part`.
     uint32_t part, copies;
     uint32_t wsh;        // TileDesc::wsh
     uint8_t *hot;        // this wavefront's LDS block (generic pointer) or nullptr
@@ -1739,13 +1741,21 @@ __device__ BT_SWEEPFN void update_allele_kmer_stats(Env env, uint32_t vtx, uint3
         }
         return;
     }
-    for (uint32_t s = 0; s < P.S; ++s) {
-        const uint16_t h1 = dip[2 * s], h2 = dip[2 * s + 1];
+    // May the sample's sweep join its pending run?  The test reads state indexed by the sample alone, and the slow path of a sample writes that sample's
+    // state only (flush_sample, rebuild_kmer_stats_cache, replay_collected, the pending copy: all (s, ...)), so the tests of a round of samples can all
+    // come before the round's slow paths.  team_apply: copy p tests sample s0 + p — one round trip to HBM for up to `copies` samples instead of one
+    // after the other — and every copy then takes the outcomes in sample order (the slow path divides its work among the copies and needs them all).
+    const uint32_t deal = c.t.copies > 1u && P.team_apply != 0 ? c.t.copies : 1u;
+    const uint32_t cw = 64u / c.t.copies, gl = (threadIdx.x & 63u) % cw;
+    for (uint32_t s0 = 0; s0 < P.S; s0 += deal) {
+        const uint32_t s = s0 + (deal > 1u ? c.t.part : 0u);
+        bool defer = false;
+        PROF_DECL;
 #ifndef ABL_NODEFER
 #ifdef BT_NODEFER_NARROW
         if (c.t.copies == 1u)
 #endif
-        if (pvalid[s] && !upd[s] && pdip[2 * s] == h1 && pdip[2 * s + 1] == h2) {
+        if (s < P.S && pvalid[s] && !upd[s] && pdip[2 * s] == dip[2 * s] && pdip[2 * s + 1] == dip[2 * s + 1]) {
             const uint32_t nn = c.nest_n()[s];
             bool same = true;
             if (nn) {   // nested groups: the parent's contribution of this sweep equals the one the pending sweeps saw
@@ -1756,19 +1766,24 @@ __device__ BT_SWEEPFN void update_allele_kmer_stats(Env env, uint32_t vtx, uint3
                         TPtr<double> q = c.nest_stats(s, j);
                         same = same && (double)q[0] == (double)pn[4 * j] && (double)q[1] == (double)pn[4 * j + 1] && (double)q[2] == (double)pn[4 * j + 2];
                     }
-            } else
-                same = true;
-            if (same) {
-                c.pend()[s] += 1;
-                continue;
             }
+            defer = same;
         }
 #endif
+        const unsigned long long outcomes = deal > 1u ? __ballot(defer) : 0ull;   // copy j of this group is lane gl + j * cw
+        PROF(27);   // (inside collect(stats), like the slow path's three)
+        for (uint32_t j = 0; j < deal && s0 + j < P.S; ++j) {
+            const bool d = deal > 1u ? ((outcomes >> (gl + j * cw)) & 1ull) != 0 : defer;
+            if (d) {
+                c.pend()[s0 + j] += 1;
+                continue;
+            }
 #ifdef BT_COLLECT_OUTLINE
-        collect_sample_slow(env, vtx, s);
+            collect_sample_slow(env, vtx, s0 + j);
 #else
-        collect_sample_body(c, P, s, nsub_u, nsub_m);
+            collect_sample_body(c, P, s0 + j, nsub_u, nsub_m);
 #endif
+        }
     }
 }
 
@@ -1800,8 +1815,21 @@ __device__ BT_SWEEPFN void sample_diplotypes(Env env, uint32_t vtx, bool collect
     uint32_t nnz = 0;
     {
         SPtrF<uint8_t, LANES> nz = c.nz();
-        for (uint32_t h = 0; h < c.H; ++h)
-            if (nz[h]) nzl[nnz++] = (uint16_t)h;
+#ifdef BT_RNG_BULK
+        if (c.t.copies > 1u && c.H > c.t.copies && P.team_apply != 0) {   // (more haplotypes than copies: below that the scan is shorter than the exchange) copy p tests haplotype base + p; a step's non-zero haplotypes go to the list in index order (as sample_kmer_subset's bulk form)
+            const MtTeamCopies grp(c.t.part, c.t.copies);
+            for (uint32_t base = 0; base < c.H; base += c.t.copies) {
+                const uint32_t h = base + c.t.part;
+                const bool sel = h < c.H && nz[h] != 0;
+                const unsigned long long b = grp.ballot(sel);
+                if (sel) nzl[nnz + grp.below(b)] = (uint16_t)h;
+                nnz += (uint32_t)__popcll(b);
+            }
+            copies_sync();
+        } else
+#endif
+            for (uint32_t h = 0; h < c.H; ++h)
+                if (nz[h]) nzl[nnz++] = (uint16_t)h;
     }
     PROF(0);
     // The S draws of a visit are independent of each other — a sample's candidates depend on the frequencies and on its own
@@ -1811,6 +1839,7 @@ __device__ BT_SWEEPFN void sample_diplotypes(Env env, uint32_t vtx, bool collect
     const uint32_t T = c.t.copies > 1u && c.d().teams > 1u ? c.d().teams : 1u;
     const uint32_t tsz = c.t.copies / T, team = c.t.part / tsz, tpart = c.t.part - team * tsz;   // team >= T: no sample this round
     const uint32_t cw = 64u / c.t.copies, gl = (threadIdx.x & 63u) % cw, tlane0 = gl + team * tsz * cw;
+    const bool team_apply = !kSingle && T > 1u && P.team_apply != 0;
     SPtrF<double, LANES> cum = c.cum() + (team < T ? team : 0u) * (c.d().D2m > 1 ? c.d().D2m : 1);
     for (uint32_t s0 = 0; s0 < P.S; s0 += T) {
       double u01 = 0;
@@ -2068,20 +2097,46 @@ __device__ BT_SWEEPFN void sample_diplotypes(Env env, uint32_t vtx, bool collect
       }
       if (T > 1u) copies_sync();
       PROF(3);
-      for (uint32_t j = 0; j < T && s0 + j < P.S; ++j) {   // apply the round's picks in sample order (every copy)
-        const uint32_t ss = s0 + j;
-        const uint32_t hh = T > 1u ? (uint32_t)__shfl((int)mine, (int)(gl + j * tsz * cw)) : mine;
-        const uint16_t h1 = (uint16_t)(hh & 0xFFFFu), h2 = (uint16_t)(hh >> 16);
-        const uint16_t p1 = dip[2 * ss], p2 = dip[2 * ss + 1];
-        dip[2 * ss] = h1;
-        dip[2 * ss + 1] = h2;
-        if (!kSingle && c.d().nvm > 1u && (h1 != p1 || h2 != p2)) c.nver()[ss] += 1;
-        hfd_increment(c, h1, is_sparse, hap_count);
-        hfd_increment(c, h2, is_sparse, hap_count);
+      // Apply the round's picks.  The diplotype and the two frequency-distribution increments go in sample order on every copy (the sets are
+      // order-dependent and live with the copies).  What is indexed by the sample alone — the version bump and the shared multiplicities,
+      // column ss of A_SHMULT / A_SMM / A_KSCUPD / A_NVER, a chain of dependent loads from HBM — is replayed per sample by every copy, or
+      // (team_apply) runs once for the whole round, sample s0 + j on team j's lanes: one extra pass of the loop, so that the code exists once.
+      const uint32_t nround = P.S - s0 < T ? P.S - s0 : T;
+      uint32_t own_now = 0, own_prev = 0;   // team_apply: the team's sample, its new and its previous diplotype
+      for (uint32_t j = 0; j < nround + (team_apply ? 1u : 0u); ++j) {
+        uint32_t ss = s0 + j, hh = 0, pp = 0;
+        bool multi_now = false;
+        if (j < nround) {
+          hh = T > 1u ? (uint32_t)__shfl((int)mine, (int)(gl + j * tsz * cw)) : mine;
+          const uint16_t h1 = (uint16_t)(hh & 0xFFFFu), h2 = (uint16_t)(hh >> 16);
+          pp = (uint32_t)dip[2 * ss] | ((uint32_t)dip[2 * ss + 1] << 16);
+          dip[2 * ss] = h1;
+          dip[2 * ss + 1] = h2;
+          hfd_increment(c, h1, is_sparse, hap_count);
+          hfd_increment(c, h2, is_sparse, hap_count);
+          if (tracing) trace_row[ss] = hh;
+          if (j == team) {
+            own_now = hh;
+            own_prev = pp;
+          }
+          multi_now = !team_apply;
+        } else {
+          ss = s0 + team;
+          hh = own_now;
+          pp = own_prev;
+          multi_now = team < nround;
+        }
         PROF(4);
-        update_multicluster_multiplicities(c, P, h1, h2, p1, p2, ss, nsub_m);
+        if (multi_now) {
+          const uint16_t h1 = (uint16_t)(hh & 0xFFFFu), h2 = (uint16_t)(hh >> 16), p1 = (uint16_t)(pp & 0xFFFFu), p2 = (uint16_t)(pp >> 16);
+          if (!kSingle && c.d().nvm > 1u && hh != pp) c.nver()[ss] += 1;
+          update_multicluster_multiplicities(c, P, h1, h2, p1, p2, ss, nsub_m);
+        }
         PROF(5);
-        if (tracing) trace_row[ss] = hh;
+      }
+      if (team_apply) {   // what the teams stored, before the next round's multi_refresh, the statistics and the children's prepare_nested read it
+        copies_sync();
+        PROF(5);
       }
     }
     mt_close(rng);
@@ -2231,23 +2286,26 @@ __device__ BT_SWEEPFN void sample_haplotype_frequencies(Env env, uint32_t vtx) {
             PROF(23);
             // "for z in zero: freq = 0, nz = 0, obs = 0": the zero set is exactly the haplotypes not selected above, so the reset
             // runs over the arrays (independent accesses, eight in flight) instead of chasing the set's list links
+            // (team_apply: the haplotypes are dealt to the group's copies, h = part, part + copies, ...: independent elements)
             {
-                uint32_t h = 0;
-                for (; h + 8 <= c.H; h += 8) {
+                const bool deal = c.t.copies > 1u && P.team_apply != 0;
+                const uint32_t step = deal ? c.t.copies : 1u;
+                uint32_t h = deal ? c.t.part : 0u;
+                for (; h + 7 * step < c.H; h += 8 * step) {
                     uint8_t m8[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) m8[q] = nz[h + q];
+                    for (uint32_t q = 0; q < 8; ++q) m8[q] = nz[h + q * step];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        if (m8[q] == 2) nz[h + q] = 1;
+                    for (uint32_t q = 0; q < 8; ++q) {
+                        if (m8[q] == 2) nz[h + q * step] = 1;
                         else {
-                            freq[h + q] = 0;
-                            nz[h + q] = 0;
-                            obs[h + q] = 0;
+                            freq[h + q * step] = 0;
+                            nz[h + q * step] = 0;
+                            obs[h + q * step] = 0;
                         }
                     }
                 }
-                for (; h < c.H; ++h) {
+                for (; h < c.H; h += step) {
                     if (nz[h] == 2) nz[h] = 1;
                     else {
                         freq[h] = 0;
@@ -2255,7 +2313,9 @@ __device__ BT_SWEEPFN void sample_haplotype_frequencies(Env env, uint32_t vtx) {
                         obs[h] = 0;
                     }
                 }
+                if (deal) copies_sync();
             }
+            PROF(29);
             // "for p in plus: freq /= norm; zero.insert(p); obs = 0" then plus.clear(): record the plus iteration order
             // first (shared `next` words), clear plus, then insert into zero in that order — same final containers
             SPtrF<uint16_t, LANES> nzl = c.nzlist();
