@@ -135,6 +135,15 @@ __global__ __launch_bounds__(256) void result_count_kernel(const TileDesc *__res
     n_ent[c] = sc[SC_DIP_ENTRIES];
     if (sc[SC_DIP_OVERFLOW]) atomicOr(overflow, 1u);
 }
+// every cluster's SC_IS_SPARSE word: the frequency distribution its genotyper was constructed with and the form of its sets (bt_gibbs_sparse_forms)
+__global__ __launch_bounds__(256) void sparse_form_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const ClusterLoc *__restrict__ loc, uint32_t num_clusters,
+                                                          uint32_t *__restrict__ form) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= num_clusters) return;
+    const Vx x = result_vx(tiles, pool, loc[c]);
+    SPtrF<uint32_t, LANES> sc = x.sc();
+    form[c] = sc[SC_CONSTRUCTED] ? (uint32_t)sc[SC_IS_SPARSE] : 0xFFFFFFFFu;
+}
 // one wavefront per cluster: the cluster's diplotype entries ordered by (h1, h2) with their per-sample counts, its allele k-mer statistics
 constexpr uint32_t kPackLds = 2048;   // entries ranked from LDS; larger tables are ranked from the table itself
 __global__ __launch_bounds__(64) void result_pack_kernel(const TileDesc *__restrict__ tiles, uint8_t *__restrict__ pool, const ClusterLoc *__restrict__ loc, uint32_t S,
@@ -963,7 +972,8 @@ inline uint32_t tile_lds_bytes(const TileDesc &d) { return d.lds_all ? d.hot_byt
 // smaller than the set of live (sample, diplotype) pairs thrashes (256 candidates x 10 samples: 12x slower than dense)
 constexpr uint32_t kBulkSubsetDefault = 1;      // BT_GIBBS_BULK_SUBSET when the variable is not set (on: profiles/chain_start_subset.txt)
 constexpr uint32_t kTeamApplyDefault = 1;       // BT_GIBBS_TEAM_APPLY when the variable is not set (profiles/team_apply.txt)
-constexpr uint32_t kMinTileWidth = 4;           // groups per wavefront of the narrowest tiles (the other lanes run copies)
+constexpr uint32_t kNibbleSetsDefault = 1;      // BT_GIBBS_NIBBLE_SETS when the variable is not set (on: profiles/nibble_sets.txt)
+constexpr uint32_t kMinTileWidth = 4;          // groups per wavefront of the narrowest tiles (the other lanes run copies)
 constexpr uint32_t kLightLds = 24576;            // tiles above this are "heavy" (they get fewer wavefronts per tile)
 // upper LDS bounds of the launch classes: at most four, the streams of more classes than hardware queues would run one after another
 const uint32_t kClassLds[] = {16384, 32768, 0xFFFFFFFFu};   // + one class of the simple tiles (two-haplotype clusters), launched as gibbs_simple_kernel
@@ -1359,6 +1369,12 @@ static int gibbs_create_impl(const bt_gibbs_source *src, bt_ctx *ctx, const bt_g
     {
         const char *e = getenv("BT_GIBBS_TEAM_APPLY");
         P.team_apply = e ? (atoi(e) != 0 ? 1u : 0u) : kTeamApplyDefault;
+    }
+    // sparse clusters of 3 .. NSET_MAX haplotypes keep their zero and plus sets as packed words (genotyper_construct chooses the form of a vertex from this and
+    // its H, Vx::HSet): BT_GIBBS_NIBBLE_SETS=0/1, read once here — a live sampler never changes the form of a vertex
+    {
+        const char *e = getenv("BT_GIBBS_NIBBLE_SETS");
+        P.nibble_sets = e ? (atoi(e) != 0 ? 1u : 0u) : kNibbleSetsDefault;
     }
     for (uint32_t s = 0; s < S; ++s) P.gender[s] = params->gender[s] ? 1 : 0;
 
@@ -3042,6 +3058,25 @@ static int result_offsets(bt_gibbs *g, std::vector<uint64_t> &dip_off, std::vect
     return BT_OK;
 }
 
+int bt_gibbs_sparse_forms(bt_gibbs *g, uint32_t *h_form) {
+    if (!g || !h_form) return fail("bt_gibbs_sparse_forms: null argument");
+    if (chain_in_flight(g)) return fail("bt_gibbs_sparse_forms: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
+    BT_HIP(hipSetDevice(g->ctx->device));
+    hipStream_t st = g->ctx->stream;
+    const uint32_t C = g->C;
+    uint32_t *d_f = nullptr;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_f), (size_t)C * 4));
+    struct Free {
+        void *p;
+        ~Free() { (void)hipFree(p); }
+    } fr{d_f};
+    hipLaunchKernelGGL(sparse_form_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const TileDesc *)g->d_tiles, g->d_pool, (const ClusterLoc *)g->d_loc, C, d_f);
+    BT_CHECK_LAUNCH();
+    BT_HIP(hipMemcpyAsync(h_form, d_f, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+    BT_HIP(hipStreamSynchronize(st));
+    return BT_OK;
+}
+
 int bt_gibbs_result_sizes(bt_gibbs *g, uint64_t *num_diplotype_entries, uint64_t *num_allele_cells) {
     if (!g) return fail("bt_gibbs_result_sizes: null handle");
     if (chain_in_flight(g)) return fail("bt_gibbs_result_sizes: a resident noise chain is in progress (bt_gibbs_noise_chain_end): the call would wait behind its launch");
@@ -3513,6 +3548,18 @@ int bt_diag_uset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *v
     *n = j;
     return BT_OK;
 }
+
+// the same container as one packed word (NSet, universes 1 .. NSET_MAX), with the two positional operations the frequency draw uses
+int bt_diag_nset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *values, uint64_t num_ops, uint32_t *h_order, uint32_t *n, uint32_t *h_at) {
+    if ((num_ops && (!ops || !values)) || !h_order || !n) return fail("bt_diag_nset_replay: null argument");
+    switch (set_replay(true, universe, ops, values, num_ops, h_order, n, h_at)) {
+        case 0: return BT_OK;
+        case 1: return fail("bt_diag_nset_replay: value outside the universe");
+        case 2: return fail("bt_diag_nset_replay: the packed form holds universes of 1 to 13 elements (NSET_MAX): larger sets stay on the lists (bt_diag_uset_replay)");
+        default: return fail("bt_diag_nset_replay: unknown operation");
+    }
+}
+uint32_t bt_diag_nset_max(void) { return NSET_MAX; }
 
 #ifdef BT_PROF
 int bt_diag_prof(unsigned long long *h_out16, int reset) {

@@ -66,6 +66,9 @@ constexpr unsigned MT_RING_PAD = MT_PAD;
 // starts without a round trip to HBM
 enum { SC_USE_MULTI = 0, SC_NSUB_U, SC_NSUB_M, SC_HAP_COUNT, SC_CONSTRUCTED, SC_DIP_ENTRIES, SC_DIP_OVERFLOW, SC_IS_SPARSE, SC_FND_AVAIL, SC_UC_DIRTY, SC_H, SC_V, SC_NM, SC_COUNT };
 constexpr uint32_t SC_STATE_COUNT = SC_H;   // slots a (re)constructed genotyper resets
+// SC_IS_SPARSE: 0 the dense frequency distribution; otherwise the sparse one, and the form of its zero and plus sets (Vx::HSet): the form is a property of
+// the vertex — SPARSE_PACKED for 3 <= H <= NSET_MAX when the sampler was created with GParams::nibble_sets — stored with the sets it describes
+constexpr uint32_t SPARSE_LISTS = 1, SPARSE_PACKED = 2;
 
 // arrays of a tile.  [V] = per vertex (index v*LEN + i), [G] = per group
 enum TileArr {
@@ -205,6 +208,7 @@ struct GParams {
     uint32_t lgamma_n, gamma_n;
     uint32_t bulk_subset;              // BT_GIBBS_BULK_SUBSET: the chain starts of OP_RUN draw the k-mer subset across a group's lockstep copies (sample_kmer_subset)
     uint32_t team_apply;               // BT_GIBBS_TEAM_APPLY: the per-sample bookkeeping of a visit is dealt to the teams / copies of a narrow tile's group instead of replayed by each (sample_diplotypes)
+    uint32_t nibble_sets;              // BT_GIBBS_NIBBLE_SETS: a sparse cluster of 3 .. NSET_MAX haplotypes keeps its zero and plus sets as packed words (SPARSE_PACKED), chosen when its genotyper is constructed
 };
 
 extern __shared__ __attribute__((aligned(16))) uint8_t bt_lds_raw[];
@@ -337,9 +341,17 @@ struct Vx {   // vertex context: tile + vertex index + the lane's true dimension
     __device__ inline SPtrF<uint32_t, LANES> obs() const { return t.harr<uint32_t>(A_OBS, v, d().Hm); }
     __device__ inline SPtrF<uint8_t, LANES> nz() const { return t.harr<uint8_t>(A_NZ, v, d().Hm); }
     __device__ inline SPtrF<uint32_t, LANES> unext() const { return t.harr<uint32_t>(A_UNEXT, v, d().Hm); }
-    typedef USetP<SPtrF<uint32_t, LANES>> HSet;
-    __device__ inline HSet zero_set() const { return HSet{t.harr<uint32_t>(A_ZHDR, v, 4), t.harr<uint32_t>(A_ZBKT, v, d().Bcap), unext(), d().Bcap}; }
-    __device__ inline HSet plus_set() const { return HSet{t.harr<uint32_t>(A_PHDR, v, 4), t.harr<uint32_t>(A_PBKT, v, d().Bcap), unext(), d().Bcap}; }
+    // The two sets of a sparse frequency distribution, in the form the vertex keeps them in for its whole life (SC_IS_SPARSE, written when the genotyper
+    // is constructed): lists (uset_*), or — SPARSE_PACKED — the four header words alone: [0], [1] the NSet word, [2] its size (where uset_size reads it
+    // too), the bucket and link words unused.  Every user goes through the hset_* operations below, which hold both forms.
+    struct HSet : USetP<SPtrF<uint32_t, LANES>> {
+        uint32_t packed;
+    };
+    __device__ inline HSet set_view(int hdr, int bkt) const {
+        return HSet{{t.harr<uint32_t>(hdr, v, 4), t.harr<uint32_t>(bkt, v, d().Bcap), unext(), d().Bcap}, sc()[SC_IS_SPARSE] == SPARSE_PACKED ? 1u : 0u};
+    }
+    __device__ inline HSet zero_set() const { return set_view(A_ZHDR, A_ZBKT); }
+    __device__ inline HSet plus_set() const { return set_view(A_PHDR, A_PBKT); }
     __device__ inline TPtr<uint32_t> hvcount() const { return a<uint32_t>(A_HVCOUNT, (uint32_t)d().Hm * d().Vm); }
     // the [S][D] table of unique-k-mer sums.  Wide tiles: lane-interleaved.  Narrow tiles (whose lanes would leave most of every
     // 64-lane row unused): each lane's table contiguous, so a tile pays for its own lanes only and even 256 candidates x 30 samples
@@ -605,6 +617,101 @@ __device__ inline uint8_t multi_mult(const Vx &c, const GParams BT_CAS &P, uint3
     return (uint8_t)(shared - dip_mult(c, k, p1, p2) + dip_mult(c, k, h1, h2) + icm);
 }
 
+// ---- operations on a vertex's zero / plus set (Vx::HSet), both forms in one place ---------------------------------------------------
+// A user opens a set where a phase starts, works on it and closes it where the phase ends.  Lists: every operation goes to memory (uset_*), the
+// opened value carries nothing.  Packed: hset_open loads the word and the size, the operations are register arithmetic on them, hset_close stores
+// them — nothing stays in registers between phases.
+__device__ inline NSet hset_open(const Vx::HSet &s) {
+    NSet v{0, 0};
+    if (s.packed) {
+        const uint32_t lo = s.hdr[0], hi = s.hdr[1];
+        v.n = s.hdr[2];
+        v.w = (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    return v;
+}
+__device__ inline void hset_close(const Vx::HSet &s, const NSet &v) {
+    if (s.packed) {
+        s.hdr[0] = (uint32_t)v.w;
+        s.hdr[1] = (uint32_t)(v.w >> 32);
+        s.hdr[2] = v.n;
+    }
+}
+__device__ inline void hset_init(const Vx::HSet &s) {   // a constructed, empty set (no open / close)
+    if (s.packed) s.hdr[0] = s.hdr[1] = s.hdr[2] = s.hdr[3] = 0;
+    else uset_init(s);
+}
+__device__ inline uint32_t hset_size(const Vx::HSet &s, const NSet &v) { return s.packed ? v.n : uset_size(s); }
+__device__ inline void hset_clear(const Vx::HSet &s, NSet &v) {
+    if (s.packed) nset_clear(v);
+    else uset_clear(s);
+}
+__device__ inline void hset_insert(const Vx::HSet &s, NSet &v, uint32_t e) {
+    if (s.packed) nset_insert(v, e);
+    else uset_insert(s, e);
+}
+__device__ inline void hset_erase(const Vx::HSet &s, NSet &v, uint32_t e) {
+    if (s.packed) nset_erase(v, e);
+    else uset_erase(s, e);
+}
+// clear, then insert 0 .. H-1
+__device__ inline void hset_fill(const Vx::HSet &s, NSet &v, uint32_t H) {
+    if (s.packed) v = nset_descending(H);
+    else {
+        uset_clear(s);
+        for (uint32_t h = 0; h < H; ++h) uset_insert(s, h);
+    }
+}
+// "it = begin(); advance(it, pos); e = *it; erase(it)": the element at a position leaves the set
+__device__ inline uint32_t hset_take_at(const Vx::HSet &s, NSet &v, uint32_t pos) {
+    uint32_t e;
+    if (s.packed) {
+        e = nset_at(v, pos);
+        nset_erase_at(v, pos);
+    } else {
+        e = uset_begin(s);
+        for (uint32_t i = 0; i < pos; ++i) e = s.next[e];
+        uset_erase(s, e);
+    }
+    return e;
+}
+// iteration: for (HCur it = hset_first(s, v); it.e != US_NONE; hset_next(s, it))
+struct HCur {
+    uint32_t e;      // the element, US_NONE at the end
+    uint64_t rest;   // packed: the fields after it
+    uint32_t left;   // packed: elements from it on
+};
+__device__ inline HCur hset_first(const Vx::HSet &s, const NSet &v) {
+    if (s.packed) return HCur{v.n ? (uint32_t)v.w & 15u : US_NONE, v.w >> 4, v.n};
+    return HCur{uset_begin(s), 0, 0};
+}
+__device__ inline void hset_next(const Vx::HSet &s, HCur &it) {
+    if (s.packed) {
+        it.left -= 1;
+        it.e = it.left ? (uint32_t)it.rest & 15u : US_NONE;
+        it.rest >>= 4;
+    } else
+        it.e = s.next[it.e];
+}
+// The end of a frequency draw moves every element of plus to zero in plus's iteration order.  The lists of the two sets share their link words, so the
+// order is recorded (lists: in `rec`, packed: the word itself) before plus is cleared; hset_recorded(.., i) is its i-th element.
+struct HOrder {
+    uint64_t w;
+    uint32_t n;
+};
+__device__ inline HOrder hset_record_clear(const Vx::HSet &s, NSet &v, SPtrF<uint16_t, LANES> rec) {
+    HOrder o{v.w, v.n};
+    if (!s.packed) {
+        o.n = 0;
+        for (uint32_t e = uset_begin(s); e != US_NONE; e = s.next[e]) rec[o.n++] = (uint16_t)e;
+    }
+    hset_clear(s, v);
+    return o;
+}
+__device__ inline uint32_t hset_recorded(const Vx::HSet &s, const HOrder &o, SPtrF<uint16_t, LANES> rec, uint32_t i) {
+    return s.packed ? (uint32_t)(o.w >> (4u * i)) & 15u : (uint32_t)rec[i];
+}
+
 // ---- FrequencyDistribution::reset / SparseFrequencyDistribution::reset (FrequencyDistribution.cpp:49-54,104-115) ----
 __device__ inline void freq_reset(const Vx &c) {
     const double f = 1 / (double)c.H;
@@ -619,10 +726,12 @@ __device__ inline void freq_reset(const Vx &c) {
         nz[h] = 1;
     }
     if (c.sc()[SC_IS_SPARSE]) {
-        uset_clear(c.plus_set());
-        Vx::HSet z = c.zero_set();
-        uset_clear(z);
-        for (uint32_t h = 0; h < c.H; ++h) uset_insert(z, h);
+        const Vx::HSet plus = c.plus_set(), zero = c.zero_set();
+        NSet pv = hset_open(plus), zv = hset_open(zero);
+        hset_clear(plus, pv);
+        hset_fill(zero, zv, c.H);
+        hset_close(plus, pv);
+        hset_close(zero, zv);
     }
 }
 
@@ -740,13 +849,14 @@ __device__ BT_NOINLINE void genotyper_construct(Env env, uint32_t vtx, uint32_t 
     c.rng_seed(1, prng_seed);
     c.fnd_saved() = 0;
     sc[SC_FND_AVAIL] = 0;
-    sc[SC_IS_SPARSE] = cover > 0 ? 1u : 0u;   // HaplotypeFrequencyDistribution.cpp:79-89
+    // HaplotypeFrequencyDistribution.cpp:79-89; the form of the sparse distribution's sets is chosen here, by the vertex alone, and read from this word ever after
+    sc[SC_IS_SPARSE] = cover > 0 ? (P.nibble_sets != 0 && c.H >= 3u && c.H <= NSET_MAX ? SPARSE_PACKED : SPARSE_LISTS) : 0u;
     if (cover > 0) {
         const double sp = (double)cover / (double)c.H;
         const double cap = 1 - BT_DBL_EPS * 100;
         c.sparsity() = sp < cap ? sp : cap;    // FrequencyDistribution.cpp:98
-        uset_init(c.zero_set());
-        uset_init(c.plus_set());
+        hset_init(c.zero_set());
+        hset_init(c.plus_set());
     }
     freq_reset(c);
     sc[SC_CONSTRUCTED] = 1;
@@ -1273,8 +1383,12 @@ __device__ inline void hfd_increment(const Vx &c, uint16_t h, bool is_sparse, ui
     if (is_sparse && o == 0) {   // SparseFrequencyDistribution::incrementObservationCount (:198-207)
         // the reference inserts into plus, then erases from zero; the sets share their `next` words here, so leave
         // the zero list first (the resulting containers are identical)
-        uset_erase(c.zero_set(), h);
-        uset_insert(c.plus_set(), h);
+        const Vx::HSet zero = c.zero_set(), plus = c.plus_set();
+        NSet zv = hset_open(zero), pv = hset_open(plus);
+        hset_erase(zero, zv, h);
+        hset_insert(plus, pv, h);
+        hset_close(zero, zv);
+        hset_close(plus, pv);
     }
     obs[h] = o + 1;
 }
@@ -2230,9 +2344,8 @@ __device__ BT_SWEEPFN void sample_haplotype_frequencies(Env env, uint32_t vtx) {
                 logf[h] = bt_log(f);
             }
         } else {
-            Vx::HSet plus = c.plus_set(), zero = c.zero_set();
-            SPtrF<uint32_t, LANES> unext = c.unext();
-            const uint32_t plus_size = uset_size(plus);
+            const Vx::HSet plus = c.plus_set(), zero = c.zero_set();
+            const uint32_t plus_size = uset_size(plus);   // (both forms keep the size in the same header word)
             // cached_simplex_prob_vectors[sum_observation_counts][|plus| - 1] (FrequencyDistribution.cpp:211-229): the vector is a pure
             // function of (n_obs, |plus|), so caching it or not is invisible; cached when the tile reserved room for it
             uint32_t len;
@@ -2264,24 +2377,31 @@ __device__ BT_SWEEPFN void sample_haplotype_frequencies(Env env, uint32_t vtx) {
                 while (ub < len && !(u < vec[ub])) ++ub;
             const uint32_t simplex_size = ub + plus_size;
             double norm = 0;
-            for (uint32_t e = uset_begin(plus); e != US_NONE; e = unext[e]) {
-                const double f = rng_gamma_count(rng, nd, P, obs[e]);
-                freq[e] = f;
-                norm += f;
-                nz[e] = 2;   // selected in this call (turned into 1 below)
+            {
+                const NSet pv = hset_open(plus);
+                for (HCur it = hset_first(plus, pv); it.e != US_NONE; hset_next(plus, it)) {
+                    const uint32_t e = it.e;
+                    const double f = rng_gamma_count(rng, nd, P, obs[e]);
+                    freq[e] = f;
+                    norm += f;
+                    nz[e] = 2;   // selected in this call (turned into 1 below)
+                }
             }
             PROF(22);
-            while (uset_size(plus) < simplex_size) {
-                const uint32_t pos = rng_uniform_int(rng, uset_size(zero));   // uniform_int(0, |zero| - 1)
-                uint32_t e = uset_begin(zero);
-                for (uint32_t i = 0; i < pos; ++i) e = unext[e];
-                const double f = rng_gamma_count(rng, nd, P, 0u);
-                freq[e] = f;
-                norm += f;
-                nz[e] = 2;
-                // the two sets share the `next` words: leave the zero list before entering the plus list
-                uset_erase(zero, e);
-                uset_insert(plus, e);
+            {
+                NSet pv = hset_open(plus), zv = hset_open(zero);
+                while (hset_size(plus, pv) < simplex_size) {
+                    const uint32_t pos = rng_uniform_int(rng, hset_size(zero, zv));   // uniform_int(0, |zero| - 1)
+                    // the lists of the two sets share the `next` words: the element leaves zero before it enters plus
+                    const uint32_t e = hset_take_at(zero, zv, pos);
+                    const double f = rng_gamma_count(rng, nd, P, 0u);
+                    freq[e] = f;
+                    norm += f;
+                    nz[e] = 2;
+                    hset_insert(plus, pv, e);
+                }
+                hset_close(plus, pv);
+                hset_close(zero, zv);
             }
             PROF(23);
             // "for z in zero: freq = 0, nz = 0, obs = 0": the zero set is exactly the haplotypes not selected above, so the reset
@@ -2319,17 +2439,18 @@ __device__ BT_SWEEPFN void sample_haplotype_frequencies(Env env, uint32_t vtx) {
             // "for p in plus: freq /= norm; zero.insert(p); obs = 0" then plus.clear(): record the plus iteration order
             // first (shared `next` words), clear plus, then insert into zero in that order — same final containers
             SPtrF<uint16_t, LANES> nzl = c.nzlist();
-            uint32_t np = 0;
-            for (uint32_t e = uset_begin(plus); e != US_NONE; e = unext[e]) nzl[np++] = (uint16_t)e;
-            uset_clear(plus);
-            for (uint32_t i = 0; i < np; ++i) {
-                const uint32_t e = nzl[i];
+            NSet pv = hset_open(plus), zv = hset_open(zero);
+            const HOrder ord = hset_record_clear(plus, pv, nzl);
+            for (uint32_t i = 0; i < ord.n; ++i) {
+                const uint32_t e = hset_recorded(plus, ord, nzl, i);
                 const double f = freq[e] / norm;
                 freq[e] = f;
                 c.logf()[e] = bt_log(f);
-                uset_insert(zero, e);
+                hset_insert(zero, zv, e);
                 obs[e] = 0;
             }
+            hset_close(plus, pv);
+            hset_close(zero, zv);
         }
         mt_close(rng);
     }

@@ -1002,4 +1002,112 @@ BT_HD uint32_t uset_begin(USetP<PT> s) { return s.hdr[1]; }
 template <class PT>
 BT_HD uint32_t uset_size(USetP<PT> s) { return s.hdr[2]; }
 
+// ------------------------------------------------------------------------------------------------------------
+// The same container over a small universe, as one 64-bit word of 4-bit fields: field p is the p-th element of the iteration order.
+// Why this is the whole container up to NSET_MAX elements: an empty set's first insert asks for at least 11 buckets and the next entry of the
+// growth chain is 13 (uset_insert, uset_next_bucket_count); a set never holds more than its universe, so with universe <= 13 the load never
+// passes 13 and the set never rehashes again; uset_clear keeps the bucket count.  With 13 buckets every element e < 13 is alone in bucket
+// e % 13 == e, so an insert always takes the "empty bucket" branch — the new element becomes the FRONT of the list — and an erase unlinks its
+// element and nothing else.  The order is therefore "push front / remove" whatever the history.  From 14 elements on the 14th insert
+// rehashes to 29 buckets, the rehash reverses the list, and the order depends on the history: NSET_MAX is 13, the first bucket count, and
+// not the 16 fields a word has room for (tools/nibble_sets_host_check.cpp and tests/test_nibble_sets_cpu.py compare against uset_*).
+// ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t NSET_MAX = 13;
+constexpr uint64_t NSET_ONES = 0x1111111111111111ull;
+struct NSet {
+    uint64_t w;   // fields at and above `n` are zero
+    uint32_t n;
+};
+BT_HD void nset_clear(NSet &s) {
+    s.w = 0;
+    s.n = 0;
+}
+BT_HD uint32_t nset_size(const NSet &s) { return s.n; }
+// the element at position pos < n of the iteration order (begin is position 0)
+BT_HD uint32_t nset_at(const NSet &s, uint32_t pos) { return (uint32_t)(s.w >> (4u * pos)) & 15u; }
+// insert an element that is not in the set: it becomes the first
+BT_HD void nset_insert(NSet &s, uint32_t e) {
+    s.w = (s.w << 4) | (uint64_t)e;
+    s.n += 1;
+}
+BT_HD void nset_erase_at(NSet &s, uint32_t pos) {   // pos < n
+    const uint64_t low = s.w & ((1ull << (4u * pos)) - 1ull);
+    s.w = ((s.w >> (4u * pos + 4u)) << (4u * pos)) | low;
+    s.n -= 1;
+}
+// position of an element that is in the set: the zero field of w ^ eeee..e, the fields that hold no element masked out; a borrow of the
+// subtraction only travels upwards, so the lowest hit is exact
+BT_HD uint32_t nset_find(const NSet &s, uint32_t e) {
+    const uint64_t x = (s.w ^ ((uint64_t)e * NSET_ONES)) | ~((1ull << (4u * s.n)) - 1ull);   // (n <= 13: the shift stays below 64)
+    const uint64_t hit = (x - NSET_ONES) & ~x & (NSET_ONES << 3);
+    return (uint32_t)__builtin_ctzll(hit) >> 2;
+}
+BT_HD void nset_erase(NSet &s, uint32_t e) { nset_erase_at(s, nset_find(s, e)); }   // e is in the set
+// the set after inserting 0 .. universe-1 into an empty one: universe-1, ..., 0
+BT_HD NSet nset_descending(uint32_t universe) { return NSet{universe ? 0x0123456789ABCDEFull >> (4u * (16u - universe)) : 0ull, universe}; }
+// "for e in from: to.insert(e)" followed by from.clear(): the reversed order of `from` in front of `to`
+BT_HD void nset_move_all(NSet &to, NSet &from) {
+    for (uint32_t i = 0; i < from.n; ++i) nset_insert(to, nset_at(from, i));
+    nset_clear(from);
+}
+// host replay of an operation list on one set in either form (bt_diag_nset_replay, tools/nibble_sets_host_check.cpp).  ops[i]: 0 insert values[i] (ignored
+// when present), 1 erase values[i] (ignored when absent), 2 clear, 3 erase the element at position values[i], 4 read the element at position values[i]
+// (3 and 4 ignored at a position >= size).  at[i] (may be null): the element of an executed op 3 / 4, US_NONE otherwise.  Afterwards the iteration order in
+// order[0 .. *n).  Returns 0, or 1: a value outside the universe, 2: the packed form does not hold this universe, 3: unknown operation.
+__host__ inline int set_replay(bool packed, uint32_t universe, const uint8_t *ops, const uint32_t *values, uint64_t num_ops, uint32_t *order, uint32_t *n, uint32_t *at) {
+    if (packed && (universe == 0 || universe > NSET_MAX)) return 2;
+    const uint32_t cap = uset_bucket_capacity(universe);
+    uint32_t hdr[4], *bkt = new uint32_t[cap](), *next = new uint32_t[universe ? universe : 1]();
+    uint8_t *present = new uint8_t[universe ? universe : 1]();
+    USet l{sptr1(hdr), sptr1(bkt), sptr1(next), cap};
+    NSet p{0, 0};
+    uset_init(l);
+    int rc = 0;
+    for (uint64_t i = 0; i < num_ops && !rc; ++i) {
+        const uint32_t v = values[i], size = packed ? nset_size(p) : uset_size(l);
+        if (at) at[i] = US_NONE;
+        if (ops[i] == 2) {
+            if (packed) nset_clear(p);
+            else uset_clear(l);
+            for (uint32_t e = 0; e < universe; ++e) present[e] = 0;
+        } else if (ops[i] == 0 || ops[i] == 1) {
+            if (v >= universe) rc = 1;
+            else if (ops[i] == 0 && !present[v]) {
+                if (packed) nset_insert(p, v);
+                else uset_insert(l, v);
+                present[v] = 1;
+            } else if (ops[i] == 1 && present[v]) {
+                if (packed) nset_erase(p, v);
+                else uset_erase(l, v);
+                present[v] = 0;
+            }
+        } else if (ops[i] == 3 || ops[i] == 4) {
+            if (v >= size) continue;
+            uint32_t e;
+            if (packed) e = nset_at(p, v);
+            else {
+                e = uset_begin(l);
+                for (uint32_t j = 0; j < v; ++j) e = next[e];
+            }
+            if (at) at[i] = e;
+            if (ops[i] == 3) {
+                if (packed) nset_erase_at(p, v);
+                else uset_erase(l, e);
+                present[e] = 0;
+            }
+        } else
+            rc = 3;
+    }
+    uint32_t j = 0;
+    if (packed)
+        for (; j < nset_size(p); ++j) order[j] = nset_at(p, j);
+    else
+        for (uint32_t e = uset_begin(l); e != US_NONE; e = next[e]) order[j++] = e;
+    *n = j;
+    delete[] bkt;
+    delete[] next;
+    delete[] present;
+    return rc;
+}
+
 }  // namespace bt

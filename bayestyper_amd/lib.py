@@ -725,6 +725,7 @@ bt_gibbs_noise_chain_step = _sig("bt_gibbs_noise_chain_step", [vp, vp, vp])
 bt_gibbs_noise_chain_end = _sig("bt_gibbs_noise_chain_end", [vp])
 bt_ctx_clone = _sig("bt_ctx_clone", [vp, C.POINTER(vp)])
 bt_gibbs_reset_groups = _sig("bt_gibbs_reset_groups", [vp])
+bt_gibbs_sparse_forms = _sig("bt_gibbs_sparse_forms", [vp, vp])
 bt_gibbs_result_sizes = _sig("bt_gibbs_result_sizes", [vp, u64p, u64p])
 bt_gibbs_result_fetch = _sig("bt_gibbs_result_fetch", [vp] * 7)
 bt_gibbs_result_words = _sig("bt_gibbs_result_words", [vp, C.POINTER(vp), u64p])
@@ -746,6 +747,8 @@ bt_gibbs_create_from_source = _sig("bt_gibbs_create_from_source", [vp, vp, vp, v
 bt_gibbs_state_bytes = _sig("bt_gibbs_state_bytes", [vp, vp, vp, u64p])
 bt_gibbs_state_bytes_from_source = _sig("bt_gibbs_state_bytes_from_source", [vp, vp, vp, C.c_uint32, u64p])
 bt_diag_uset_replay = _sig("bt_diag_uset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p])
+bt_diag_nset_replay = _sig("bt_diag_nset_replay", [C.c_uint32, vp, vp, C.c_uint64, vp, u32p, vp])
+bt_diag_nset_max = _sig("bt_diag_nset_max", [], C.c_uint32)
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
 bt_diag_bulk_bernoulli = _sig("bt_diag_bulk_bernoulli", [C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_int, vp, vp, vp])
 bt_genotype_text_sizes = _sig("bt_genotype_text_sizes", [vp, vp, C.c_uint64, u64p, u64p])
@@ -1302,6 +1305,12 @@ class Gibbs:
         p, n = vp(), C.c_uint64()
         check(bt_gibbs_result_words(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def sparse_forms(self):
+        """bt_gibbs_sparse_forms -> uint32 [C]: 0 dense, 1 sparse on lists, 2 sparse on packed words, 0xFFFFFFFF not constructed"""
+        out = np.zeros(self.C, np.uint32)
+        check(bt_gibbs_sparse_forms(self.h, _np_ptr(out)))
+        return out
 
     def result_words_host(self):
         p, n = self.result_words()

@@ -627,6 +627,9 @@ int bt_gibbs_noise_chain_step(bt_gibbs *g, const double *h_noise, uint64_t *h_hi
 int bt_gibbs_noise_chain_end(bt_gibbs *g);
 /* resetGroup for every group (InferenceEngine.cpp:100-113): genotypers are rebuilt by the next init_chain */
 int bt_gibbs_reset_groups(bt_gibbs *g);
+/* diagnostics: the frequency distribution every cluster's genotyper was constructed with, h_form[C]: 0 dense, 1 sparse with its zero and plus
+ * sets as lists, 2 sparse with the sets as packed words (BT_GIBBS_NIBBLE_SETS, clusters of 3 .. 13 haplotypes), 0xFFFFFFFF not constructed yet */
+int bt_gibbs_sparse_forms(bt_gibbs *g, uint32_t *h_form);
 
 /* Results (collectGenotypes input): per cluster the diplotype sampling frequencies
  * (VariantClusterGenotyper.hpp:112) and the allele k-mer statistics (:104).
@@ -789,6 +792,12 @@ int bt_gibbs_noise_chain(bt_gibbs *g, bt_noise_model *m, uint32_t num_iterations
 /* replay a sequence of operations on the unordered_set<uint> emulation: op[i] = 0 insert, 1 erase, 2 clear;
  * afterwards writes the iteration order to h_order (capacity universe) and its length to *n */
 int bt_diag_uset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *values, uint64_t num_ops, uint32_t *h_order, uint32_t *n);
+/* the same replay on the packed form of the container (one 64-bit word of 4-bit fields; BT_GIBBS_NIBBLE_SETS), which holds universes of
+ * 1 .. bt_diag_nset_max() elements and fails for any other.  Operations as above, plus 3: erase the element at position values[i] of the
+ * iteration order, 4: read the element at position values[i] (both ignored at a position >= size).  h_at (capacity num_ops, may be NULL):
+ * the element of an executed operation 3 or 4, 0xFFFFFFFF for every other operation. */
+int bt_diag_nset_replay(uint32_t universe, const uint8_t *ops, const uint32_t *values, uint64_t num_ops, uint32_t *h_order, uint32_t *n, uint32_t *h_at);
+uint32_t bt_diag_nset_max(void);
 /* draws from the device random-number stack seeded like std::mt19937(seed): kind 0 raw u32, 1 generate_canonical<double,53>,
  * 2 gamma(shape=a, scale=b) with one persistent distribution object, 3 uniform_int(0, a), 4 bernoulli(float a),
  * 5 std::shuffle of 0..a-1 (h_out gets the permutation as doubles, n ignored) */
