@@ -18,6 +18,7 @@
 #include "Comm.hpp"
 #include "KmcFile.hpp"
 #include "Options.hpp"
+#include "ReadsFile.hpp"
 
 namespace bthost {
 
@@ -608,6 +609,21 @@ void KmerCounter::parseSampleKmers(bt_table *table, bt_bloom *path_bloom, Comm *
     const uint64_t world = comm ? (uint64_t)comm->world() : 1, rank = comm ? (uint64_t)comm->rank() : 0;
     for (size_t s = 0; s < samples.size(); s++) {
         std::cout << "[" << getLocalTime() << "] Parsing kmers from sample " << samples[s].name << " ..." << std::endl;
+        if (sampleRoute(samples[s].file) == SampleRoute::Reads) {   // no KMC database: the counts come from the reads themselves (bt_reads_count_host)
+            if (comm) throw std::runtime_error(readsSeveralRanksMessage(samples[s].name));
+            const auto t_scan = std::chrono::steady_clock::now();
+            uint64_t hits = 0;
+            const unsigned threads = getenv("BT_HOST_THREADS") ? (unsigned)std::max(1, atoi(getenv("BT_HOST_THREADS"))) : 1u;
+            const ReadsTotals totals = forEachReadsSlab(samples[s].file, kmer_size, threads, (size_t)32 << 20, [&](const std::string &slab) {
+                uint64_t h = 0;
+                check(bt_reads_count_host(ctx, path_bloom, table, (uint32_t)s, slab.data(), slab.size(), 0, &h), "bt_reads_count_host");
+                hits += h;
+            });
+            const double scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan).count();
+            std::cout << "[" << getLocalTime() << "] Parsed " << totals.bases << " bases (" << hits << " kmer occurrences passed the path kmer filter)" << std::endl;
+            if (getenv("BT_STAGE_TIMES")) std::cerr << "  parse sample k-mers (reads route): " << samples[s].name << " " << totals.bases << " bases in " << scan_s << " s = " << (double)totals.bases / scan_s << " bases/s" << std::endl;
+            continue;
+        }
         KmcFile db(samples[s].file);
         if (db.kmer_length != kmer_size) throw std::runtime_error("KMC database " + samples[s].file + " holds " + std::to_string(db.kmer_length) + "-mers, not " + std::to_string(kmer_size) + "-mers");
         // rank r of w scans records [r * total / w, (r + 1) * total / w): a byte range of the .kmc_suf payload

@@ -19,6 +19,7 @@ struct TableCheckpointInputs {
         bool present = true;   // false: the database is not there (a run that loads the checkpoint does not need it); the line then reads "absent"
         uint64_t total_kmers = 0, suf_bytes = 0, max_count = 0;
         uint32_t counter_size = 0, min_count = 0;
+        std::string reads_identity;   // not empty: the sample has no database and is counted from its reads (ReadsFile.hpp: readsIdentity); the line carries this instead
     };
     struct InputFile {   // variant_clusters.bin, parameter_kmers.fa.gz, intercluster_regions.txt.gz
         std::string what;
@@ -39,6 +40,7 @@ struct TableCheckpointInputs {
 
 inline std::string sampleDbLine(size_t s, const TableCheckpointInputs::SampleDb &db) {
     const std::string name = "sample." + std::to_string(s) + ".kmc=";
+    if (!db.reads_identity.empty()) return name + db.reads_identity;
     if (!db.present) return name + "absent";
     return name + "total_kmers:" + std::to_string(db.total_kmers) + " suf_bytes:" + std::to_string(db.suf_bytes) + " counter_size:" + std::to_string(db.counter_size) +
            " min_count:" + std::to_string(db.min_count) + " max_count:" + std::to_string(db.max_count);

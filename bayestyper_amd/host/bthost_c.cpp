@@ -14,6 +14,7 @@
 #include "KmcFile.hpp"
 #include "KmerHashOrder.hpp"
 #include "Parallel.hpp"
+#include "ReadsFile.hpp"
 #include "InferenceUnit.hpp"
 #include "KmerCounter.hpp"
 #include "Sample.hpp"
@@ -732,6 +733,35 @@ long long bth_parse_sample_kmers(void *ctx, const char *kmc_prefix, void *path_b
             err[err_len - 1] = 0;
         }
         return -1;
+    }
+}
+// ReadsFile: the slabs of one read file, a 0 byte after each -> buf (when it fits); stats[0..1] = bases, reads; returns the bytes needed, or -1 (error text in *err)
+long long bth_reads_file_slabs(const char *path, unsigned kmer_size, unsigned long long slab_bytes, char *buf, unsigned long long cap, unsigned long long *stats, char *err,
+                               unsigned err_len) {
+    try {
+        ReadsFile file(path, kmer_size, (size_t)slab_bytes);
+        std::string all, slab;
+        while (file.next(slab)) {
+            all += slab;
+            all += '\0';
+        }
+        if (stats) {
+            stats[0] = file.bases();
+            stats[1] = file.reads();
+        }
+        return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// readReadsList: the read files of <prefix>.reads, a newline after each -> buf (when it fits); returns the bytes needed, or -1 (error text in *err)
+long long bth_reads_list(const char *prefix, char *buf, unsigned long long cap, char *err, unsigned err_len) {
+    try {
+        std::string all;
+        for (const std::string &f : readReadsList(prefix)) all += f + "\n";
+        return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
     }
 }
 // header fields of a KMC database: out[0..5] = k, mode, counter_size, lut_prefix_length, total_kmers, record_size; 0 on success

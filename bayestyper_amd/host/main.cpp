@@ -48,6 +48,7 @@
 #include "KmerHashOrder.hpp"
 #include "Options.hpp"
 #include "Parallel.hpp"
+#include "ReadsFile.hpp"
 #include "Sample.hpp"
 #include "StageTimes.hpp"
 #include "TableCheckpoint.hpp"
@@ -324,7 +325,8 @@ std::string tableCheckpointManifest(unsigned kmer_size, const std::vector<Sample
         TableCheckpointInputs::SampleDb db;
         db.name = sample.name;
         struct stat sb;
-        if (databases_optional && (stat((sample.file + ".kmc_pre").c_str(), &sb) != 0 || stat((sample.file + ".kmc_suf").c_str(), &sb) != 0)) db.present = false;
+        if (sampleRoute(sample.file) == SampleRoute::Reads) db.reads_identity = readsIdentity(sample.file);
+        else if (databases_optional && (stat((sample.file + ".kmc_pre").c_str(), &sb) != 0 || stat((sample.file + ".kmc_suf").c_str(), &sb) != 0)) db.present = false;
         else {
             const KmcFile kmc(sample.file);
             if (stat(kmc.suffix_file().c_str(), &sb) != 0) throw std::runtime_error("Unable to open file " + kmc.suffix_file());
@@ -481,7 +483,11 @@ int runGenotype(int argc, char *const argv[], unsigned kmer_size) {
         st.reset(new StageScope("count inter-cluster k-mers"));
         kmer_counter.countInterclusterKmers(kmer_hash.h, path_kmer_bloom->h, intercluster_regions_dir_prefix, chromosomes, chrom_ploidy);
         std::cout << std::endl;
-        st.reset(new StageScope("parse sample k-mers (KMC scan incl. H2D)"));
+        size_t reads_samples = 0;
+        for (const Sample &sample : samples) reads_samples += sampleRoute(sample.file) == SampleRoute::Reads;
+        st.reset(new StageScope(reads_samples == 0   ? "parse sample k-mers (KMC scan incl. H2D)"
+                                : reads_samples == S ? "parse sample k-mers (reads scan incl. reader + H2D)"
+                                                     : "parse sample k-mers (KMC scans + reads scans incl. reader + H2D)"));
         kmer_counter.parseSampleKmers(kmer_hash.h, path_kmer_bloom->h, comm.get());
         path_kmer_bloom.reset();
         if (!checkpoint_file.empty() && rank == 0) {   // (several ranks: after the merge every rank holds the whole table)
@@ -866,6 +872,17 @@ std::vector<pid_t> startRanks(int argc, char *const argv[]) {
     const int n = gpus ? atoi(gpus) : 1;
     if (n <= 1 || getenv("BT_WORLD")) return children;
     if (argc < 2 || std::strcmp(argv[1], "genotype") != 0) return children;
+    // a reads sample is refused here, before a rank is started or a device opened (KmerCounter::parseSampleKmers refuses ranks started by someone else)
+    for (int i = 2; i + 1 < argc; i++)
+        if (std::strcmp(argv[i], "-s") == 0 || std::strcmp(argv[i], "--samples-file") == 0) {
+            std::vector<Sample> samples;
+            try {
+                samples = readSamples(argv[i + 1]);
+            } catch (const std::exception &) {   // (the run itself reports an unreadable samples file)
+            }
+            for (const Sample &sample : samples)
+                if (sampleRoute(sample.file) == SampleRoute::Reads) throw std::runtime_error(readsSeveralRanksMessage(sample.name));
+        }
     std::string prefix = "bayestyper";   // -o / --output-prefix (main.cpp:379)
     for (int i = 2; i + 1 < argc; i++)
         if (std::strcmp(argv[i], "-o") == 0 || std::strcmp(argv[i], "--output-prefix") == 0) prefix = argv[i + 1];

@@ -3,7 +3,11 @@
 // `bayesTyper cluster` reads (Sample.cpp / KmerCounter.cpp:59-103).  Same options (-k/--kmc-table-prefix, -p/--num-threads,
 // --false-positive-rate 0.001), same progress lines, byte-identical output files (insertion is an order-independent OR).  The records are
 // streamed from the memory-mapped .kmc_suf through the GPU in chunks (bt_kmc_scan_make_bloom); there is no CPU path.
+// -r/--reads-prefix <prefix> is the alternative to -k for a sample without a KMC database: the read files listed in <prefix>.reads (FASTA / FASTQ, plain or
+// gzip) are streamed through bt_reads_make_bloom_host; the filter is sized by --num-kmers, or by a first pass that estimates the number of distinct k-mers
+// (bt_reads_sketch_host).  With the N of the sample's KMC database the bytes written are those of -k.
 // The VCF utilities of bayesTyperTools (convertAllele, combine, filter, annotate, addAttributes) are not part of this build.
+#include <cmath>
 #include <cstring>
 #include <iostream>
 #include <stdexcept>
@@ -11,6 +15,7 @@
 #include "../../include/btgpu.h"
 #include "KmcFile.hpp"
 #include "Options.hpp"
+#include "ReadsFile.hpp"
 
 using namespace bthost;
 
@@ -21,18 +26,61 @@ void check(int rc, const char *what) {
     if (rc != BT_OK) throw std::runtime_error(std::string(what) + ": " + bt_last_error());
 }
 
+// makeBloom -r: MakeBloom.cpp:200-295 with the reads in place of the KMC table
+int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kmers, unsigned threads, unsigned kmer_size) {
+    const size_t slab_bytes = (size_t)32 << 20;
+    bt_ctx *ctx = nullptr;
+    const char *dev = getenv("BT_DEVICE");
+    check(bt_ctx_create(dev ? atoi(dev) : 0, &ctx), "bt_ctx_create");
+    bt_bloom *bloom = nullptr;
+    try {
+        if (num_kmers == 0) {
+            std::cout << stamp() << "Estimating the number of distinct kmers in the reads of " << prefix << ".reads ..." << std::endl;
+            std::vector<uint8_t> registers(65536, 0);
+            forEachReadsSlab(prefix, kmer_size, threads, slab_bytes,
+                             [&](const std::string &slab) { check(bt_reads_sketch_host(ctx, slab.data(), slab.size(), kmer_size, 0, registers.data()), "bt_reads_sketch_host"); });
+            double estimate = 0;
+            check(bt_reads_sketch_estimate(registers.data(), &estimate), "bt_reads_sketch_estimate");
+            num_kmers = std::max<uint64_t>(1, (uint64_t)std::ceil(estimate));
+            std::cout << stamp() << "Estimated " << num_kmers << " distinct kmers\n" << std::endl;
+        } else
+            std::cout << stamp() << "Using the given number of " << num_kmers << " distinct kmers\n" << std::endl;
+        std::cout << stamp() << "Making bloom filter of " << num_kmers << " kmers with a false positive rate of " << fpr << " ...\n" << std::endl;
+        check(bt_bloom_create(ctx, num_kmers, fpr, kmer_size, 0, &bloom), "bt_bloom_create");   // KmerBloom(N, fpr), MakeBloom.cpp:221
+        const ReadsTotals totals = forEachReadsSlab(prefix, kmer_size, threads, slab_bytes, [&](const std::string &slab) {
+            check(bt_reads_make_bloom_host(ctx, bloom, slab.data(), slab.size(), kmer_size, 0), "bt_reads_make_bloom_host");
+        });
+        std::cout << stamp() << "Parsed " << totals.bases << " bases of " << totals.reads << " reads in " << totals.files << " file(s)" << std::endl;
+        std::cout << "\n" << stamp() << "Saving bloom filter to " << prefix << " ..." << std::endl;
+        check(bt_bloom_save(bloom, prefix.c_str()), "bt_bloom_save");
+        std::cout << stamp() << "Completed saving bloom filter\n" << std::endl;
+    } catch (...) {
+        if (bloom) bt_bloom_destroy(bloom);
+        bt_ctx_destroy(ctx);
+        throw;
+    }
+    bt_bloom_destroy(bloom);
+    bt_ctx_destroy(ctx);
+    return 0;
+}
+
 int runMakeBloom(int argc, char *const argv[], unsigned kmer_size) {
     const std::vector<OptionSpec> specs = {
-        {"kmc-table-prefix", 'k', "Required", true, false, "", "KMC kmer table prefix. Output is written as <kmc-table-prefix>.bloomMeta and <kmc-table-prefix>.bloomData.", 's'},
+        {"kmc-table-prefix", 'k', "Required (one of)", false, false, "", "KMC kmer table prefix. Output is written as <kmc-table-prefix>.bloomMeta and <kmc-table-prefix>.bloomData.", 's'},
+        {"reads-prefix", 'r', "Required (one of)", false, false, "", "sample prefix without a KMC table: the read files (FASTA/FASTQ, plain or gzip) listed in <reads-prefix>.reads are used. Output is written as <reads-prefix>.bloomMeta and <reads-prefix>.bloomData.", 's'},
         {"num-threads", 'p', "General", false, false, "1", "number of threads used (+= 1 I/O thread).", 'u'},
         {"false-positive-rate", 0, "Parameters", false, false, "0.001", "bloom filter false positive rate.", 'f'},
+        {"num-kmers", 0, "Parameters", false, false, "0", "number of distinct kmers the filter is made for (--reads-prefix only; 0 = estimate it in a first pass over the reads).", 'u'},
     };
     OptionsContainer options("makeBloom", BT_VERSION, getLocalTime(), kmer_size);
     if (options.parse(argc, argv, specs, "## BayesTyperTools makeBloom ##")) return 1;
-    const std::string prefix = options.getString("kmc-table-prefix");
+    const std::string prefix = options.getString("kmc-table-prefix"), reads_prefix = options.getString("reads-prefix");
+    if (prefix.empty() == reads_prefix.empty()) throw std::runtime_error("exactly one of the options '--kmc-table-prefix' and '--reads-prefix' is required");
     const float fpr = options.getFloat("false-positive-rate");
     if (!(fpr > 0) || !(fpr < 1)) throw std::runtime_error("--false-positive-rate must be in (0, 1)");
     std::cout << stamp() << "Running BayesTyperTools (" << BT_VERSION << ") makeBloom ...\n" << std::endl;
+    if (!reads_prefix.empty()) return runMakeBloomFromReads(reads_prefix, fpr, options.getUInt("num-kmers"), (unsigned)options.getUInt("num-threads"), kmer_size);
+    if (options.getUInt("num-kmers")) throw std::runtime_error("--num-kmers goes with --reads-prefix: a KMC table states its number of kmers");
     KmcFile db(prefix);   // throws "Unable to open KMC table ..." like MakeBloom.cpp:206-210
     if (db.kmer_length != kmer_size) throw std::runtime_error("KMC table " + prefix + " holds " + std::to_string(db.kmer_length) + "-mers, not " + std::to_string(kmer_size) + "-mers");
     std::cout << stamp() << "Making bloom filter of " << db.total_kmers << " kmers with a false positive rate of " << fpr << " ...\n" << std::endl;

@@ -112,7 +112,16 @@ bt_kmc_scan_kmer_stats = _sig("bt_kmc_scan_kmer_stats", [vp, vp, C.c_uint64, C.c
 KMER_STATS_PROGRESS = C.CFUNCTYPE(None, C.c_uint64, vp)
 bt_kmc_scan_kmer_stats_file = _sig("bt_kmc_scan_kmer_stats_file", [vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, u64p,
                                                                    KMER_STATS_PROGRESS, vp])
-
+bt_reads_count = _sig("bt_reads_count", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp])
+bt_reads_make_bloom = _sig("bt_reads_make_bloom", [vp, vp, vp, C.c_uint64, C.c_uint32])
+bt_reads_sketch = _sig("bt_reads_sketch", [vp, vp, C.c_uint64, C.c_uint32, vp])
+bt_reads_count_host = _sig("bt_reads_count_host", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, u64p])
+bt_reads_make_bloom_host = _sig("bt_reads_make_bloom_host", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64])
+bt_reads_sketch_host = _sig("bt_reads_sketch_host", [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp])
+bt_reads_sketch_estimate = _sig("bt_reads_sketch_estimate", [vp, f64p])
+bt_diag_reads_kmers = _sig("bt_diag_reads_kmers", [vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, u64p])
+bt_diag_reads_sketch = _sig("bt_diag_reads_sketch", [vp, C.c_uint64, C.c_uint32, vp])
+SKETCH_REGISTERS = 1 << 16
 
 
 class BtError(RuntimeError):
@@ -691,6 +700,93 @@ class KmcScan:
         if self.h:
             bt_kmc_scan_destroy(self.h)
             self.h = None
+
+
+def _reads_text(text):
+    """a reads text (bytes, or a uint8 array) as a contiguous uint8 array"""
+    return np.ascontiguousarray(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text, dtype=np.uint8)
+
+
+def reads_count(ctx, bloom, table, sample_idx, text, host=False, chunk_bytes=0):
+    """bt_reads_count (text uploaded here) or, host=True, bt_reads_count_host (text streamed through the staging slots): every k-mer occurrence of the
+    reads text that hits the path filter is added to the table and to the sample's count -> occurrences that hit"""
+    a = _reads_text(text)
+    if host:
+        hits = C.c_uint64()
+        check(bt_reads_count_host(ctx.h, bloom.h, table.h, sample_idx, _np_ptr(a) if a.size else None, a.size, chunk_bytes, C.byref(hits)))
+        return hits.value
+    d, h = ctx.to_device(a) if a.size else None, ctx.buffer(8).zero()
+    try:
+        check(bt_reads_count(ctx.h, bloom.h, table.h, sample_idx, d.ptr if d else None, a.size, h.ptr))
+        ctx.sync()
+        return int(h.download(np.uint64, 1)[0])
+    finally:
+        h.free()
+        if d:
+            d.free()
+
+
+def reads_make_bloom(ctx, bloom, text, k, host=False, chunk_bytes=0):
+    """bt_reads_make_bloom / bt_reads_make_bloom_host: the k-mers of the reads text are added to a sample's filter"""
+    a = _reads_text(text)
+    if host:
+        check(bt_reads_make_bloom_host(ctx.h, bloom.h, _np_ptr(a) if a.size else None, a.size, k, chunk_bytes))
+        return
+    d = ctx.to_device(a) if a.size else None
+    try:
+        check(bt_reads_make_bloom(ctx.h, bloom.h, d.ptr if d else None, a.size, k))
+        ctx.sync()
+    finally:
+        if d:
+            d.free()
+
+
+def reads_sketch(ctx, text, k, registers=None, host=False, chunk_bytes=0):
+    """bt_reads_sketch / bt_reads_sketch_host: the sketch registers (SKETCH_REGISTERS uint8; `registers`: those of earlier texts, merged into) -> registers"""
+    a = _reads_text(text)
+    reg = np.zeros(SKETCH_REGISTERS, np.uint8) if registers is None else np.array(registers, dtype=np.uint8)
+    assert reg.size == SKETCH_REGISTERS
+    if host:
+        check(bt_reads_sketch_host(ctx.h, _np_ptr(a) if a.size else None, a.size, k, chunk_bytes, _np_ptr(reg)))
+        return reg
+    d, r = ctx.to_device(a) if a.size else None, ctx.to_device(reg)
+    try:
+        check(bt_reads_sketch(ctx.h, d.ptr if d else None, a.size, k, r.ptr))
+        ctx.sync()
+        return r.download(np.uint8, SKETCH_REGISTERS)
+    finally:
+        r.free()
+        if d:
+            d.free()
+
+
+def reads_sketch_estimate(registers):
+    """bt_reads_sketch_estimate (no GPU): the number of distinct k-mers a sketch has seen"""
+    reg = np.ascontiguousarray(registers, dtype=np.uint8)
+    assert reg.size == SKETCH_REGISTERS
+    out = C.c_double()
+    check(bt_reads_sketch_estimate(_np_ptr(reg), C.byref(out)))
+    return out.value
+
+
+def diag_reads_sketch(text, k, registers=None):
+    """bt_diag_reads_sketch (no GPU): the sketch registers of a reads text from the kernels' window code run on the host"""
+    a = _reads_text(text)
+    reg = np.zeros(SKETCH_REGISTERS, np.uint8) if registers is None else np.array(registers, dtype=np.uint8)
+    assert reg.size == SKETCH_REGISTERS
+    check(bt_diag_reads_sketch(_np_ptr(a) if a.size else None, a.size, k, _np_ptr(reg)))
+    return reg
+
+
+def diag_reads_kmers(text, k):
+    """bt_diag_reads_kmers (no GPU): the kernels' window code run on the host -> (canonical k-mers (n, 2) uint64, hashes (n,), index of each window's last byte
+    (n,)), in text order"""
+    a = _reads_text(text)
+    cap = max(a.size, 1)
+    kmers, hashes, ends = np.zeros((cap, 2), np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    n = C.c_uint64()
+    check(bt_diag_reads_kmers(_np_ptr(a) if a.size else None, a.size, k, _np_ptr(kmers), _np_ptr(hashes), _np_ptr(ends), cap, C.byref(n)))
+    return kmers[:n.value].copy(), hashes[:n.value].copy(), ends[:n.value].copy()
 
 
 def kmer_stats_bins(k):

@@ -311,6 +311,43 @@ int bt_kmc_scan_decode(bt_kmc_scan *s, const uint8_t *d_records, uint64_t first_
                        uint64_t *d_kmers, uint32_t *d_counts);
 
 /* ------------------------------------------------------------------------------------------
+ * Reads scan: what the consumers of a sample's KMC database compute, computed from the reads themselves.
+ * A READS TEXT is ASCII bases, one read per line, joined by '\n'.  Every byte outside ACGTacgt (N, the newline, anything else: the rule of
+ * bt_kmers_from_sequence) ends the k-mer window, so no k-mer spans two reads; lower case counts as upper case.  Every window of k valid bases
+ * contributes its canonical k-mer once per occurrence.  All three consumers are commutative: the result depends on the multiset of k-mers only, not
+ * on the order or the cut of the texts handed in.  The d_ calls are asynchronous on the context's stream; k is 1 .. 64.
+ * ---------------------------------------------------------------------------------------- */
+/* KmerCounter::parseSampleKmers + parseSampleKmersCallBack (src/bayesTyper/KmerCounter.cpp:388-524) without the database: every k-mer occurrence of
+ * d_text[0 .. len) that hits path_bloom does table.addKmer(unsorted) + addSampleCount(sample_idx, 1), saturating at 255 — what bt_kmc_scan_run does
+ * with the record (k-mer, min(occurrences, 255)) of a database counted from the same reads.  k is the table's.  d_hit_count (optional, device
+ * uint64) is incremented by the number of OCCURRENCES that hit the filter. */
+int bt_reads_count(bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx, const char *d_text, uint64_t len, uint64_t *d_hit_count);
+/* bayesTyperTools makeBloom (src/bayesTyperTools/MakeBloom.cpp:200-295) without the database: the k-mers of d_text[0 .. len) are added to a sample's
+ * KmerBloom (bt_bloom_create(ctx, num_kmers, fpr, k, 0, ..)): the bits bt_kmc_scan_make_bloom sets from a database of the same reads. */
+int bt_reads_make_bloom(bt_ctx *ctx, bt_bloom *sample_bloom, const char *d_text, uint64_t len, uint32_t k);
+/* A HyperLogLog sketch of the distinct canonical k-mers (the number a KMC database states in its header; makeBloom sizes the filter with it,
+ * MakeBloom.cpp:200-295): 65536 one-byte registers in device memory (4-byte aligned, zeroed by the caller before the first text).  Register = top 16
+ * bits of the splitmix64 finaliser of the k-mer's ntHash, rank = 1 + leading zeros of the other 48 bits (at most 49); a register takes the maximum. */
+int bt_reads_sketch(bt_ctx *ctx, const char *d_text, uint64_t len, uint32_t k, uint8_t *d_registers);
+/* The same three for a text in HOST memory, streamed through the pinned staging slots of bt_kmc_scan_run_host (kept with the context).  Blocking;
+ * chunk_bytes = bytes per transfer (0: default 64 MiB); consecutive transfers overlap by k - 1 bytes and no window is consumed twice, so chunk_bytes
+ * changes no result.  A text must end at a read boundary: nothing is carried from one call to the next.  *h_hit_count (optional) = occurrences that
+ * hit the filter; h_registers (65536 bytes) is read, merged into and written back. */
+int bt_reads_count_host(bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx, const char *h_text, uint64_t len, uint64_t chunk_bytes,
+                        uint64_t *h_hit_count);   /* KmerCounter.cpp:388-524 */
+int bt_reads_make_bloom_host(bt_ctx *ctx, bt_bloom *sample_bloom, const char *h_text, uint64_t len, uint32_t k, uint64_t chunk_bytes);   /* MakeBloom.cpp:200-295 */
+int bt_reads_sketch_host(bt_ctx *ctx, const char *h_text, uint64_t len, uint32_t k, uint64_t chunk_bytes, uint8_t *h_registers);   /* MakeBloom.cpp:200-295 */
+/* Host only, no GPU: the number of distinct k-mers from 65536 registers (the N of MakeBloom.cpp:200-295's KmerBloom(N, fpr)) — the standard
+ * estimator alpha m^2 / sum 2^-register, replaced by linear counting m ln(m / zero registers) at or below 2.5 m. */
+int bt_reads_sketch_estimate(const uint8_t *h_registers, double *out);
+/* Host only, no GPU: the kernels' window code run by one thread over h_text[0 .. len) (what KmerCounter.cpp:388-524 would see record by record, here
+ * occurrence by occurrence).  Window i in text order: h_kmers[2i], h_kmers[2i + 1] = the canonical k-mer (lo, hi), h_hashes[i] = its ntHash,
+ * h_ends[i] = index of its last byte (each array may be NULL).  *n = number of windows; an error when capacity is smaller (n is still set). */
+int bt_diag_reads_kmers(const char *h_text, uint64_t len, uint32_t k, uint64_t *h_kmers, uint64_t *h_hashes, uint64_t *h_ends, uint64_t capacity, uint64_t *n);
+/* Host only, no GPU: the sketch of bt_reads_sketch built by the same window code on one thread; h_registers (65536 bytes) is merged into. */
+int bt_diag_reads_sketch(const char *h_text, uint64_t len, uint32_t k, uint8_t *h_registers);
+
+/* ------------------------------------------------------------------------------------------
  * Path k-mer enumeration over variant-cluster graphs:
  *   VariantClusterGraph::{countPathKmers, classifyPathKmers, getHaplotypeCandidates, updateVariantPathIndices}
  *   (src/bayesTyper/VariantClusterGraph.cpp:800-1184), driven per unit by KmerCounter::{countPathKmers, classifyPathKmers}
