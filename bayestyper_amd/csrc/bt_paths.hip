@@ -1560,6 +1560,8 @@ int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial
     return BT_OK;
 }
 
+uint64_t bt_diag_std_hash_bitset(uint64_t lo, uint64_t hi, unsigned k) { return (k == 0 || k > 64) ? 0 : std_hash_bitset(lo, hi, k); }
+
 int bt_paths_destroy(bt_paths *p) {
     if (!p) return BT_OK;
     (void)hipSetDevice(p->ctx->device);

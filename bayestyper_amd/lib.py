@@ -855,6 +855,7 @@ bt_diag_format_g6 = _sig("bt_diag_format_g6", [vp, C.c_uint64, vp, vp])
 bt_diag_genotype_cluster = _sig("bt_diag_genotype_cluster", [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p])
 bt_diag_kmer_set_order = _sig("bt_diag_kmer_set_order", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
 bt_diag_kmer_set_order_staged = _sig("bt_diag_kmer_set_order_staged", [vp, C.c_uint32, C.c_uint64, C.c_uint, vp, vp])
+bt_diag_std_hash_bitset = _sig("bt_diag_std_hash_bitset", [C.c_uint64, C.c_uint64, C.c_uint], C.c_uint64)
 bt_kmer_set_orders = _sig("bt_kmer_set_orders", [vp, vp, vp, C.c_uint32, C.c_uint, C.c_uint64, C.c_uint32, vp, vp, vp])
 bt_paths_multigroup_info = _sig("bt_paths_multigroup_info", [vp, vp])
 

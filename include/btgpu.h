@@ -867,6 +867,9 @@ int bt_diag_kmer_set_order(const uint64_t *h_kmers, uint32_t n, uint64_t initial
  * __host__ __device__ code with a team of one thread.  The bucket count comes from the stage plan alone.  initial_buckets (and the count the set grows to)
  * must stay below 2^32 - 2, as on the device route: an error otherwise. */
 int bt_diag_kmer_set_order_staged(const uint64_t *h_kmers, uint32_t n, uint64_t initial_buckets, unsigned k, uint32_t *h_rank, uint64_t *h_final_buckets);
+/* The hash both replays place a k-mer by: the library's restatement of libstdc++'s std::hash<std::bitset<2k>> of the k-mer (lo, hi), k in 1..64 (0 for any
+ * other k).  The ranks expose it only modulo a bucket count.  (CPU tests compare it with the standard library's own hash at every k.) */
+uint64_t bt_diag_std_hash_bitset(uint64_t lo, uint64_t hi, unsigned k);
 
 /* ------------------------------------------------------------------------------------------
  * Deflate on the device (RFC 1951) and gzip files written through it (opt-in: BT_GZIP_ON_DEVICE=1 in the executables).

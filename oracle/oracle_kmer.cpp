@@ -18,12 +18,14 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <random>
 #include <sstream>
 #include <string>
 #include <functional>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -720,7 +722,109 @@ static void walk_path(const OrcGraphs &g, uint32_t c, uint32_t p, FV f_vertex, F
     }
 }
 
+// ---- the real container at run-time k ----
+// std::unordered_set<std::bitset<2k>> needs k at compile time; KmerSetOf<K> wraps one behind a k-free interface and make_kmer_set picks
+// the instantiation.  kKmerSetSizes: 3 hashes its one byte as a tail only; 15 and 28 a tail inside the first word; 31 and 32 exactly
+// one word (62 bits round up to 8 bytes); 33, 36, 55 and 60 one word and a tail of 1, 1, 6 and 7 bytes; 64 two words.
+struct KmerSet {
+    virtual ~KmerSet() {}
+    virtual void clear() = 0;
+    virtual bool emplace(uint64_t lo, uint64_t hi) = 0;   // true when the k-mer was new
+    virtual size_t size() const = 0;
+    virtual uint64_t bucket_count() const = 0;
+    virtual void rehash(uint64_t buckets) = 0;
+    virtual void for_each(const std::function<void(uint64_t, uint64_t)> &f) const = 0;   // in iteration order
+};
+template <unsigned K>
+std::bitset<2 * K> to_bitset(uint64_t lo, uint64_t hi) {
+    std::bitset<2 * K> b;
+    for (unsigned i = 0; i < 2 * K; i++) b[i] = (((i < 64 ? lo : hi) >> (i % 64)) & 1) != 0;
+    return b;
+}
+template <unsigned K>
+struct KmerSetOf : KmerSet {
+    std::unordered_set<std::bitset<2 * K>> set;
+    void clear() override { set.clear(); }
+    bool emplace(uint64_t lo, uint64_t hi) override { return set.emplace(to_bitset<K>(lo, hi)).second; }
+    size_t size() const override { return set.size(); }
+    uint64_t bucket_count() const override { return set.bucket_count(); }
+    void rehash(uint64_t buckets) override { set.rehash(buckets); }
+    void for_each(const std::function<void(uint64_t, uint64_t)> &f) const override {
+        for (auto &b : set) {
+            uint64_t w[2] = {0, 0};
+            for (unsigned i = 0; i < 2 * K; i++)
+                if (b[i]) w[i / 64] |= 1ULL << (i % 64);
+            f(w[0], w[1]);
+        }
+    }
+};
+const unsigned kKmerSetSizes[] = {3, 15, 28, 31, 32, 33, 36, 55, 60, 64};
+KmerSet *make_kmer_set(unsigned k) {   // nullptr for a size outside kKmerSetSizes: the caller reports it, there is no other order to fall back to
+    switch (k) {
+        case 3: return new KmerSetOf<3>();
+        case 15: return new KmerSetOf<15>();
+        case 28: return new KmerSetOf<28>();
+        case 31: return new KmerSetOf<31>();
+        case 32: return new KmerSetOf<32>();
+        case 33: return new KmerSetOf<33>();
+        case 36: return new KmerSetOf<36>();
+        case 55: return new KmerSetOf<55>();
+        case 60: return new KmerSetOf<60>();
+        case 64: return new KmerSetOf<64>();
+        default: return nullptr;
+    }
+}
+template <unsigned K>
+uint64_t std_hash_of(uint64_t lo, uint64_t hi) { return std::hash<std::bitset<2 * K>>()(to_bitset<K>(lo, hi)); }
+typedef uint64_t (*StdHashFn)(uint64_t, uint64_t);
+template <size_t... I>
+const StdHashFn *std_hash_table(std::index_sequence<I...>) {
+    static const StdHashFn table[] = {&std_hash_of<I + 1>...};   // table[k - 1], k = 1..64
+    return table;
+}
+
 extern "C" {
+// std::hash<std::bitset<2k>> of the standard library this oracle is built with, k = 1..64 (0 for any other k; bits above 2k are ignored)
+uint64_t orc_std_hash_bitset(uint64_t lo, uint64_t hi, unsigned k) {
+    if (k == 0 || k > 64) return 0;
+    return std_hash_table(std::make_index_sequence<64>())[k - 1](lo, hi);
+}
+// 1 when make_kmer_set knows k
+int orc_kmer_set_supported(unsigned k) {
+    for (unsigned s : kKmerSetSizes)
+        if (s == k) return 1;
+    return 0;
+}
+// What countPathMultigroupKmersCallback's container does to a sequence of groups (KmerCounter.cpp:111-119), at run-time k: ONE
+// std::unordered_set<std::bitset<2k>>, clear()ed between groups.  Groups of ASCII k-mers lie back to back (group_off[g] .. group_off[g+1]);
+// order_out receives, group by group, the indices (within the group) of its k-mers in iteration order, buckets_out[g] = bucket_count()
+// after the group.  initial_buckets <= 1 is a freshly constructed set; any other value must be a bucket count the container can take
+// (rehash() on the empty set lands on it).  Returns 0; 1 for a k outside kKmerSetSizes; 2 for an initial bucket count the container
+// does not take; 3 for a k-mer that repeats inside its group.
+int orc_kmer_set_orders(unsigned k, const char *kmers, const uint64_t *group_off, uint64_t num_groups, uint64_t initial_buckets, uint32_t *order_out,
+                        uint64_t *buckets_out) {
+    std::unique_ptr<KmerSet> set(make_kmer_set(k));
+    if (!set) return 1;
+    if (initial_buckets > 1) {
+        set->rehash(initial_buckets);
+        if (set->bucket_count() != initial_buckets) return 2;
+    }
+    for (uint64_t g = 0; g < num_groups; g++) {
+        set->clear();
+        std::map<std::pair<uint64_t, uint64_t>, uint32_t> index;
+        for (uint64_t i = group_off[g]; i < group_off[g + 1]; i++) {
+            uint64_t w[2];
+            pack(kmers + i * k, k, w);
+            if (!set->emplace(w[0], w[1])) return 3;
+            index[{w[0], w[1]}] = (uint32_t)(i - group_off[g]);
+        }
+        uint64_t j = group_off[g];
+        set->for_each([&](uint64_t lo, uint64_t hi) { order_out[j++] = index.at({lo, hi}); });
+        buckets_out[g] = set->bucket_count();
+    }
+    return 0;
+}
+
 // VariantClusterGraph::countPathKmers (:800-846) for all clusters + KmerCounter::countPathKmersCallback (KmerCounter.cpp:252-289):
 // the set of path k-mers goes into the path Bloom filter.  Returns the number of k-mer windows.
 uint64_t orc_paths_count_kmers(void *gh, void *bloom) {
@@ -740,51 +844,36 @@ uint64_t orc_paths_count_kmers(void *gh, void *bloom) {
 // reference's outcome is defined): groups in index order; the group's path k-mers are collected in ONE
 // std::unordered_set<std::bitset<2k>> that lives across the groups and is clear()ed between them (its bucket count survives), and are
 // visited in that container's iteration order; a path k-mer the filter already reports goes into the multigroup table, otherwise it
-// is added to the filter.  Returns num_path_kmers.  (k = 55 as the reference is built: bitset<110>; any other k falls back to a set
-// of strings, whose order is not the reference's.)
+// is added to the filter.  Returns num_path_kmers, or UINT64_MAX for a k the real container is not instantiated at (kKmerSetSizes):
+// no other container has the reference's order.
 uint64_t orc_paths_count_multigroup(void *gh, const uint32_t *cluster_group, void *bloom, void *table) {
     const OrcGraphs &g = *(OrcGraphs *)gh;
     OrcBloom *b = (OrcBloom *)bloom;
     OrcTable *t = (OrcTable *)table;
+    std::unique_ptr<KmerSet> group_kmers(make_kmer_set(g.k));
+    if (!group_kmers) return UINT64_MAX;
     uint32_t num_groups = 0;
     for (uint32_t c = 0; c < g.C; c++) num_groups = std::max(num_groups, cluster_group[c] + 1);
     uint64_t num_kmers = 0;
-    auto visit = [&](const std::string &km) {
-        FlatBloom &f = b->subs[b->route(km.data())];
-        if (f.containsF(km.data())) t->map[km];
-        else f.insertF(km.data());
-    };
-    if (g.k == 55) {
-        static const char nt[4] = {'A', 'C', 'G', 'T'};
-        std::unordered_set<std::bitset<110>> group_kmers;
-        for (uint32_t grp = 0; grp < num_groups; grp++) {
-            group_kmers.clear();
-            for (uint32_t c = 0; c < g.C; c++)
-                if (cluster_group[c] == grp)
-                    for (uint32_t p = 0; p < g.num_paths[c]; p++)
-                        walk_path(g, c, p, [](uint32_t) {}, [&](const std::string &km) {
-                            uint64_t w[2];
-                            pack(km.data(), 55, w);
-                            std::bitset<110> bits(w[0]);
-                            bits |= std::bitset<110>(w[1]) << 64;
-                            group_kmers.emplace(bits);
-                        }, [] {});
-            num_kmers += group_kmers.size();
-            for (auto &bits : group_kmers) {
-                std::string km(55, 'A');
-                for (unsigned i = 0; i < 55; i++) km[i] = nt[(bits[2 * i] ? 1 : 0) | (bits[2 * i + 1] ? 2 : 0)];
-                visit(km);
-            }
-        }
-        return num_kmers;
-    }
     for (uint32_t grp = 0; grp < num_groups; grp++) {
-        std::unordered_set<std::string> group_kmers;
+        group_kmers->clear();
         for (uint32_t c = 0; c < g.C; c++)
             if (cluster_group[c] == grp)
-                for (uint32_t p = 0; p < g.num_paths[c]; p++) walk_path(g, c, p, [](uint32_t) {}, [&](const std::string &km) { group_kmers.insert(km); }, [] {});
-        num_kmers += group_kmers.size();
-        for (auto &km : group_kmers) visit(km);
+                for (uint32_t p = 0; p < g.num_paths[c]; p++)
+                    walk_path(g, c, p, [](uint32_t) {}, [&](const std::string &km) {
+                        uint64_t w[2];
+                        pack(km.data(), g.k, w);
+                        group_kmers->emplace(w[0], w[1]);
+                    }, [] {});
+        num_kmers += group_kmers->size();
+        group_kmers->for_each([&](uint64_t lo, uint64_t hi) {
+            const uint64_t w[2] = {lo, hi};
+            std::string km(g.k, 'A');
+            unpack(w, g.k, &km[0]);
+            FlatBloom &f = b->subs[b->route(km.data())];
+            if (f.containsF(km.data())) t->map[km];
+            else f.insertF(km.data());
+        });
     }
     return num_kmers;
 }

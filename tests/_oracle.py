@@ -11,6 +11,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "liboracle.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libbtref.so")
+KMER_SET_SIZES = (3, 15, 28, 31, 32, 33, 36, 55, 60, 64)   # the k the oracle instantiates the real unordered_set<bitset<2k>> at
+
+
+def ref_so(k=55):
+    """the compiled reference of k-mer size k: libbtref.so is the reference's own 55, libbtref_k<k>.so any other build"""
+    return REF_SO if k == 55 else os.path.join(ROOT, "oracle", "_ref", f"libbtref_k{k}.so")
 vp = C.c_void_p
 
 
@@ -101,6 +107,10 @@ class Oracle:
         L.orc_parse_sample_kmers.argtypes = [vp, vp, vp, C.c_uint, C.c_uint64, C.c_uint64]
         L.orc_match_only.restype = C.c_uint64
         L.orc_match_only.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+        L.orc_std_hash_bitset.restype = C.c_uint64
+        L.orc_std_hash_bitset.argtypes = [C.c_uint64, C.c_uint64, C.c_uint]
+        L.orc_kmer_set_supported.argtypes = [C.c_uint]
+        L.orc_kmer_set_orders.argtypes = [C.c_uint, vp, vp, C.c_uint64, C.c_uint64, vp, vp]
 
     # ---- hashing / packing ----
     def ntp64(self, kmers, k, seed=None):
@@ -134,6 +144,26 @@ class Oracle:
         valid = np.zeros(len(a), dtype=np.uint8)
         self.l.orc_kmers_from_sequence(_ptr(a), len(a), k, _ptr(kmers), _ptr(valid))
         return kmers, valid
+
+    def std_hash_bitset(self, lo, hi, k):
+        """std::hash<std::bitset<2k>> of the standard library the oracle is built with, k in 1..64"""
+        assert 1 <= k <= 64, k
+        return self.l.orc_std_hash_bitset(int(lo), int(hi), k)
+
+    def kmer_set_orders(self, k, groups, initial_buckets=1):
+        """one real std::unordered_set<std::bitset<2k>>, clear()ed between `groups` (ASCII arrays [n, k] of distinct k-mers):
+        -> (order, buckets), order[g][j] = the k-mer of group g visited j-th, buckets[g] = bucket_count() after group g.
+        A k outside KMER_SET_SIZES raises: there is no other container with that order."""
+        off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.uint64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(g, np.uint8).reshape(-1, k) for g in groups] + [np.zeros((1, k), np.uint8)])).reshape(-1)
+        order = np.zeros(max(int(off[-1]), 1), np.uint32)
+        buckets = np.zeros(max(len(groups), 1), np.uint64)
+        rc = self.l.orc_kmer_set_orders(k, _ptr(flat), _ptr(off), len(groups), initial_buckets, _ptr(order), _ptr(buckets))
+        if rc:
+            raise ValueError({1: f"orc_kmer_set_orders: no std::unordered_set<std::bitset<{2 * k}>> in the oracle (k must be one of {KMER_SET_SIZES})",
+                              2: f"orc_kmer_set_orders: the container does not take {initial_buckets} buckets",
+                              3: "orc_kmer_set_orders: a k-mer repeats inside its group"}.get(rc, f"orc_kmer_set_orders failed ({rc})"))
+        return [order[int(off[g]):int(off[g + 1])] for g in range(len(groups))], buckets[:len(groups)]
 
     # ---- KMC ----
     def kmc2_write(self, prefix, kmers_ascii, counts, k, p, counter_size=1, nbins=4):
@@ -299,8 +329,12 @@ class OrcGraphs:
         return self.o.l.orc_paths_count_kmers(self.h, bloom.h if bloom is not None else None)
 
     def count_multigroup(self, cluster_group, bloom, table):
+        if not self.o.l.orc_kmer_set_supported(self.k):
+            raise ValueError(f"count_multigroup: the oracle has the reference's container only at k in {KMER_SET_SIZES}, not {self.k}")
         cg = np.ascontiguousarray(cluster_group, np.uint32)
-        return self.o.l.orc_paths_count_multigroup(self.h, _ptr(cg), bloom.h, table.h)
+        n = self.o.l.orc_paths_count_multigroup(self.h, _ptr(cg), bloom.h, table.h)
+        assert n != 2 ** 64 - 1
+        return n
 
     def classify(self, table, mg_bloom):
         n = np.zeros(self.f["num_clusters"], np.uint32)
@@ -418,14 +452,15 @@ class Ref:
         L.ref_sparsity_cover.argtypes = [vp, C.c_uint, C.c_uint, vp, C.c_uint, vp]
 
 
-_REF = False
+_REF = {}
 
 
-def load_ref():
-    global _REF
-    if _REF is False:
-        _REF = Ref(REF_SO) if os.path.exists(REF_SO) else None
-    return _REF
+def load_ref(k=55):
+    """the compiled reference of k-mer size k, or None when that build is absent"""
+    if k not in _REF:
+        _REF[k] = Ref(ref_so(k)) if os.path.exists(ref_so(k)) else None
+        assert _REF[k] is None or _REF[k].k == k, (k, _REF[k].k)
+    return _REF[k]
 
 
 def random_kmers(rng, n, k):

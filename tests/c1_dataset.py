@@ -17,19 +17,19 @@ K = 55
 NT = np.frombuffer(b"ACGT", np.uint8)
 
 
-def _sorted_kmc_order(orc, packed):
+def _sorted_kmc_order(orc, packed, k=K):
     """KMC order = ascending ASCII order of the k-mers"""
-    codes = np.searchsorted(NT, orc.unpack(packed, K).reshape(-1, K)).astype(np.uint64)
+    codes = np.searchsorted(NT, orc.unpack(packed, k).reshape(-1, k)).astype(np.uint64)
     key1 = np.zeros(len(codes), np.uint64)
     key2 = np.zeros(len(codes), np.uint64)
-    for i in range(32):
+    for i in range(min(32, k)):
         key1 |= codes[:, i] << np.uint64(2 * (31 - i))
-    for i in range(32, K):
-        key2 |= codes[:, i] << np.uint64(2 * (K - 1 - i))
+    for i in range(32, k):
+        key2 |= codes[:, i] << np.uint64(2 * (k - 1 - i))
     return np.lexsort((key2, key1))
 
 
-def make(out_dir, orc, genome_len=1_000_000, num_snvs=5000, num_samples=1, num_error_kmers=1_000_000, genders=None, mean=15.0, var=30.0):
+def make(out_dir, orc, genome_len=1_000_000, num_snvs=5000, num_samples=1, num_error_kmers=1_000_000, genders=None, mean=15.0, var=30.0, k=K):
     os.makedirs(out_dir, exist_ok=True)
     rng = np.random.default_rng(1)
     codes = rng.integers(0, 4, genome_len).astype(np.uint8)
@@ -39,7 +39,7 @@ def make(out_dir, orc, genome_len=1_000_000, num_snvs=5000, num_samples=1, num_e
         for i in range(0, genome_len, 60):
             f.write(genome[i:i + 60] + "\n")
     rng = np.random.default_rng(2)
-    pos = np.sort(rng.choice(np.arange(55, genome_len - 110), num_snvs, replace=False))
+    pos = np.sort(rng.choice(np.arange(k, genome_len - 2 * k), num_snvs, replace=False))
     alt = (codes[pos] + 1 + rng.integers(0, 3, num_snvs)) % 4
     with open(os.path.join(out_dir, "candidates.vcf"), "w") as f:
         f.write("##fileformat=VCFv4.2\n##contig=<ID=chr1,length=%d>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n" % genome_len)
@@ -60,13 +60,13 @@ def make(out_dir, orc, genome_len=1_000_000, num_snvs=5000, num_samples=1, num_e
                 carries = (gt == 2) | ((gt == 1) & (which == h))
                 c[pos[carries]] = alt[carries]
                 haps.append(NT[c].tobytes())
-            km, va = orc.kmers_from_sequence(haps[0] + b"N" + haps[1], K)
+            km, va = orc.kmers_from_sequence(haps[0] + b"N" + haps[1], k)
             uniq, mult = np.unique(km[va == 1], axis=0, return_counts=True)
             rng = np.random.default_rng(4 + s)
             cnt = rng.negative_binomial(size * mult, p)
-            err = orc.pack(NT[rng.integers(0, 4, num_error_kmers * K)].copy(), K) if num_error_kmers else np.zeros((0, 2), np.uint64)
+            err = orc.pack(NT[rng.integers(0, 4, num_error_kmers * k)].copy(), k) if num_error_kmers else np.zeros((0, 2), np.uint64)
             if len(err):   # canonical form of the error k-mers (the database holds canonical k-mers)
-                asc = orc.unpack(err, K).reshape(-1, K)
+                asc = orc.unpack(err, k).reshape(-1, k)
                 comp = np.zeros(256, np.uint8)
                 comp[[65, 67, 71, 84]] = [84, 71, 67, 65]
                 rc = comp[asc[:, ::-1]]
@@ -74,19 +74,19 @@ def make(out_dir, orc, genome_len=1_000_000, num_snvs=5000, num_samples=1, num_e
                 first = diff.argmax(axis=1)                                 # first position where the k-mer and its reverse complement differ
                 rows = np.arange(len(asc))
                 lower = ~diff.any(axis=1) | (asc[rows, first] < rc[rows, first])
-                err = orc.pack(np.ascontiguousarray(np.where(lower[:, None], asc, rc)).reshape(-1), K)
+                err = orc.pack(np.ascontiguousarray(np.where(lower[:, None], asc, rc)).reshape(-1), k)
             keep = cnt > 0
             allk = np.concatenate([uniq[keep], err])
             allc = np.concatenate([np.minimum(cnt[keep], 255), np.ones(len(err), np.int64)])
             allk, first = np.unique(allk, axis=0, return_index=True)
             allc = allc[first]
-            order = _sorted_kmc_order(orc, allk)
+            order = _sorted_kmc_order(orc, allk, k)
             prefix = os.path.join(out_dir, f"sample{s + 1}")
-            orc.kmc_write(prefix, orc.unpack(allk[order], K), allc[order].astype(np.uint32), K, 7, 1)
+            orc.kmc_write(prefix, orc.unpack(allk[order], k), allc[order].astype(np.uint32), k, 7, 1)
             from _oracle import OrcBloom
 
-            bloom = OrcBloom(orc, len(allk), 1e-3, K)
-            bloom.insert(orc.unpack(allk, K))
+            bloom = OrcBloom(orc, len(allk), 1e-3, k)
+            bloom.insert(orc.unpack(allk, k))
             bloom.save(prefix)
             bloom.close()
             sf.write(f"sample{s + 1}\t{genders[s]}\t{prefix}\n")

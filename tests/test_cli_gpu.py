@@ -32,7 +32,7 @@ CODE = {c: i for i, c in enumerate("ACGT")}
 KC_PARAMETER, KC_DECOY = 0x20, 0x08
 
 
-def _graph_arrays(orc, chrom_ascii, vars_, red, contained):
+def _graph_arrays(orc, chrom_ascii, vars_, red, contained, k=K):
     """one cluster's graph from the oracle's restatement of the reference constructor (oracle/oracle_graph.cpp)"""
     L = orc.l
     L.orc_graph_build.restype = C.c_void_p
@@ -51,14 +51,14 @@ def _graph_arrays(orc, chrom_ascii, vars_, red, contained):
     cl = np.array([c[1] for c in contained] + [0], np.uint32)
     cr = np.array([c[2] for c in contained] + [0], np.uint32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    h = L.orc_graph_build(K, chrom_ascii, len(chrom_ascii), len(vars_), p(pos), p(nalt), p(redn), p(dep), p(ref_len), p(off), b"".join(seqs), len(contained), p(cl), p(cr), p(ci))
+    h = L.orc_graph_build(k, chrom_ascii, len(chrom_ascii), len(vars_), p(pos), p(nalt), p(redn), p(dep), p(ref_len), p(off), b"".join(seqs), len(contained), p(cl), p(cr), p(ci))
     sizes = np.zeros(4, np.uint64)
     L.orc_graph_sizes(h, p(sizes))
     nv, ne, nnt, nref = [int(x) for x in sizes]
     out = {"seq_off": np.zeros(nv + 1, np.uint64), "seq": np.zeros(max(nnt, 1), np.uint8), "var": np.zeros(nv, np.uint16), "allele": np.zeros(nv, np.uint16),
            "flags": np.zeros(nv, np.uint8), "nested": np.zeros(nv, np.uint32), "refvar_off": np.zeros(nv + 1, np.uint32), "refvar": np.zeros(max(nref, 1), np.uint16),
            "edges": np.zeros(max(2 * ne, 1), np.uint32), "num_alleles": np.zeros(len(vars_), np.uint16), "dep": np.zeros(len(vars_), np.uint8)}
-    L.orc_graph_fetch(h, *[p(out[k]) for k in ("seq_off", "seq", "var", "allele", "flags", "nested", "refvar_off", "refvar", "edges", "num_alleles", "dep")])
+    L.orc_graph_fetch(h, *[p(out[name]) for name in ("seq_off", "seq", "var", "allele", "flags", "nested", "refvar_off", "refvar", "edges", "num_alleles", "dep")])
     L.orc_graph_free(h)
     out["seq"], out["refvar"], out["edges"] = out["seq"][:nnt], out["refvar"][:nref], out["edges"][: 2 * ne].reshape(-1, 2)
     return out
@@ -131,7 +131,7 @@ def _fmt(x):
     return "%g" % x
 
 
-def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_unit_variants=10 ** 9, unit=0):
+def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_unit_variants=10 ** 9, unit=0, k=K):
     """the cluster stage over all units (they share the path filter, the multigroup table and the parameter k-mers), then the genotype stage of unit `unit`"""
     import oracle_writer
     from bayestyper_amd.host import genotypes as G   # (ctypes signatures of the oracle's genotype functions only; `fn=` selects the oracle)
@@ -154,13 +154,13 @@ def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_un
     oracle.l.orc_cluster_stage.restype = C.c_ulonglong
     oracle.l.orc_cluster_stage.argtypes = [C.c_char_p, C.c_ulonglong, C.c_uint, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_ulonglong), C.c_char_p, C.c_uint, C.c_uint,
                                            C.c_float, C.c_uint, C.c_char_p, C.c_ulonglong]
-    units, _, regions_sorted, _ = T.parse_dump(T.oracle_text(oracle, vcf, genome, K, min_unit_variants))
+    units, _, regions_sorted, _ = T.parse_dump(T.oracle_text(oracle, vcf, genome, k, min_unit_variants))
     out["num_units"] = len(units)
     out["regions_text"] = "".join(f"{c}\t{d}\t{s}\t{e}\n" for c, d, s, e in regions_sorted)
     genome_len = sum(len(seq) for _, seq, decoy in genome if not decoy)
     expected_path = int(np.ceil(genome_len * (1 + 0.05 * 2 * S)))
-    pb = OrcBloom(oracle, expected_path, 1e-4, K, threaded=True)
-    mg_table = OrcTable(oracle, 1, K)
+    pb = OrcBloom(oracle, expected_path, 1e-4, k, threaded=True)
+    mg_table = OrcTable(oracle, 1, k)
     per_unit = []
     for groups_u in units:
         where, groups, sources, out_edges, cluster_ids = [], [], [], [], []
@@ -171,33 +171,33 @@ def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_un
                 where.append((gi, vi))
                 out_edges.append(v["edges"])
                 cluster_ids.append(v["cluster_idx"])
-        graphs = [_graph_arrays(oracle, seqs[groups_u[gi]["vertices"][vi]["chrom"]].encode(), groups_u[gi]["vertices"][vi]["vars"], groups_u[gi]["vertices"][vi]["red"], groups_u[gi]["vertices"][vi]["contained"]) for gi, vi in where]
+        graphs = [_graph_arrays(oracle, seqs[groups_u[gi]["vertices"][vi]["chrom"]].encode(), groups_u[gi]["vertices"][vi]["vars"], groups_u[gi]["vertices"][vi]["red"], groups_u[gi]["vertices"][vi]["contained"], k) for gi, vi in where]
         # ---- best paths per sample ----
-        og = OrcGraphs(oracle, _flatten(graphs), K)
+        og = OrcGraphs(oracle, _flatten(graphs), k)
         for s in range(S):
-            sb = OrcBloom.load(oracle, sample_rows[s][2], K)
+            sb = OrcBloom.load(oracle, sample_rows[s][2], k)
             seeds = np.array([seed + (gi + 1) * (s + 1) + cluster_ids[c] for c, (gi, _) in enumerate(where)], np.uint32)
             paths = og.find_sample_paths(sb, seeds, 32)
             sb.close()
         og.close()
         f = _flatten(graphs, paths)
-        og = OrcGraphs(oracle, f, K)
+        og = OrcGraphs(oracle, f, k)
         # ---- multigroup k-mers, path k-mer count (filter and table are shared by the units) ----
         num_path_kmers = og.count_multigroup(np.array([gi for gi, _ in where], np.uint32), pb, mg_table)
         og.close()
         per_unit.append((groups_u, where, groups, sources, out_edges, cluster_ids, f, num_path_kmers))
     groups_o, where, groups, sources, out_edges, cluster_ids, f, num_path_kmers = per_unit[unit]
     NC = len(where)
-    og = OrcGraphs(oracle, f, K)
+    og = OrcGraphs(oracle, f, k)
     mg_keys = mg_table.export()[0]
     # ---- parameter k-mers ----
-    num_region_kmers = sum(e - s + 1 for _, _, s, e in regions_sorted) - len(regions_sorted) * (K - 1)
+    num_region_kmers = sum(e - s + 1 for _, _, s, e in regions_sorted) - len(regions_sorted) * (k - 1)
     fraction = min(1.0, np.float32(3_000_000) / np.float32(num_region_kmers))
-    ptab = OrcTable(oracle, 1, K)
+    ptab = OrcTable(oracle, 1, k)
     for i, (c, d, s, e) in enumerate(regions_sorted):
         ptab.count_parameter_kmers(pb, seqs[c][s:e + 1].encode(), d, seed + i, fraction)
     pk, _, pmeta = ptab.export()
-    asc = oracle.unpack(pk, K)
+    asc = oracle.unpack(pk, k)
     order = np.zeros(len(pk), np.uint32)
     if ref is not None:   # the reference's own container decides the order
         ref.l.ref_hybrid_hash_order.restype = C.c_uint64
@@ -207,15 +207,15 @@ def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_un
         from bayestyper_amd.host import dll
 
         dll.bth_hybrid_hash_order.argtypes = [C.c_void_p, C.c_uint64, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
-        dll.bth_hybrid_hash_order(np.ascontiguousarray(pk).ctypes.data, len(pk), K, seed, 4 ** 12, order.ctypes.data)
+        dll.bth_hybrid_hash_order(np.ascontiguousarray(pk).ctypes.data, len(pk), k, seed, 4 ** 12, order.ctypes.data)
     flags = pmeta[:, 0]
     chosen = [i for i in order if (flags[i] & KC_PARAMETER) and not (flags[i] & KC_DECOY)][:1_000_000]
-    param_ascii = asc.reshape(-1, K)[chosen]
+    param_ascii = asc.reshape(-1, k)[chosen]
     out["parameter_kmers"] = [bytes(r).decode() for r in param_ascii]
     pb.close(), ptab.close(), mg_table.close()
     # ---- genotype: tables ----
-    pb = OrcBloom(oracle, num_path_kmers + 1_000_000, 1e-4, K, threaded=True)
-    table = OrcTable(oracle, S, K)
+    pb = OrcBloom(oracle, num_path_kmers + 1_000_000, 1e-4, k, threaded=True)
+    table = OrcTable(oracle, S, k)
     flat_params = np.ascontiguousarray(param_ascii).reshape(-1)
     pb.insert(flat_params)
     table.insert(flat_params, mark_parameter=True)
@@ -226,9 +226,9 @@ def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_un
         db = OrcKmc(oracle, sample_rows[s][2])
         table.parse_sample_kmers(pb, db, s)
         db.close()
-    mgb = OrcBloom(oracle, max(len(mg_keys), 1), 1e-4, K)
+    mgb = OrcBloom(oracle, max(len(mg_keys), 1), 1e-4, k)
     if len(mg_keys):
-        mgb.insert(oracle.unpack(mg_keys, K))
+        mgb.insert(oracle.unpack(mg_keys, k))
     og.classify(table, mgb)
     cand = og.candidates(table)
     # ---- NB fit from the parameter k-mers (CountDistribution.cpp:66-141) ----
@@ -297,23 +297,29 @@ def oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping=False, min_un
                           (90_000, 450, 1, dict(chains=3, burn=12, samples=30), False, 120, 2)],
                          ids=["small-default-schedule", "C1-1Mb-5000-SNVs", "trio-female-male-female", "noise-genotyping-two-samples", "several-units-genotype-the-third"])
 def test_cluster_then_genotype_equal_the_oracle_pipeline(oracle, tmp_path, genome_len, num_snvs, num_samples, gibbs, noise_genotyping, min_unit, unit):
-    ref = _oracle.load_ref()
-    ds = c1_dataset.make(str(tmp_path / "data"), oracle, genome_len, num_snvs, num_samples, num_error_kmers=200_000, genders=["F", "M", "F"][:num_samples])
+    check_cluster_then_genotype(oracle, tmp_path, genome_len, num_snvs, num_samples, gibbs, noise_genotyping, min_unit, unit)
+
+
+def check_cluster_then_genotype(oracle, tmp_path, genome_len, num_snvs, num_samples, gibbs, noise_genotyping, min_unit, unit, k=K):
+    """the C1 dataset at k-mer size k through both command lines (BT_KMER_SIZE in their environment when k is not the default), every file against the oracle pipeline"""
+    ref = _oracle.load_ref(k)
+    env = dict(os.environ, BT_KMER_SIZE=str(k)) if k != K else None
+    ds = c1_dataset.make(str(tmp_path / "data"), oracle, genome_len, num_snvs, num_samples, num_error_kmers=200_000, genders=["F", "M", "F"][:num_samples], k=k)
     seed = 42
     prefix = str(tmp_path / "bt")
     r = subprocess.run([EXE, "cluster", "-v", os.path.join(ds["dir"], "candidates.vcf"), "-s", os.path.join(ds["dir"], "samples.tsv"), "-g", os.path.join(ds["dir"], "genome.fa"), "-o", prefix,
-                        "-r", str(seed)] + (["--min-number-of-unit-variants", str(min_unit)] if min_unit else []), capture_output=True, text=True)
+                        "-r", str(seed)] + (["--min-number-of-unit-variants", str(min_unit)] if min_unit else []), capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr
     assert "BayesTyper cluster completed succesfully!" in r.stdout
     r = subprocess.run([EXE, "genotype", "-v", prefix + f"_unit_{unit + 1}/variant_clusters.bin", "-c", prefix + "_cluster_data", "-s", os.path.join(ds["dir"], "samples.tsv"), "-g",
                         os.path.join(ds["dir"], "genome.fa"), "-o", prefix, "-r", str(seed), "--number-of-gibbs-chains", str(gibbs["chains"]), "--gibbs-burn-in", str(gibbs["burn"]),
-                        "--gibbs-samples", str(gibbs["samples"])] + (["--noise-genotyping", "-z"] if noise_genotyping else []), capture_output=True, text=True)
+                        "--gibbs-samples", str(gibbs["samples"])] + (["--noise-genotyping", "-z"] if noise_genotyping else []), capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr
     assert "BayesTyper genotype completed succesfully!" in r.stdout
 
     # main.cpp:218,242: the option gives the number of units, floor(variants / option), and every unit then takes ceil(variants / units) variants
     per_unit = int(np.ceil(num_snvs / max(1, num_snvs // min_unit))) if min_unit else 10 ** 9
-    want = oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping, per_unit, unit)
+    want = oracle_pipeline(oracle, ref, ds, seed, gibbs, noise_genotyping, per_unit, unit, k)
     assert f"- {want['unit_variants']} were genotyped" in r.stdout, r.stdout[-1500:]
     if min_unit:
         assert want["num_units"] >= 3 and unit < want["num_units"] and want["unit_variants"] < num_snvs
@@ -323,8 +329,8 @@ def test_cluster_then_genotype_equal_the_oracle_pipeline(oracle, tmp_path, genom
     # cluster stage files
     assert gzip.open(prefix + "_cluster_data/intercluster_regions.txt.gz", "rt").read() == want["regions_text"]
     got_params = gzip.open(prefix + "_cluster_data/parameter_kmers.fa.gz", "rt").read().split("\n")
-    assert got_params[0] == ">k55" and got_params[-1] == "" and got_params[1:-1] == want["parameter_kmers"] and len(want["parameter_kmers"]) > 10_000
-    assert open(prefix + "_cluster_data/multigroup_kmers.bloomMeta").read().split("\t")[2].strip() == "55"
+    assert got_params[0] == f">k{k}" and got_params[-1] == "" and got_params[1:-1] == want["parameter_kmers"] and len(want["parameter_kmers"]) > 10_000
+    assert open(prefix + "_cluster_data/multigroup_kmers.bloomMeta").read().split("\t")[2].strip() == str(k)
     # genotype stage files
     rows = open(prefix + "_genomic_parameters.txt").read().split("\n")
     assert rows[0] == "Sample\tMean\tVariance"

@@ -11,7 +11,7 @@ K = 55
 NT = np.frombuffer(b"ACGT", np.uint8)
 
 
-def _build(chrom_ascii, variants, contained, lib=None, prefix="bth"):
+def _build(chrom_ascii, variants, contained, lib=None, prefix="bth", k=K):
     """the graph of one cluster as flat arrays: from the product's builder (default) or, with lib = the oracle library and
     prefix = "orc", from the oracle's restatement of the reference constructor (oracle/oracle_graph.cpp)"""
     class _Api:
@@ -20,10 +20,10 @@ def _build(chrom_ascii, variants, contained, lib=None, prefix="bth"):
     src = dll if lib is None else lib
     for name in ("build", "free", "sizes", "fetch"):
         setattr(api, "bth_graph_" + name, getattr(src, f"{prefix}_graph_{name}"))
-    return _build_with(api, chrom_ascii, variants, contained)
+    return _build_with(api, chrom_ascii, variants, contained, k)
 
 
-def _build_with(dll, chrom_ascii, variants, contained):
+def _build_with(dll, chrom_ascii, variants, contained, k=K):
     dll.bth_graph_build.restype = C.c_void_p
     dll.bth_graph_build.argtypes = [C.c_uint, C.c_char_p, C.c_ulonglong, C.c_uint] + [C.c_void_p] * 6 + [C.c_char_p, C.c_uint] + [C.c_void_p] * 3
     dll.bth_graph_free.argtypes = [C.c_void_p]
@@ -40,7 +40,7 @@ def _build_with(dll, chrom_ascii, variants, contained):
     cr = np.array([c[1] for c in contained] + [0], np.uint32)
     ci = np.array([c[2] for c in contained] + [0], np.uint32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    h = dll.bth_graph_build(K, chrom_ascii, len(chrom_ascii), len(variants), p(pos), p(nalt), p(red), p(dep), p(ref_len), p(off), b"".join(seqs), len(contained), p(cl), p(cr), p(ci))
+    h = dll.bth_graph_build(k, chrom_ascii, len(chrom_ascii), len(variants), p(pos), p(nalt), p(red), p(dep), p(ref_len), p(off), b"".join(seqs), len(contained), p(cl), p(cr), p(ci))
     assert h, "bth_graph_build failed"
     sizes = np.zeros(4, np.uint64)
     dll.bth_graph_sizes(h, p(sizes))
@@ -48,17 +48,17 @@ def _build_with(dll, chrom_ascii, variants, contained):
     out = {"seq_off": np.zeros(nv + 1, np.uint64), "seq": np.zeros(max(nnt, 1), np.uint8), "var": np.zeros(nv, np.uint16), "allele": np.zeros(nv, np.uint16),
            "flags": np.zeros(nv, np.uint8), "nested": np.zeros(nv, np.uint32), "refvar_off": np.zeros(nv + 1, np.uint32), "refvar": np.zeros(max(nref, 1), np.uint16),
            "edges": np.zeros(max(2 * ne, 1), np.uint32), "num_alleles": np.zeros(len(variants), np.uint16), "dep": np.zeros(len(variants), np.uint8)}
-    dll.bth_graph_fetch(h, *[p(out[k]) for k in ("seq_off", "seq", "var", "allele", "flags", "nested", "refvar_off", "refvar", "edges", "num_alleles", "dep")])
+    dll.bth_graph_fetch(h, *[p(out[name]) for name in ("seq_off", "seq", "var", "allele", "flags", "nested", "refvar_off", "refvar", "edges", "num_alleles", "dep")])
     dll.bth_graph_free(h)
     out["seq"], out["refvar"], out["edges"] = out["seq"][:nnt], out["refvar"][:nref], out["edges"][: 2 * ne].reshape(-1, 2)
     return out
 
 
-def test_cpp_graph_equals_python_restatement():
+def check_cpp_graph_equals_python_restatement(k=K, n=60):
     rng = np.random.default_rng(3)
-    for i in range(60):
-        g = synth_graphs.random_cluster(rng, K, int(rng.integers(1, 9)), 2, nested_cluster=(900 + i) if i % 3 else None)
-        out = _build(NT[g.chrom].tobytes(), g.variants, g.contained)
+    for i in range(n):
+        g = synth_graphs.random_cluster(rng, k, int(rng.integers(1, 9)), 2, nested_cluster=(900 + i) if i % 3 else None)
+        out = _build(NT[g.chrom].tobytes(), g.variants, g.contained, k=k)
         nv = len(g.seq)
         assert len(out["var"]) == nv
         assert np.array_equal(out["seq"], np.concatenate(g.seq)) and np.array_equal(out["seq_off"], np.concatenate([[0], np.cumsum([len(x) for x in g.seq])]))
@@ -71,7 +71,11 @@ def test_cpp_graph_equals_python_restatement():
         assert np.array_equal(out["num_alleles"], np.array([1 + len(v["alts"]) for v in g.variants], np.uint16))
 
 
-def test_cpp_graph_equals_oracle_restatement():
+def test_cpp_graph_equals_python_restatement():
+    check_cpp_graph_equals_python_restatement()
+
+
+def check_cpp_graph_equals_oracle_restatement(k=K, n=150, min_split=10):
     """the product's graph builder against the oracle's own restatement of VariantClusterGraph.cpp:62-377 (oracle/oracle_graph.cpp, which
     shares no code with bayestyper_amd): multi-allelic variants, redundant first nucleotides, dependencies, nested clusters, N runs"""
     import sys
@@ -82,25 +86,29 @@ def test_cpp_graph_equals_oracle_restatement():
     orc = _oracle.load_oracle()
     rng = np.random.default_rng(17)
     checked = n_split = 0
-    for i in range(150):
-        g = synth_graphs.random_cluster(rng, K, int(rng.integers(1, 12)), int(rng.integers(1, 4)), nested_cluster=(500 + i) if i % 2 else None)
+    for i in range(n):
+        g = synth_graphs.random_cluster(rng, k, int(rng.integers(1, 12)), int(rng.integers(1, 4)), nested_cluster=(500 + i) if i % 2 else None)
         variants = [dict(v) for v in g.variants]
         for v in variants:   # vary what the parser would have set
             v["has_dependency"] = bool(rng.random() < 0.3)
             v["num_redundant"] = int(rng.random() < 0.3 and min(min(a[0], len(a[1])) for a in v["alts"]) > 0)
         chrom = NT[g.chrom].copy()
         if i % 3 == 0:   # N runs anywhere in the cluster's stretch of the reference (flanks, between and under variants)
-            lo, hi = variants[0]["pos"] - (K - 1), variants[-1]["pos"] + K
+            lo, hi = variants[0]["pos"] - (k - 1), variants[-1]["pos"] + k
             for _ in range(int(rng.integers(1, 4))):
                 a = int(rng.integers(lo, hi))
                 chrom[a:a + int(rng.integers(1, 6))] = ord("N")
-        a = _build(chrom.tobytes(), variants, g.contained)
-        b = _build(chrom.tobytes(), variants, g.contained, lib=orc.l, prefix="orc")
+        a = _build(chrom.tobytes(), variants, g.contained, k=k)
+        b = _build(chrom.tobytes(), variants, g.contained, lib=orc.l, prefix="orc", k=k)
         for key in a:
             assert np.array_equal(a[key], b[key]), (i, key)
         checked += 1
         n_split += int((a["flags"] & 1).sum() > len(g.contained))
-    assert checked == 150 and n_split > 10
+    assert checked == n and n_split > min_split
+
+
+def test_cpp_graph_equals_oracle_restatement():
+    check_cpp_graph_equals_oracle_restatement()
 
 
 def test_n_runs_split_vertices():
