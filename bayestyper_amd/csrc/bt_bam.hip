@@ -1,0 +1,538 @@
+// libbtgpu: a BAM sample's reads as the reads text of bt_reads.hip, on the device.
+//   bt_bam_reads_text      inflated BAM records -> "<bases>\n" per kept record (bt_bam.hpp holds the record's code, one text for kernels and host)
+//   bt_bam_scan_*          the stream object: slabs of whole BGZF blocks from the host -> inflate (bt_inflate.hip) behind the carried tail -> text
+//   bt_diag_bam_reads_text the host run of the same record code
+// What `samtools fastq` does on the host before the reads of a BAM can enter the reads route (the reference's workflow counts BAMs with kmc -fbam).
+//
+// Record starts are a dependent chain (each start comes from the previous block_size), and no workgroup may wait on another, so the chain is walked in segments
+// from guessed entries, the guesses are checked in order, and wrong ones walked again (bam_guess_kernel, bam_stitch_kernel, bam_fill_kernel: see there).  Then:
+//   bam_measure_kernel  a thread per record: fields checked, flag & skip_flags judged, l_seq + 1 (0 when skipped) into sizes[], a sum per workgroup
+//   bam_offsets_kernel  one workgroup: exclusive scan over the workgroups' sums, the text's length
+//   bam_emit_kernel     a workgroup per 256 records rebuilds its records' offsets from sizes[]; a wavefront per record, a lane per base: 64 consecutive
+//                       bytes of text per store instruction, 32 consecutive bytes of the packed sequence per load instruction
+// The first failing record is the one at the smallest offset: a 64-bit atomic minimum over offset << 2 | condition.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+#include "bt_bam.hpp"
+#include "bt_internal.hpp"
+
+using namespace bt;
+using namespace btbam;
+
+namespace {
+
+constexpr uint32_t kTile = 256;
+constexpr unsigned long long kNoError = ~0ull;
+
+struct BamResult {
+    unsigned long long err;   // offset << 2 | condition of the first failing record
+    unsigned long long consumed, text_bytes, kept, skipped, bases;
+    uint32_t n_records, overflow;   // overflow: 1 starts[] too small (never: it is sized for the shortest record), 2 text capacity
+};
+
+// ---- record starts ------------------------------------------------------------------------------------------------------------------------------------------
+// The slab is cut into at most kMaxSegs segments of equal length.  A segment's walk needs its first record start, which only the walk of the segments before it
+// can tell, so it is GUESSED, the walks run in parallel, and the guesses are then checked one after the other:
+//   bam_guess_kernel   a wavefront per segment: the 64 lanes try 64 consecutive offsets at a time for one that starts three plausible records in a row
+//                      (read_record's check), the first such offset is the guess; lane 0 walks from it to the segment's end and leaves the number of records
+//                      and where the walk left the segment.  Segment 0 starts at offset 0, which is known.
+//   bam_stitch_kernel  one workgroup: the segments' results into LDS, then thread 0 goes through them in order: the true entry of a segment is where the walk of
+//                      the segment before left off; when the guess equals it the segment's result stands, otherwise thread 0 walks that segment again from the
+//                      true entry.  It also sums the counts: entry[] and base[] per segment.
+//   bam_fill_kernel    a thread per segment walks from the segment's true entry and stores the starts at their final places.
+// So the starts are those of the chain from offset 0 whatever the data looks like; bytes that only look like records (in a quality string, an auxiliary array) cost
+// time, never a wrong start.  No workgroup waits on another: the kernels follow each other on the stream.
+constexpr uint32_t kMaxSegs = 2048, kMinSeg = 1024, kPlausible = 3;
+constexpr unsigned long long kNone = ~0ull;
+enum : uint32_t { kWalkOn = 0, kWalkEnd = 1, kWalkBad = 2 };   // left the segment; met a record that is not whole; met a block_size below 32
+
+struct Seg {
+    unsigned long long guess, exit;   // exit: the first start at or behind the segment's end, or where the walk stopped
+    uint32_t count, stop;
+};
+
+__device__ inline Seg walk_segment(const uint8_t *__restrict__ bam, uint64_t len, uint64_t p, uint64_t limit, uint32_t *__restrict__ starts) {
+    Seg w{p, p, 0, kWalkOn};
+    while (p < limit) {
+        if (len - p < 4) {
+            w.stop = kWalkEnd;
+            break;
+        }
+        const uint32_t bs = rd32(bam + p);
+        if (bs < kFixed || bs > 0x7FFFFFFFu) {
+            w.stop = kWalkBad;
+            break;
+        }
+        if (4ull + bs > len - p) {
+            w.stop = kWalkEnd;
+            break;
+        }
+        if (starts) starts[w.count] = (uint32_t)p;
+        ++w.count;
+        p += 4ull + bs;
+    }
+    w.exit = p;
+    return w;
+}
+
+// kPlausible records in a row from q on (fewer when the data ends first), each with what a writer always leaves: a block_size that covers its fields and stays
+// below 64 MiB, reference indices of at least -1, a read name that ends with its NUL.  A chain that jumps past the data's end is none (only the slab's last
+// segment can lose a true start to this rule, and then walks again).
+__device__ inline bool plausible_start(const uint8_t *__restrict__ bam, uint64_t len, uint64_t q) {
+    for (uint32_t i = 0; i < kPlausible; ++i) {
+        if (q == len) return true;
+        if (q > len) return false;
+        if (len - q < kHead) return i > 0;
+        if (rd32(bam + q) > (1u << 26)) return false;
+        Record r;
+        if (read_record(bam + q, len - q, r) != kRecOk) return false;
+        const uint32_t l_read_name = bam[q + 12];
+        if ((int32_t)rd32(bam + q + 4) < -1 || (int32_t)rd32(bam + q + 24) < -1 || l_read_name == 0) return false;
+        if (len - q < kHead + l_read_name || bam[q + kHead + l_read_name - 1] != 0) return false;
+        q += 4ull + r.block_size;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void bam_guess_kernel(const uint8_t *__restrict__ bam, uint64_t len, uint64_t seg_len, Seg *__restrict__ segs) {
+    const uint64_t begin = (uint64_t)blockIdx.x * seg_len, end = std::min<uint64_t>(len, begin + seg_len);
+    unsigned long long guess = blockIdx.x == 0 ? 0 : kNone;
+    for (uint64_t base = begin; guess == kNone && base < end; base += 64) {
+        const uint64_t q = base + threadIdx.x;
+        const unsigned long long hit = __ballot(q < end && plausible_start(bam, len, q));
+        if (hit) guess = base + (uint64_t)__builtin_ctzll(hit);
+    }
+    if (threadIdx.x == 0) {
+        Seg w{kNone, kNone, 0, kWalkOn};
+        if (guess != kNone) w = walk_segment(bam, len, guess, end, nullptr);
+        segs[blockIdx.x] = w;
+    }
+}
+
+__global__ __launch_bounds__(256) void bam_stitch_kernel(const uint8_t *__restrict__ bam, uint64_t len, uint64_t seg_len, uint32_t num_segs, const Seg *__restrict__ segs,
+                                                         unsigned long long *__restrict__ entry, uint32_t *__restrict__ base, BamResult *res) {
+    __shared__ Seg sseg[kMaxSegs];
+    for (uint32_t s = threadIdx.x; s < num_segs; s += blockDim.x) sseg[s] = segs[s];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint64_t at = 0;
+    uint32_t total = 0, stop = kWalkOn;
+    for (uint32_t s = 0; s < num_segs; ++s) {
+        const uint64_t end = std::min<uint64_t>(len, (uint64_t)(s + 1) * seg_len);
+        base[s] = total;
+        if (stop != kWalkOn || at >= end) {   // (a record longer than the segment: no start lies in it)
+            entry[s] = kNone;
+            continue;
+        }
+        Seg g = sseg[s];
+        if (g.guess != at) g = walk_segment(bam, len, at, end, nullptr);
+        entry[s] = at;
+        total += g.count;
+        at = g.exit;
+        stop = g.stop;
+    }
+    if (stop == kWalkBad)
+        atomicMin(&res->err, (unsigned long long)at << 2 | kRecShort);
+    else if (len - at >= kHead) {   // the record that is not whole is judged by what is there of it
+        Record r;
+        const uint32_t e = read_record(bam + at, len - at, r);
+        if (e != kRecOk) atomicMin(&res->err, (unsigned long long)at << 2 | e);
+    }
+    res->consumed = at;
+    res->n_records = total;
+}
+
+__global__ __launch_bounds__(64) void bam_fill_kernel(const uint8_t *__restrict__ bam, uint64_t len, uint64_t seg_len, uint32_t num_segs, const unsigned long long *__restrict__ entry,
+                                                      const uint32_t *__restrict__ base, uint32_t *__restrict__ starts, uint32_t starts_cap, BamResult *res) {
+    const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= num_segs || entry[s] == kNone) return;
+    if (res->n_records > starts_cap) {   // (never: starts[] is sized for the shortest record)
+        res->overflow = 1;
+        return;
+    }
+    walk_segment(bam, len, entry[s], std::min<uint64_t>(len, (uint64_t)(s + 1) * seg_len), starts + base[s]);
+}
+
+__global__ __launch_bounds__(kTile) void bam_measure_kernel(const uint8_t *__restrict__ bam, uint64_t len, const uint32_t *__restrict__ starts, uint32_t n, uint32_t skip_flags,
+                                                            uint32_t *__restrict__ sizes, unsigned long long *__restrict__ sums, BamResult *res) {
+    __shared__ unsigned long long s_sum;
+    __shared__ uint32_t s_kept;
+    if (threadIdx.x == 0) s_sum = 0, s_kept = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kTile + threadIdx.x;
+    if (i < n) {
+        const uint64_t at = starts[i];
+        Record r;
+        const uint32_t e = read_record(bam + at, len - at, r);   // (whole: the walk stored only whole records, of at least kHead bytes)
+        uint32_t size = 0;
+        if (e != kRecOk)
+            atomicMin(&res->err, (unsigned long long)at << 2 | e);
+        else if (!(r.flag & skip_flags))
+            size = r.l_seq + 1;
+        sizes[i] = size;
+        if (size) {
+            atomicAdd(&s_sum, (unsigned long long)size);
+            atomicAdd(&s_kept, 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t in_tile = std::min<uint32_t>(kTile, n - blockIdx.x * kTile);
+        sums[blockIdx.x] = s_sum;
+        if (s_kept) atomicAdd(&res->kept, (unsigned long long)s_kept);
+        if (in_tile - s_kept) atomicAdd(&res->skipped, (unsigned long long)(in_tile - s_kept));
+        if (s_sum) atomicAdd(&res->bases, s_sum - s_kept);
+    }
+}
+
+// sums[0..nb) -> exclusive prefix sums in place; the total is the text's length
+__global__ __launch_bounds__(256) void bam_offsets_kernel(unsigned long long *sums, uint32_t nb, BamResult *res) {
+    __shared__ unsigned long long part[256];
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < nb; base += 256) {
+        const uint32_t i = base + threadIdx.x;
+        const unsigned long long v = i < nb ? sums[i] : 0;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < 256; d <<= 1) {
+            const unsigned long long o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+            __syncthreads();
+            part[threadIdx.x] += o;
+            __syncthreads();
+        }
+        if (i < nb) sums[i] = carry + part[threadIdx.x] - v;
+        carry += part[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) res->text_bytes = carry;
+}
+
+__global__ __launch_bounds__(kTile) void bam_emit_kernel(const uint8_t *__restrict__ bam, const uint32_t *__restrict__ starts, const uint32_t *__restrict__ sizes,
+                                                         const unsigned long long *__restrict__ sums, uint32_t n, char *__restrict__ text, uint64_t capacity, BamResult *res) {
+    __shared__ uint32_t part[kTile], size_of[kTile];
+    const uint32_t first = blockIdx.x * kTile, i = first + threadIdx.x;
+    const uint32_t v = i < n ? sizes[i] : 0;
+    part[threadIdx.x] = v;
+    size_of[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < kTile; d <<= 1) {   // a tile's sizes sum to less than the slab's length: 32 bits
+        const uint32_t o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += o;
+        __syncthreads();
+    }
+    const uint64_t tile_at = sums[blockIdx.x];
+    const uint32_t lane = threadIdx.x & 63u, in_tile = std::min<uint32_t>(kTile, n - first);
+    for (uint32_t r = threadIdx.x >> 6; r < in_tile; r += kTile / 64) {
+        const uint32_t size = size_of[r];
+        if (!size) continue;
+        const uint64_t at = tile_at + part[r] - size;
+        if (at + size > capacity) {   // nothing is written past the capacity
+            if (lane == 0) res->overflow = 2;
+            continue;
+        }
+        const uint8_t *rec = bam + starts[r + first];
+        const uint8_t *seq = rec + kHead + rec[12] + 4u * rd16(rec + 16);
+        const uint32_t l_seq = size - 1;
+        for (uint32_t j = lane; j < l_seq; j += 64) text[at + j] = (char)base_at(seq, j);
+        if (lane == 0) text[at + l_seq] = '\n';
+    }
+}
+
+// device arrays of one conversion: starts and sizes per record, a sum per tile, the result
+struct BamWork {
+    uint32_t *d_starts = nullptr, *d_sizes = nullptr;
+    unsigned long long *d_sums = nullptr;
+    BamResult *d_res = nullptr;
+    Seg *d_segs = nullptr;
+    unsigned long long *d_entry = nullptr;
+    uint32_t *d_base = nullptr;
+    uint64_t cap_records = 0;
+    int reserve(uint64_t len) {
+        const uint64_t need = len / kHead + 1;
+        if (!d_res) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_res), sizeof(BamResult)));
+        if (!d_segs) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_segs), kMaxSegs * sizeof(Seg)));
+        if (!d_entry) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_entry), kMaxSegs * 8));
+        if (!d_base) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_base), kMaxSegs * 4));
+        if (need <= cap_records) return BT_OK;
+        release_arrays();
+        const uint64_t cap = need + need / 4;
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_starts), cap * 4));
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sizes), cap * 4));
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sums), (cap / kTile + 1) * 8));
+        cap_records = cap;
+        return BT_OK;
+    }
+    void release_arrays() {
+        if (d_starts) (void)hipFree(d_starts);
+        if (d_sizes) (void)hipFree(d_sizes);
+        if (d_sums) (void)hipFree(d_sums);
+        d_starts = d_sizes = nullptr;
+        d_sums = nullptr;
+        cap_records = 0;
+    }
+    ~BamWork() {
+        release_arrays();
+        for (void *p : {(void *)d_res, (void *)d_segs, (void *)d_entry, (void *)d_base})
+            if (p) (void)hipFree(p);
+    }
+};
+
+std::string record_error(uint64_t offset, uint32_t e) { return "BAM record at offset " + std::to_string(offset) + ": " + record_error_text(e); }
+
+// d_bam [len] -> d_text; complete on return.  stream_offset: where d_bam[0] lies in the decompressed stream, for messages.
+int bam_text_run(const char *who, bt_ctx *ctx, BamWork &w, const uint8_t *d_bam, uint64_t len, uint32_t skip_flags, char *d_text, uint64_t capacity, uint64_t stream_offset,
+                 uint64_t *text_bytes, uint64_t *consumed, bt_bam_stats *stats) {
+    *text_bytes = *consumed = 0;
+    if (stats) *stats = bt_bam_stats{0, 0, 0};
+    if (len < 4) return BT_OK;
+    if (len >= 0xFFFFFFFFull) return fail(std::string(who) + ": at most 4 GiB - 2 of records per call");
+    BT_HIP(hipSetDevice(ctx->device));
+    if (w.reserve(len) != BT_OK) return BT_ERR;
+    BamResult r;
+    std::memset(&r, 0, sizeof r);
+    r.err = kNoError;
+    BT_HIP(hipMemcpyAsync(w.d_res, &r, sizeof r, hipMemcpyHostToDevice, ctx->stream));
+    BT_HIP(hipStreamSynchronize(ctx->stream));   // (r is pageable: the copy has left it)
+    const uint64_t seg_len = std::max<uint64_t>(kMinSeg, (len + kMaxSegs - 1) / kMaxSegs);
+    const uint32_t num_segs = (uint32_t)((len + seg_len - 1) / seg_len);
+    hipLaunchKernelGGL(bam_guess_kernel, dim3(num_segs), dim3(64), 0, ctx->stream, d_bam, len, seg_len, w.d_segs);
+    BT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bam_stitch_kernel, dim3(1), dim3(256), 0, ctx->stream, d_bam, len, seg_len, num_segs, (const Seg *)w.d_segs, w.d_entry, w.d_base, w.d_res);
+    BT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bam_fill_kernel, dim3((num_segs + 63) / 64), dim3(64), 0, ctx->stream, d_bam, len, seg_len, num_segs, (const unsigned long long *)w.d_entry,
+                       (const uint32_t *)w.d_base, w.d_starts, (uint32_t)std::min<uint64_t>(w.cap_records, 0xFFFFFFFFu), w.d_res);
+    BT_CHECK_LAUNCH();
+    BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+    BT_HIP(hipStreamSynchronize(ctx->stream));
+    if (r.overflow) return fail(std::string(who) + ": more records than the shortest record allows");
+    const uint32_t n = r.n_records, nb = (n + kTile - 1) / kTile;
+    if (n) {
+        hipLaunchKernelGGL(bam_measure_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_bam, len, (const uint32_t *)w.d_starts, n, skip_flags, w.d_sizes, w.d_sums, w.d_res);
+        BT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bam_offsets_kernel, dim3(1), dim3(256), 0, ctx->stream, w.d_sums, nb, w.d_res);
+        BT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bam_emit_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_bam, (const uint32_t *)w.d_starts, (const uint32_t *)w.d_sizes, (const unsigned long long *)w.d_sums, n,
+                           d_text, capacity, w.d_res);
+        BT_CHECK_LAUNCH();
+        BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (r.err != kNoError) return fail(record_error(stream_offset + (r.err >> 2), (uint32_t)(r.err & 3u)));
+    if (r.overflow) return fail(std::string(who) + ": capacity " + std::to_string(capacity) + " below the text's " + std::to_string(r.text_bytes) + " bytes");
+    *text_bytes = r.text_bytes;
+    *consumed = r.consumed;
+    if (stats) *stats = bt_bam_stats{r.kept, r.skipped, r.bases};
+    return BT_OK;
+}
+
+// the same walk on the host (bt_bam.hpp)
+int bam_text_host(const char *who, const uint8_t *bam, uint64_t len, uint32_t skip_flags, char *text, uint64_t capacity, uint64_t stream_offset, uint64_t *text_bytes, uint64_t *consumed,
+                  bt_bam_stats *stats) {
+    *text_bytes = *consumed = 0;
+    if (stats) *stats = bt_bam_stats{0, 0, 0};
+    const HostText t = reads_text_host(bam, len, skip_flags, text, capacity);
+    if (t.err != kRecOk) return fail(record_error(stream_offset + t.err_offset, t.err));
+    if (t.too_small) return fail(std::string(who) + ": capacity " + std::to_string(capacity) + " too small for the text");
+    *text_bytes = t.text_bytes;
+    *consumed = t.consumed;
+    if (stats) *stats = bt_bam_stats{t.kept, t.skipped, t.bases};
+    return BT_OK;
+}
+
+}  // namespace
+
+// Slabs of whole BGZF blocks in, reads text out.  The decompressed bytes of a call land behind the tail the call before left (the record that was not whole);
+// d_raw and d_text grow to what a call needs and are kept.
+struct bt_bam_scan {
+    bt_ctx *ctx = nullptr;
+    uint64_t max_in_bytes = 0;
+    uint32_t skip_flags = 0;
+    uint8_t *pin[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};   // the staging slots: the context's when they are large enough
+    size_t stage_bytes = 0;
+    uint64_t calls = 0;
+    std::vector<bt_bgzf_block> blocks;
+    bt_bgzf_block *d_blocks = nullptr;
+    uint32_t *d_status = nullptr;
+    uint64_t cap_blocks = 0;
+    uint8_t *d_raw = nullptr, *d_tail = nullptr;
+    char *d_text = nullptr;
+    uint64_t cap_raw = 0, cap_tail = 0, cap_text = 0;
+    uint64_t tail = 0;                          // bytes of the record that was not whole, in d_tail
+    uint64_t file_offset = 0, stream_offset = 0;   // compressed bytes taken so far; decompressed offset of d_raw[0]
+    uint64_t skip_left = 0;                     // header bytes still to step over
+    BamWork work;
+};
+
+namespace {
+
+int grow(void **p, uint64_t *cap, uint64_t need) {
+    if (need <= *cap) return BT_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const uint64_t bytes = need + need / 4 + 256;
+    BT_HIP(hipMalloc(p, bytes));
+    *cap = bytes;
+    return BT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bt_bam_reads_text(bt_ctx *ctx, const uint8_t *d_bam, uint64_t len, uint32_t skip_flags, char *d_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed, bt_bam_stats *stats) {
+    if (!ctx || (len && !d_bam) || (capacity && !d_text) || !text_bytes || !consumed) return fail("bt_bam_reads_text: null argument");
+    BamWork w;
+    return bam_text_run("bt_bam_reads_text", ctx, w, d_bam, len, skip_flags, d_text, capacity, 0, text_bytes, consumed, stats);
+}
+
+int bt_diag_bam_reads_text(const uint8_t *h_bam, uint64_t len, uint32_t skip_flags, char *h_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed, bt_bam_stats *stats) {
+    if ((len && !h_bam) || (capacity && !h_text) || !text_bytes || !consumed) return fail("bt_diag_bam_reads_text: null argument");
+    return bam_text_host("bt_diag_bam_reads_text", h_bam, len, skip_flags, h_text, capacity, 0, text_bytes, consumed, stats);
+}
+
+int bt_bam_scan_create(bt_ctx *ctx, uint64_t max_in_bytes, uint32_t skip_flags, bt_bam_scan **out) {
+    if (!ctx || !out) return fail("bt_bam_scan_create: null argument");
+    if (max_in_bytes < 65536 || max_in_bytes > (1ull << 30)) return fail("bt_bam_scan_create: max_in_bytes must lie in 64 KiB .. 1 GiB (a slab holds at least one whole BGZF block)");
+    BT_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<bt_bam_scan> s(new bt_bam_scan);
+    s->ctx = ctx;
+    s->max_in_bytes = max_in_bytes;
+    s->skip_flags = skip_flags;
+    const size_t need = (size_t)(max_in_bytes + 15) / 16 * 16;
+    if (ctx->kmc_stage_bytes >= need && ctx->kmc_pin[0] && ctx->kmc_pin[1] && ctx->kmc_dev[0] && ctx->kmc_dev[1]) {
+        s->stage_bytes = ctx->kmc_stage_bytes;
+        for (int b = 0; b < 2; ++b) {
+            s->pin[b] = ctx->kmc_pin[b];
+            s->dev[b] = ctx->kmc_dev[b];
+            ctx->kmc_pin[b] = ctx->kmc_dev[b] = nullptr;
+        }
+        ctx->kmc_stage_bytes = 0;
+    } else {
+        s->stage_bytes = need;
+        // one slot: a call is complete on return, so no transfer overlaps the kernels of the call before (the context's slots come as a pair and go back as one)
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&s->pin[0]), need, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->dev[0]), need + 16);
+        if (e != hipSuccess) {
+            bt_bam_scan_destroy(s.release());
+            return fail(std::string("bt_bam_scan_create: ") + hipGetErrorString(e));
+        }
+    }
+    *out = s.release();
+    return BT_OK;
+}
+
+int bt_bam_scan_text(bt_bam_scan *s, const uint8_t *h_blocks, uint64_t n_bytes, uint64_t skip_first_bytes, const char **d_text, uint64_t *text_len, bt_bam_stats *stats) {
+    const char *who = "bt_bam_scan_text";
+    if (!s || (n_bytes && !h_blocks) || !d_text || !text_len) return fail("bt_bam_scan_text: null argument");
+    *d_text = nullptr;
+    *text_len = 0;
+    if (stats) *stats = bt_bam_stats{0, 0, 0};
+    if (n_bytes > s->max_in_bytes) return fail("bt_bam_scan_text: " + std::to_string(n_bytes) + " bytes handed in, the stream was created for " + std::to_string(s->max_in_bytes));
+    if (skip_first_bytes && s->calls) return fail("bt_bam_scan_text: skip_first_bytes belongs to the first call");
+    bt_ctx *ctx = s->ctx;
+    BT_HIP(hipSetDevice(ctx->device));
+    if (!s->calls) s->skip_left = skip_first_bytes;
+    // the blocks of the slab
+    uint64_t n_blocks = 0, taken = 0, total = 0;
+    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, nullptr, 0, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
+    if (taken != n_bytes) return fail("bt_bam_scan_text: the slab ends inside the BGZF block at offset " + std::to_string(s->file_offset + taken) + " (whole blocks are handed in)");
+    s->blocks.resize(n_blocks);
+    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, s->blocks.data(), n_blocks, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
+    const int b = 0;   // (one slot: nothing of this call overlaps the next)
+    ++s->calls;
+    if (n_blocks > s->cap_blocks) {
+        if (s->d_blocks) (void)hipFree(s->d_blocks);
+        if (s->d_status) (void)hipFree(s->d_status);
+        s->d_blocks = nullptr;
+        s->d_status = nullptr;
+        s->cap_blocks = 0;
+        const uint64_t cap = n_blocks + n_blocks / 4 + 64;
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_blocks), cap * sizeof(bt_bgzf_block)));
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_status), (cap + 1) * 4));
+        s->cap_blocks = cap;
+    }
+    const uint64_t raw = s->tail + total;
+    if (raw >= 0xFFFFFFFFull)
+        return fail("bt_bam_scan_text: the slab at offset " + std::to_string(s->file_offset) + " inflates to " + std::to_string(total) + " bytes (" + std::to_string(s->tail) +
+                    " carried over): 4 GiB - 2 of records is the most a call takes; hand in smaller slabs");
+    if (grow(reinterpret_cast<void **>(&s->d_raw), &s->cap_raw, raw) != BT_OK) return BT_ERR;
+    if (grow(reinterpret_cast<void **>(&s->d_text), &s->cap_text, raw) != BT_OK) return BT_ERR;
+    // through the pinned slot to the device, the tail in front, the blocks' data behind it
+    if (n_bytes) {
+        std::memcpy(s->pin[b], h_blocks, n_bytes);
+        BT_HIP(hipMemcpyAsync(s->dev[b], s->pin[b], n_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_blocks) BT_HIP(hipMemcpyAsync(s->d_blocks, s->blocks.data(), n_blocks * sizeof(bt_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
+    if (s->tail) BT_HIP(hipMemcpyAsync(s->d_raw, s->d_tail, s->tail, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_blocks) {
+        if (bgzf_inflate_launch(ctx, s->dev[b], n_bytes, s->d_blocks, n_blocks, s->d_raw + s->tail, total, s->d_status) != BT_OK) return BT_ERR;
+        if (bgzf_inflate_result(ctx, s->d_blocks, n_blocks, s->d_status, s->file_offset) != BT_OK) return BT_ERR;
+    }
+    BT_HIP(hipStreamSynchronize(ctx->stream));   // (the blocks' table and the pinned slot have been read)
+    s->file_offset += n_bytes;
+    // the header's bytes are stepped over; they never meet a tail, since no record precedes them
+    const uint64_t skip = std::min(s->skip_left, raw);
+    s->skip_left -= skip;
+    uint64_t consumed = 0;
+    const uint8_t *d_records = s->d_raw + skip;
+    if (bam_text_run(who, ctx, s->work, d_records, raw - skip, s->skip_flags, s->d_text, s->cap_text, s->stream_offset + skip, text_len, &consumed, stats) != BT_OK) return BT_ERR;
+    // what is left is the start of a record that is not whole: it waits in d_tail for the next call
+    const uint64_t rest = raw - skip - consumed;
+    s->stream_offset += skip + consumed;
+    if (rest >= 4) {
+        uint8_t head[4];
+        BT_HIP(hipMemcpyAsync(head, d_records + consumed, 4, hipMemcpyDeviceToHost, ctx->stream));
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+        const uint64_t record = 4ull + rd32(head), limit = 8 * s->max_in_bytes;
+        if (record > limit)
+            return fail("bt_bam_scan_text: the BAM record at offset " + std::to_string(s->stream_offset) + " takes " + std::to_string(record) + " bytes, more than a slab may hold (" +
+                        std::to_string(limit) + ", 8 x max_in_bytes)");
+    }
+    if (rest) {
+        if (grow(reinterpret_cast<void **>(&s->d_tail), &s->cap_tail, rest) != BT_OK) return BT_ERR;
+        BT_HIP(hipMemcpyAsync(s->d_tail, d_records + consumed, rest, hipMemcpyDeviceToDevice, ctx->stream));
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    s->tail = rest;
+    *d_text = s->d_text;
+    return BT_OK;
+}
+
+int bt_bam_scan_finish(bt_bam_scan *s) {
+    if (!s) return fail("bt_bam_scan_finish: null argument");
+    if (s->skip_left) return fail("bt_bam_scan_finish: the file ends inside the BAM header (" + std::to_string(s->skip_left) + " bytes missing): truncated");
+    if (s->tail)
+        return fail("bt_bam_scan_finish: the file ends inside the BAM record at offset " + std::to_string(s->stream_offset) + " (" + std::to_string(s->tail) + " bytes of it are there): truncated");
+    return BT_OK;
+}
+
+void bt_bam_scan_destroy(bt_bam_scan *s) {
+    if (!s) return;
+    bt_ctx *ctx = s->ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    // the slots go (back) to the context when they are whole and no smaller than what it holds
+    const bool whole = s->pin[0] && s->pin[1] && s->dev[0] && s->dev[1];
+    if (whole && s->stage_bytes >= ctx->kmc_stage_bytes && !ctx_caches_off()) {
+        for (int b = 0; b < 2; ++b) {
+            if (ctx->kmc_pin[b]) (void)hipHostFree(ctx->kmc_pin[b]);
+            if (ctx->kmc_dev[b]) (void)hipFree(ctx->kmc_dev[b]);
+            ctx->kmc_pin[b] = s->pin[b];
+            ctx->kmc_dev[b] = s->dev[b];
+        }
+        ctx->kmc_stage_bytes = s->stage_bytes;
+    } else
+        for (int b = 0; b < 2; ++b) {
+            if (s->pin[b]) (void)hipHostFree(s->pin[b]);
+            if (s->dev[b]) (void)hipFree(s->dev[b]);
+        }
+    for (void *p : {(void *)s->d_blocks, (void *)s->d_status, (void *)s->d_raw, (void *)s->d_tail, (void *)s->d_text})
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+}  // extern "C"

@@ -128,6 +128,12 @@ struct GenoTextShape {
 int geno_text_shape(bt_ctx *ctx, const uint32_t *d_words, uint64_t num_words, GenoTextShape &sh, const char *who);
 int geno_text_count(bt_ctx *ctx, const uint32_t *d_words, const GenoTextShape &sh, uint32_t *d_index, uint64_t *text_bytes, uint32_t *not_covered, const char *who);
 int geno_text_write(bt_ctx *ctx, const uint32_t *d_words, const GenoTextShape &sh, uint32_t *d_index, uint8_t *d_text);
+
+// The seam between bt_inflate.hip and bt_bam.hip (bt_bam_scan_text): bt_bgzf_inflate over a status array the caller keeps.  d_status: n_blocks + 1 words, a
+// block's status each and the first failing block's index behind them.  _launch enqueues on the context's stream; _result waits and turns the first
+// failing block into the error message (file_offset: where d_in[0] lies in the file).
+int bgzf_inflate_launch(bt_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, const bt_bgzf_block *d_blocks, uint64_t n_blocks, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_status);
+int bgzf_inflate_result(bt_ctx *ctx, const bt_bgzf_block *d_blocks, uint64_t n_blocks, const uint32_t *d_status, uint64_t file_offset);
 }  // namespace bt
 
 struct bt_timer {

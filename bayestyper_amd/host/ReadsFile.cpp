@@ -215,7 +215,10 @@ std::vector<std::string> readReadsList(const std::string &prefix) {
 
 
 ReadsTotals forEachReadsSlab(const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume) {
-    const std::vector<std::string> files = readReadsList(prefix);
+    return forEachReadsSlab(readReadsList(prefix), kmer_size, threads, slab_bytes, consume);
+}
+
+ReadsTotals forEachReadsSlab(const std::vector<std::string> &files, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume) {
     ReadsTotals totals;
     totals.files = files.size();
     std::atomic<size_t> next_file{0};

@@ -68,5 +68,7 @@ struct ReadsTotals {
     uint64_t bases = 0, reads = 0, slabs = 0, files = 0;
 };
 ReadsTotals forEachReadsSlab(const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume);
+// the same over the files given (SampleReads.hpp: the FASTA / FASTQ files of a list that also names BAM files)
+ReadsTotals forEachReadsSlab(const std::vector<std::string> &files, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume);
 
 }  // namespace bthost

@@ -1,0 +1,74 @@
+// Every read file of <prefix>.reads to the consumers of the reads scan (include/btgpu.h: bt_reads_*), whatever its format.  A file is told by its content, not by
+// its name: a BAM (BamFile::isBam) goes through the stream object of libbtgpu — compressed blocks in, reads text in device memory out (bt_bam_scan_text) — and
+// reaches `device_text`; every other file is read as FASTA / FASTQ on the host (forEachReadsSlab) and reaches `host_slab`, as before BAM was taken.
+#pragma once
+#include <functional>
+#include <iostream>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/btgpu.h"
+#include "BamFile.hpp"
+#include "ReadsFile.hpp"
+
+namespace bthost {
+
+struct ReadsSinks {
+    std::function<void(const std::string &)> host_slab;              // a slab of reads text in host memory
+    std::function<void(const char *, uint64_t)> device_text;         // reads text in device memory, valid until the call returns
+};
+
+// ReadsTotals of a BAM file: bases and reads of the kept records (flag & skip_flags == 0), slabs = calls of bt_bam_scan_text
+// *bam_files (may be NULL): how many of the list's files were BAM files
+inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const ReadsSinks &sinks,
+                                      size_t *bam_files = nullptr) {
+    std::vector<std::string> bams, texts;
+    for (const std::string &f : readReadsList(prefix)) (BamFile::isBam(f) ? bams : texts).push_back(f);
+    ReadsTotals totals;
+    if (bam_files) *bam_files = bams.size();
+    if (!bams.empty()) {
+        const uint32_t skip_flags = bamSkipFlags();
+        const size_t bam_slab = std::max<size_t>(slab_bytes / 2, 65536);   // compressed bytes: about a quarter of the text they hold
+        bt_bam_scan *scan = nullptr;
+        auto check = [](int rc, const std::string &file) {
+            if (rc != BT_OK) throw std::runtime_error("read file " + file + ": " + bt_last_error());
+        };
+        for (const std::string &f : bams) {
+            BamFile file(f, bam_slab);
+            static std::set<std::string> warned;   // once per file and process: makeBloom -r reads a file in two passes
+            if (!file.hasEofBlock() && warned.insert(f).second) std::cerr << "WARNING: read file " << f << " has no BGZF end-of-file block: it may be truncated" << std::endl;
+            check(bt_bam_scan_create(ctx, bam_slab, skip_flags, &scan), f);
+            try {
+                std::vector<uint8_t> slab;
+                for (bool first = true; file.next(slab); first = false) {
+                    const char *d_text = nullptr;
+                    uint64_t len = 0;
+                    bt_bam_stats stats;
+                    check(bt_bam_scan_text(scan, slab.data(), slab.size(), first ? file.skipFirstBytes() : 0, &d_text, &len, &stats), f);
+                    if (len) sinks.device_text(d_text, len);
+                    totals.bases += stats.bases;
+                    totals.reads += stats.kept;
+                    totals.slabs++;
+                }
+                check(bt_bam_scan_finish(scan), f);
+            } catch (...) {
+                bt_bam_scan_destroy(scan);
+                throw;
+            }
+            bt_bam_scan_destroy(scan);
+            totals.files++;
+        }
+    }
+    if (!texts.empty()) {
+        const ReadsTotals t = forEachReadsSlab(texts, kmer_size, threads, slab_bytes, sinks.host_slab);
+        totals.bases += t.bases;
+        totals.reads += t.reads;
+        totals.slabs += t.slabs;
+        totals.files += t.files;
+    }
+    return totals;
+}
+
+}  // namespace bthost

@@ -14,6 +14,7 @@
 #include "KmcFile.hpp"
 #include "KmerHashOrder.hpp"
 #include "Parallel.hpp"
+#include "BamFile.hpp"
 #include "ReadsFile.hpp"
 #include "InferenceUnit.hpp"
 #include "KmerCounter.hpp"
@@ -760,6 +761,43 @@ long long bth_reads_list(const char *prefix, char *buf, unsigned long long cap, 
         std::string all;
         for (const std::string &f : readReadsList(prefix)) all += f + "\n";
         return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// BamFile::isBam: 1 a BAM, 0 anything else, -1 an error (CRAM magic, an unreadable file; text in *err).  No GPU.
+int bth_bam_is_bam(const char *path, char *err, unsigned err_len) {
+    try {
+        return BamFile::isBam(path) ? 1 : 0;
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// BamFile: the slabs of one BAM file laid end to end -> buf (when it fits); stats[0..6] = header bytes, references, skipFirstBytes, file offset of the first slab,
+// has an EOF block, slabs, file bytes; returns the bytes needed, or -1 (error text in *err).  No GPU.
+long long bth_bam_file_slabs(const char *path, unsigned long long slab_bytes, char *buf, unsigned long long cap, unsigned long long *stats, char *err, unsigned err_len) {
+    try {
+        BamFile file(path, (size_t)slab_bytes);
+        std::string all;
+        std::vector<uint8_t> slab;
+        uint64_t slabs = 0, first_at = 0;
+        while (file.next(slab)) {
+            if (!slabs++) first_at = file.slabOffset();
+            all.append(reinterpret_cast<const char *>(slab.data()), slab.size());
+        }
+        if (stats) {
+            stats[0] = file.headerBytes(), stats[1] = file.references(), stats[2] = file.skipFirstBytes(), stats[3] = first_at;
+            stats[4] = file.hasEofBlock() ? 1 : 0, stats[5] = slabs, stats[6] = file.fileBytes();
+        }
+        return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// bamSkipFlags: BT_BAM_SKIP_FLAGS or 0x900; -1 when the variable is not a number below 65536 (text in *err)
+long long bth_bam_skip_flags(char *err, unsigned err_len) {
+    try {
+        return (long long)bamSkipFlags();
     } catch (const std::exception &e) {
         return stage_error(e, err, err_len);
     }

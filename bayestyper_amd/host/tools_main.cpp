@@ -4,9 +4,10 @@
 // --false-positive-rate 0.001), same progress lines, byte-identical output files (insertion is an order-independent OR).  The records are
 // streamed from the memory-mapped .kmc_suf through the GPU in chunks (bt_kmc_scan_make_bloom); there is no CPU path.
 // -r/--reads-prefix <prefix> is the alternative to -k for a sample without a KMC database: the read files listed in <prefix>.reads (FASTA / FASTQ, plain or
-// gzip) are streamed through bt_reads_make_bloom_host; the filter is sized by --num-kmers, or by a first pass that estimates the number of distinct k-mers
+// gzip, through bt_reads_make_bloom_host; BAM through bt_bam_scan_text + bt_reads_make_bloom) are streamed; the filter is sized by --num-kmers, or by a first pass that estimates the number of distinct k-mers
 // (bt_reads_sketch_host).  With the N of the sample's KMC database the bytes written are those of -k.
 // The VCF utilities of bayesTyperTools (convertAllele, combine, filter, annotate, addAttributes) are not part of this build.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <iostream>
@@ -16,6 +17,7 @@
 #include "KmcFile.hpp"
 #include "Options.hpp"
 #include "ReadsFile.hpp"
+#include "SampleReads.hpp"
 
 using namespace bthost;
 
@@ -36,9 +38,23 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
     try {
         if (num_kmers == 0) {
             std::cout << stamp() << "Estimating the number of distinct kmers in the reads of " << prefix << ".reads ..." << std::endl;
-            std::vector<uint8_t> registers(65536, 0);
-            forEachReadsSlab(prefix, kmer_size, threads, slab_bytes,
-                             [&](const std::string &slab) { check(bt_reads_sketch_host(ctx, slab.data(), slab.size(), kmer_size, 0, registers.data()), "bt_reads_sketch_host"); });
+            std::vector<uint8_t> registers(65536, 0), device_registers(65536, 0);
+            void *d_registers = nullptr;   // the sketch of the BAM files' reads, whose text stays on the device; a register-wise maximum joins the two
+            check(bt_malloc(ctx, registers.size(), &d_registers), "bt_malloc");
+            try {
+                check(bt_memset(ctx, d_registers, 0, registers.size()), "bt_memset");
+                ReadsSinks sinks;
+                sinks.host_slab = [&](const std::string &slab) { check(bt_reads_sketch_host(ctx, slab.data(), slab.size(), kmer_size, 0, registers.data()), "bt_reads_sketch_host"); };
+                sinks.device_text = [&](const char *d_text, uint64_t len) { check(bt_reads_sketch(ctx, d_text, len, kmer_size, (uint8_t *)d_registers), "bt_reads_sketch"); };
+                forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks);
+                check(bt_sync(ctx), "bt_sync");
+                check(bt_memcpy_d2h(ctx, device_registers.data(), d_registers, registers.size()), "bt_memcpy_d2h");
+            } catch (...) {
+                bt_free(ctx, d_registers);
+                throw;
+            }
+            bt_free(ctx, d_registers);
+            for (size_t i = 0; i < registers.size(); i++) registers[i] = std::max(registers[i], device_registers[i]);
             double estimate = 0;
             check(bt_reads_sketch_estimate(registers.data(), &estimate), "bt_reads_sketch_estimate");
             num_kmers = std::max<uint64_t>(1, (uint64_t)std::ceil(estimate));
@@ -47,9 +63,11 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
             std::cout << stamp() << "Using the given number of " << num_kmers << " distinct kmers\n" << std::endl;
         std::cout << stamp() << "Making bloom filter of " << num_kmers << " kmers with a false positive rate of " << fpr << " ...\n" << std::endl;
         check(bt_bloom_create(ctx, num_kmers, fpr, kmer_size, 0, &bloom), "bt_bloom_create");   // KmerBloom(N, fpr), MakeBloom.cpp:221
-        const ReadsTotals totals = forEachReadsSlab(prefix, kmer_size, threads, slab_bytes, [&](const std::string &slab) {
-            check(bt_reads_make_bloom_host(ctx, bloom, slab.data(), slab.size(), kmer_size, 0), "bt_reads_make_bloom_host");
-        });
+        ReadsSinks sinks;
+        sinks.host_slab = [&](const std::string &slab) { check(bt_reads_make_bloom_host(ctx, bloom, slab.data(), slab.size(), kmer_size, 0), "bt_reads_make_bloom_host"); };
+        sinks.device_text = [&](const char *d_text, uint64_t len) { check(bt_reads_make_bloom(ctx, bloom, d_text, len, kmer_size), "bt_reads_make_bloom"); };
+        const ReadsTotals totals = forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks);
+        check(bt_sync(ctx), "bt_sync");
         std::cout << stamp() << "Parsed " << totals.bases << " bases of " << totals.reads << " reads in " << totals.files << " file(s)" << std::endl;
         std::cout << "\n" << stamp() << "Saving bloom filter to " << prefix << " ..." << std::endl;
         check(bt_bloom_save(bloom, prefix.c_str()), "bt_bloom_save");
@@ -67,7 +85,7 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
 int runMakeBloom(int argc, char *const argv[], unsigned kmer_size) {
     const std::vector<OptionSpec> specs = {
         {"kmc-table-prefix", 'k', "Required (one of)", false, false, "", "KMC kmer table prefix. Output is written as <kmc-table-prefix>.bloomMeta and <kmc-table-prefix>.bloomData.", 's'},
-        {"reads-prefix", 'r', "Required (one of)", false, false, "", "sample prefix without a KMC table: the read files (FASTA/FASTQ, plain or gzip) listed in <reads-prefix>.reads are used. Output is written as <reads-prefix>.bloomMeta and <reads-prefix>.bloomData.", 's'},
+        {"reads-prefix", 'r', "Required (one of)", false, false, "", "sample prefix without a KMC table: the read files (FASTA/FASTQ, plain or gzip, or BAM) listed in <reads-prefix>.reads are used. Output is written as <reads-prefix>.bloomMeta and <reads-prefix>.bloomData.", 's'},
         {"num-threads", 'p', "General", false, false, "1", "number of threads used (+= 1 I/O thread).", 'u'},
         {"false-positive-rate", 0, "Parameters", false, false, "0.001", "bloom filter false positive rate.", 'f'},
         {"num-kmers", 0, "Parameters", false, false, "0", "number of distinct kmers the filter is made for (--reads-prefix only; 0 = estimate it in a first pass over the reads).", 'u'},

@@ -1229,6 +1229,151 @@ def bgzf_save(ctx, path, data, threads=1):
     return [int(o) for o in offs], st.as_dict()
 
 
+BGZF_BLOCK = np.dtype([("in_offset", np.uint64), ("out_offset", np.uint64), ("in_size", np.uint32), ("isize", np.uint32)])   # include/btgpu.h: bt_bgzf_block
+
+
+class BamStats(C.Structure):   # include/btgpu.h: bt_bam_stats
+    _fields_ = [("kept", C.c_uint64), ("skipped", C.c_uint64), ("bases", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+bt_bgzf_scan_blocks = _sig("bt_bgzf_scan_blocks", [vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p])
+bt_bgzf_inflate = _sig("bt_bgzf_inflate", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64])
+bt_diag_bgzf_inflate = _sig("bt_diag_bgzf_inflate", [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64])
+bt_bam_reads_text = _sig("bt_bam_reads_text", [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p, C.POINTER(BamStats)])
+bt_diag_bam_reads_text = _sig("bt_diag_bam_reads_text", [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p, C.POINTER(BamStats)])
+bt_bam_scan_create = _sig("bt_bam_scan_create", [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)])
+bt_bam_scan_text = _sig("bt_bam_scan_text", [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(BamStats)])
+bt_bam_scan_finish = _sig("bt_bam_scan_finish", [vp])
+bt_bam_scan_destroy = _sig("bt_bam_scan_destroy", [vp], None)
+BAM_SKIP_FLAGS = 0x900   # secondary and supplementary alignments: every read once
+
+
+def bgzf_scan_blocks(data):
+    """bt_bgzf_scan_blocks (no GPU): a buffer that starts at a BGZF block boundary -> (table of its whole blocks as a BGZF_BLOCK array, bytes they take,
+    sum of their ISIZEs); a trailing partial block is not taken"""
+    a = _bytes_array(data)
+    n, used, total = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(bt_bgzf_scan_blocks(_np_ptr(a) if a.size else None, a.size, None, 0, C.byref(n), C.byref(used), C.byref(total)))
+    blocks = np.zeros(n.value, BGZF_BLOCK)
+    check(bt_bgzf_scan_blocks(_np_ptr(a) if a.size else None, a.size, _np_ptr(blocks), blocks.size, C.byref(n), C.byref(used), C.byref(total)))
+    return blocks, used.value, total.value
+
+
+def _bgzf_job(data, blocks, out_bytes):
+    a = _bytes_array(data)
+    if blocks is None:
+        blocks, used, total = bgzf_scan_blocks(a)
+        if used != a.size:
+            raise BtError(f"BGZF block at offset {used}: incomplete (the buffer ends inside it)")
+    blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK)
+    if out_bytes is None:
+        out_bytes = int(max((int(b["out_offset"]) + int(b["isize"]) for b in blocks), default=0))
+    return a, blocks, out_bytes
+
+
+def diag_bgzf_inflate(data, blocks=None, out=None, capacity=None, out_bytes=None, file_offset=0):
+    """bt_diag_bgzf_inflate: the device's BGZF reader run on the host (a team of one thread) -> the blocks' data as bytes.  blocks: a table other than
+    bgzf_scan_blocks(data)'s; out: a uint8 array to write into (capacity: how much of it the call may use)"""
+    a, blocks, out_bytes = _bgzf_job(data, blocks, out_bytes)
+    if out is None:
+        out = np.zeros(max(out_bytes, 1), np.uint8)
+    cap = out.size if capacity is None else capacity
+    check(bt_diag_bgzf_inflate(_np_ptr(a) if a.size else None, a.size, _np_ptr(blocks) if blocks.size else None, blocks.size, _np_ptr(out), cap, out_bytes, file_offset))
+    return out[:out_bytes].tobytes()
+
+
+def bgzf_inflate(ctx, data, blocks=None, capacity=None, out_bytes=None, file_offset=0, guard=0, keep=None):
+    """bt_bgzf_inflate over a host buffer: blocks and table uploaded, inflated on the device, downloaded -> the blocks' data as bytes.  guard: bytes
+    allocated behind the output (preset to 0xA5) and returned with it; keep: a dict that receives the output as downloaded even when the call fails"""
+    a, blocks, out_bytes = _bgzf_job(data, blocks, out_bytes)
+    cap = out_bytes if capacity is None else capacity
+    d_in, d_tab, d_out = DeviceBuffer(ctx, a.size), DeviceBuffer(ctx, blocks.nbytes), DeviceBuffer(ctx, max(cap, out_bytes) + guard)
+    try:
+        if a.size:
+            d_in.upload(a)
+        if blocks.size:
+            d_tab.upload(blocks)
+        check(bt_memset(ctx.h, d_out.ptr, 0xA5, d_out.nbytes))
+        try:
+            check(bt_bgzf_inflate(ctx.h, d_in.ptr if a.size else None, a.size, d_tab.ptr if blocks.size else None, blocks.size, d_out.ptr, cap, out_bytes, file_offset))
+        finally:
+            if keep is not None:
+                ctx.sync()
+                keep["out"] = d_out.download(np.uint8, out_bytes + guard).tobytes()
+        return d_out.download(np.uint8, out_bytes + guard).tobytes()
+    finally:
+        d_in.free()
+        d_tab.free()
+        d_out.free()
+
+
+def diag_bam_reads_text(bam, skip_flags=BAM_SKIP_FLAGS, capacity=None):
+    """bt_diag_bam_reads_text (no GPU): inflated BAM records from a record boundary on -> (reads text as bytes, offset of the first record that is not
+    whole, stats)"""
+    a = _bytes_array(bam)
+    cap = a.size if capacity is None else capacity
+    out, n, used, st = np.full(cap + 16, 0xA5, np.uint8), C.c_uint64(), C.c_uint64(), BamStats()
+    check(bt_diag_bam_reads_text(_np_ptr(a) if a.size else None, a.size, skip_flags, _np_ptr(out), cap, C.byref(n), C.byref(used), C.byref(st)))
+    assert (out[cap:] == 0xA5).all()
+    return out[:n.value].tobytes(), used.value, st.as_dict()
+
+
+def bam_reads_text(ctx, bam, skip_flags=BAM_SKIP_FLAGS, capacity=None, misalign=0):
+    """bt_bam_reads_text over a host buffer (uploaded `misalign` bytes into its allocation) -> (reads text as bytes, offset of the first record that is not
+    whole, stats)"""
+    a = _bytes_array(bam)
+    cap = a.size if capacity is None else capacity
+    d_in, d_out = DeviceBuffer(ctx, a.size + misalign), DeviceBuffer(ctx, cap + 16)
+    try:
+        if a.size:
+            check(bt_memcpy_h2d(ctx.h, d_in.ptr + misalign, _np_ptr(a), a.size))
+        check(bt_memset(ctx.h, d_out.ptr, 0xA5, d_out.nbytes))
+        n, used, st = C.c_uint64(), C.c_uint64(), BamStats()
+        check(bt_bam_reads_text(ctx.h, d_in.ptr + misalign if a.size else None, a.size, skip_flags, d_out.ptr, cap, C.byref(n), C.byref(used), C.byref(st)))
+        out = d_out.download(np.uint8, cap + 16)
+        assert (out[cap:] == 0xA5).all()
+        return out[:n.value].tobytes(), used.value, st.as_dict()
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+class BamScan:
+    """bt_bam_scan: slabs of whole BGZF blocks of a BAM file -> reads text in device memory"""
+
+    def __init__(self, ctx, max_in_bytes, skip_flags=BAM_SKIP_FLAGS):
+        self.ctx = ctx
+        h = vp()
+        check(bt_bam_scan_create(ctx.h, max_in_bytes, skip_flags, C.byref(h)))
+        self.h = h.value
+
+    def text(self, blocks, skip_first_bytes=0):
+        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
+        a = _bytes_array(blocks)
+        d, n, st = vp(), C.c_uint64(), BamStats()
+        check(bt_bam_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, skip_first_bytes, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def text_bytes(self, blocks, skip_first_bytes=0):
+        """text(), downloaded -> (bytes, stats)"""
+        d, n, st = self.text(blocks, skip_first_bytes)
+        out = np.empty(n, np.uint8)
+        if n:
+            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
+        return out.tobytes(), st
+
+    def finish(self):
+        check(bt_bam_scan_finish(self.h))
+
+    def close(self):
+        if self.h:
+            bt_bam_scan_destroy(self.h)
+            self.h = None
+
+
 def parse_genotype_text(text, index):
     """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
     dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer

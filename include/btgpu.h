@@ -926,6 +926,64 @@ int bt_diag_bgzf(const uint8_t *h_in, uint64_t n, int eof, uint8_t *h_out, uint6
 /* Host-side run of the blocks' CRC-32 routine: zlib's crc32 of h_in [n] (contents longer than a block: per block, joined as crc32_combine does). */
 int bt_diag_crc32(const uint8_t *h_in, uint64_t n, uint32_t *crc);
 
+/* ------------------------------------------------------------------------------------------
+ * BAM samples on the device: BGZF read (SAM specification section 4.1) and alignment records -> reads text (section 4.2).
+ * Replaces the `samtools fastq` a user would run before the reads route (bt_reads_count / bt_reads_make_bloom / bt_reads_sketch) can take the BAM the
+ * reference's workflow counts with `kmc -fbam`.  bayestyper_amd/csrc/bt_inflate.hpp holds the decoder (stored, fixed and dynamic blocks, several per
+ * BGZF block), bayestyper_amd/csrc/bt_bam.hpp the record's code, each one text for the kernels and the host.  One BGZF block per wavefront; no
+ * workgroup waits on another.  Damaged input is an error naming the block or the record, never a fault: every load is bounded by the block's payload,
+ * every store by its ISIZE.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bt_bgzf_block {
+    uint64_t in_offset;    /* the block's first byte in the input buffer */
+    uint64_t out_offset;   /* where its data goes in the output: the sum of the ISIZEs before it */
+    uint32_t in_size;      /* the whole block: BSIZE + 1 (SAM 4.1) */
+    uint32_t isize;        /* its data's length, at most 65536 (SAM 4.1: ISIZE) */
+} bt_bgzf_block;
+/* Host only, no GPU.  h_in [n] starts at a block boundary -> h_blocks (may be NULL: the blocks are counted; else at most blocks_capacity are taken) for
+ * every WHOLE block, *consumed = the bytes they take, *out_bytes = the sum of their ISIZEs.  Every header field is checked (SAM 4.1: ID1 ID2, CM = 8,
+ * FLG = 4, the BC subfield of two bytes inside XLEN, BSIZE no smaller than header + trailer, ISIZE <= 65536): a violation is an error naming the block's
+ * offset.  A trailing partial block is not consumed and is no error. */
+int bt_bgzf_scan_blocks(const uint8_t *h_in, uint64_t n, bt_bgzf_block *h_blocks, uint64_t blocks_capacity, uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes);
+/* d_in [in_bytes] and d_blocks [n_blocks] (a table of bt_bgzf_scan_blocks, in device memory) -> d_out: each block's data at its out_offset (SAM 4.1), its
+ * CRC-32 checked against the trailer.  out_bytes = the table's total; capacity below it is an error before any launch, and nothing is written at or past
+ * out_bytes: an entry that reaches outside d_in or out_bytes fails as a block.  The first failing block (smallest index) is the error, as
+ * "BGZF block at offset <file_offset + in_offset>: <condition>"; the other blocks' data is written all the same.  Complete on return. */
+int bt_bgzf_inflate(bt_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, const bt_bgzf_block *d_blocks, uint64_t n_blocks, uint8_t *d_out, uint64_t capacity, uint64_t out_bytes,
+                    uint64_t file_offset);
+/* Host-side run of bt_bgzf_inflate (SAM 4.1; the same __host__ __device__ code with a team of one thread, no GPU): the same bytes, the same message. */
+int bt_diag_bgzf_inflate(const uint8_t *h_in, uint64_t in_bytes, const bt_bgzf_block *h_blocks, uint64_t n_blocks, uint8_t *h_out, uint64_t capacity, uint64_t out_bytes,
+                         uint64_t file_offset);
+
+typedef struct bt_bam_stats {
+    uint64_t kept, skipped, bases;   /* records written to the text, records left out by skip_flags, bases of the kept records */
+} bt_bam_stats;
+/* d_bam [len] (inflated BAM, SAM 4.2, from a record boundary on; len < 4 GiB - 1) -> d_text: for every WHOLE record with flag & skip_flags == 0, in record
+ * order, its l_seq bases and '\n' (4-bit codes 1 2 4 8 -> A C G T, every other code -> N; l_seq = 0 gives an empty line; nothing is reverse-complemented).
+ * *consumed = the offset of the first record that is not whole; *text_bytes = the text's length; capacity >= len always suffices, a smaller one that
+ * does not is an error and nothing is written past it.  A record whose block_size is below 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq,
+ * or whose l_seq is negative, is an error naming its offset (the one at the smallest offset).  stats may be NULL.  Complete on return. */
+int bt_bam_reads_text(bt_ctx *ctx, const uint8_t *d_bam, uint64_t len, uint32_t skip_flags, char *d_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed,
+                      bt_bam_stats *stats);
+/* Host-side run of bt_bam_reads_text (SAM 4.2; the same record code, no GPU): the same text, numbers and message. */
+int bt_diag_bam_reads_text(const uint8_t *h_bam, uint64_t len, uint32_t skip_flags, char *h_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed, bt_bam_stats *stats);
+
+/* The stream object (SAM 4.1 + 4.2): a BAM file's compressed blocks in slabs -> reads text on the device.  max_in_bytes (64 KiB .. 1 GiB): the largest slab.
+ * The slabs go through the context's pinned staging slots (taken when they are large enough, handed back by _destroy). */
+typedef struct bt_bam_scan bt_bam_scan;
+int bt_bam_scan_create(bt_ctx *ctx, uint64_t max_in_bytes, uint32_t skip_flags, bt_bam_scan **out);
+/* h_blocks [n_bytes]: WHOLE BGZF blocks in host memory (SAM 4.1; a slab that ends inside a block is an error), in file order from call to call.  They are
+ * inflated behind the tail the previous call left (the record that was not whole) and turned into text: *d_text [*text_len] is device memory, valid until
+ * the next call on this object, and fit for bt_reads_count / bt_reads_make_bloom / bt_reads_sketch as it stands (whole reads, no halo needed).
+ * skip_first_bytes (first call only): decompressed bytes to step over, the BAM header's; a header longer than the first slab runs on into the next.
+ * Blocks with ISIZE 0 (the EOF block, empty blocks mid-file) are legal anywhere.  A record of more than 8 x max_in_bytes bytes is refused.  A slab whose
+ * data, with the carried tail, would reach 4 GiB is refused with a message that asks for smaller slabs.  stats (may be
+ * NULL): this call's.  After an error the object can only be destroyed.  Complete on return. */
+int bt_bam_scan_text(bt_bam_scan *scan, const uint8_t *h_blocks, uint64_t n_bytes, uint64_t skip_first_bytes, const char **d_text, uint64_t *text_len, bt_bam_stats *stats);
+/* SAM 4.2: the file has to end at a record boundary: an error when part of a record (or of the header) is left over — a truncated file. */
+int bt_bam_scan_finish(bt_bam_scan *scan);
+void bt_bam_scan_destroy(bt_bam_scan *scan);
+
 #ifdef __cplusplus
 }
 #endif
