@@ -1,6 +1,6 @@
 // libbtgpu: a BAM sample's reads as the reads text of bt_reads.hip, on the device.
 //   bt_bam_reads_text      inflated BAM records -> "<bases>\n" per kept record (bt_bam.hpp holds the record's code, one text for kernels and host)
-//   bt_bam_scan_*          the stream object: slabs of whole BGZF blocks from the host -> inflate (bt_inflate.hip) behind the carried tail -> text
+//   bt_bam_scan_*          the stream object: slabs of whole BGZF blocks from the host -> inflate (bt_bgzf_stream.hpp) behind the carried tail -> text
 //   bt_diag_bam_reads_text the host run of the same record code
 // What `samtools fastq` does on the host before the reads of a BAM can enter the reads route (the reference's workflow counts BAMs with kmc -fbam).
 //
@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "bt_bam.hpp"
+#include "bt_bgzf_stream.hpp"
 #include "bt_internal.hpp"
 
 using namespace bt;
@@ -344,42 +345,15 @@ int bam_text_host(const char *who, const uint8_t *bam, uint64_t len, uint32_t sk
 
 }  // namespace
 
-// Slabs of whole BGZF blocks in, reads text out.  The decompressed bytes of a call land behind the tail the call before left (the record that was not whole);
-// d_raw and d_text grow to what a call needs and are kept.
+// Slabs of whole BGZF blocks in, reads text out.  The decompressed bytes of a call land behind the tail the call before left (the record that was not whole):
+// bt_bgzf_stream.hpp holds that part, which bt_fastq_scan shares.
 struct bt_bam_scan {
-    bt_ctx *ctx = nullptr;
-    uint64_t max_in_bytes = 0;
+    BgzfStream st;
     uint32_t skip_flags = 0;
-    uint8_t *pin[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};   // the staging slots: the context's when they are large enough
-    size_t stage_bytes = 0;
-    uint64_t calls = 0;
-    std::vector<bt_bgzf_block> blocks;
-    bt_bgzf_block *d_blocks = nullptr;
-    uint32_t *d_status = nullptr;
-    uint64_t cap_blocks = 0;
-    uint8_t *d_raw = nullptr, *d_tail = nullptr;
-    char *d_text = nullptr;
-    uint64_t cap_raw = 0, cap_tail = 0, cap_text = 0;
-    uint64_t tail = 0;                          // bytes of the record that was not whole, in d_tail
-    uint64_t file_offset = 0, stream_offset = 0;   // compressed bytes taken so far; decompressed offset of d_raw[0]
-    uint64_t skip_left = 0;                     // header bytes still to step over
+    uint64_t stream_offset = 0;   // decompressed offset of d_raw[0]
+    uint64_t skip_left = 0;       // header bytes still to step over
     BamWork work;
 };
-
-namespace {
-
-int grow(void **p, uint64_t *cap, uint64_t need) {
-    if (need <= *cap) return BT_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const uint64_t bytes = need + need / 4 + 256;
-    BT_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return BT_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -396,30 +370,12 @@ int bt_diag_bam_reads_text(const uint8_t *h_bam, uint64_t len, uint32_t skip_fla
 
 int bt_bam_scan_create(bt_ctx *ctx, uint64_t max_in_bytes, uint32_t skip_flags, bt_bam_scan **out) {
     if (!ctx || !out) return fail("bt_bam_scan_create: null argument");
-    if (max_in_bytes < 65536 || max_in_bytes > (1ull << 30)) return fail("bt_bam_scan_create: max_in_bytes must lie in 64 KiB .. 1 GiB (a slab holds at least one whole BGZF block)");
-    BT_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<bt_bam_scan> s(new bt_bam_scan);
-    s->ctx = ctx;
-    s->max_in_bytes = max_in_bytes;
     s->skip_flags = skip_flags;
-    const size_t need = (size_t)(max_in_bytes + 15) / 16 * 16;
-    if (ctx->kmc_stage_bytes >= need && ctx->kmc_pin[0] && ctx->kmc_pin[1] && ctx->kmc_dev[0] && ctx->kmc_dev[1]) {
-        s->stage_bytes = ctx->kmc_stage_bytes;
-        for (int b = 0; b < 2; ++b) {
-            s->pin[b] = ctx->kmc_pin[b];
-            s->dev[b] = ctx->kmc_dev[b];
-            ctx->kmc_pin[b] = ctx->kmc_dev[b] = nullptr;
-        }
-        ctx->kmc_stage_bytes = 0;
-    } else {
-        s->stage_bytes = need;
-        // one slot: a call is complete on return, so no transfer overlaps the kernels of the call before (the context's slots come as a pair and go back as one)
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&s->pin[0]), need, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->dev[0]), need + 16);
-        if (e != hipSuccess) {
-            bt_bam_scan_destroy(s.release());
-            return fail(std::string("bt_bam_scan_create: ") + hipGetErrorString(e));
-        }
+    const int rc = s->st.create("bt_bam_scan_create", ctx, max_in_bytes);
+    if (rc != BT_OK) {
+        s->st.release();
+        return rc;
     }
     *out = s.release();
     return BT_OK;
@@ -431,55 +387,20 @@ int bt_bam_scan_text(bt_bam_scan *s, const uint8_t *h_blocks, uint64_t n_bytes, 
     *d_text = nullptr;
     *text_len = 0;
     if (stats) *stats = bt_bam_stats{0, 0, 0};
-    if (n_bytes > s->max_in_bytes) return fail("bt_bam_scan_text: " + std::to_string(n_bytes) + " bytes handed in, the stream was created for " + std::to_string(s->max_in_bytes));
-    if (skip_first_bytes && s->calls) return fail("bt_bam_scan_text: skip_first_bytes belongs to the first call");
-    bt_ctx *ctx = s->ctx;
+    BgzfStream &st = s->st;
+    if (n_bytes > st.max_in_bytes) return fail("bt_bam_scan_text: " + std::to_string(n_bytes) + " bytes handed in, the stream was created for " + std::to_string(st.max_in_bytes));
+    if (skip_first_bytes && st.calls) return fail("bt_bam_scan_text: skip_first_bytes belongs to the first call");
+    bt_ctx *ctx = st.ctx;
     BT_HIP(hipSetDevice(ctx->device));
-    if (!s->calls) s->skip_left = skip_first_bytes;
-    // the blocks of the slab
-    uint64_t n_blocks = 0, taken = 0, total = 0;
-    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, nullptr, 0, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
-    if (taken != n_bytes) return fail("bt_bam_scan_text: the slab ends inside the BGZF block at offset " + std::to_string(s->file_offset + taken) + " (whole blocks are handed in)");
-    s->blocks.resize(n_blocks);
-    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, s->blocks.data(), n_blocks, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
-    const int b = 0;   // (one slot: nothing of this call overlaps the next)
-    ++s->calls;
-    if (n_blocks > s->cap_blocks) {
-        if (s->d_blocks) (void)hipFree(s->d_blocks);
-        if (s->d_status) (void)hipFree(s->d_status);
-        s->d_blocks = nullptr;
-        s->d_status = nullptr;
-        s->cap_blocks = 0;
-        const uint64_t cap = n_blocks + n_blocks / 4 + 64;
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_blocks), cap * sizeof(bt_bgzf_block)));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_status), (cap + 1) * 4));
-        s->cap_blocks = cap;
-    }
-    const uint64_t raw = s->tail + total;
-    if (raw >= 0xFFFFFFFFull)
-        return fail("bt_bam_scan_text: the slab at offset " + std::to_string(s->file_offset) + " inflates to " + std::to_string(total) + " bytes (" + std::to_string(s->tail) +
-                    " carried over): 4 GiB - 2 of records is the most a call takes; hand in smaller slabs");
-    if (grow(reinterpret_cast<void **>(&s->d_raw), &s->cap_raw, raw) != BT_OK) return BT_ERR;
-    if (grow(reinterpret_cast<void **>(&s->d_text), &s->cap_text, raw) != BT_OK) return BT_ERR;
-    // through the pinned slot to the device, the tail in front, the blocks' data behind it
-    if (n_bytes) {
-        std::memcpy(s->pin[b], h_blocks, n_bytes);
-        BT_HIP(hipMemcpyAsync(s->dev[b], s->pin[b], n_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (n_blocks) BT_HIP(hipMemcpyAsync(s->d_blocks, s->blocks.data(), n_blocks * sizeof(bt_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
-    if (s->tail) BT_HIP(hipMemcpyAsync(s->d_raw, s->d_tail, s->tail, hipMemcpyDeviceToDevice, ctx->stream));
-    if (n_blocks) {
-        if (bgzf_inflate_launch(ctx, s->dev[b], n_bytes, s->d_blocks, n_blocks, s->d_raw + s->tail, total, s->d_status) != BT_OK) return BT_ERR;
-        if (bgzf_inflate_result(ctx, s->d_blocks, n_blocks, s->d_status, s->file_offset) != BT_OK) return BT_ERR;
-    }
-    BT_HIP(hipStreamSynchronize(ctx->stream));   // (the blocks' table and the pinned slot have been read)
-    s->file_offset += n_bytes;
+    if (!st.calls) s->skip_left = skip_first_bytes;
+    uint64_t raw = 0;
+    if (st.inflate_slab(who, h_blocks, n_bytes, &raw) != BT_OK) return BT_ERR;
     // the header's bytes are stepped over; they never meet a tail, since no record precedes them
     const uint64_t skip = std::min(s->skip_left, raw);
     s->skip_left -= skip;
     uint64_t consumed = 0;
-    const uint8_t *d_records = s->d_raw + skip;
-    if (bam_text_run(who, ctx, s->work, d_records, raw - skip, s->skip_flags, s->d_text, s->cap_text, s->stream_offset + skip, text_len, &consumed, stats) != BT_OK) return BT_ERR;
+    const uint8_t *d_records = st.d_raw + skip;
+    if (bam_text_run(who, ctx, s->work, d_records, raw - skip, s->skip_flags, st.d_text, st.cap_text, s->stream_offset + skip, text_len, &consumed, stats) != BT_OK) return BT_ERR;
     // what is left is the start of a record that is not whole: it waits in d_tail for the next call
     const uint64_t rest = raw - skip - consumed;
     s->stream_offset += skip + consumed;
@@ -487,51 +408,27 @@ int bt_bam_scan_text(bt_bam_scan *s, const uint8_t *h_blocks, uint64_t n_bytes, 
         uint8_t head[4];
         BT_HIP(hipMemcpyAsync(head, d_records + consumed, 4, hipMemcpyDeviceToHost, ctx->stream));
         BT_HIP(hipStreamSynchronize(ctx->stream));
-        const uint64_t record = 4ull + rd32(head), limit = 8 * s->max_in_bytes;
+        const uint64_t record = 4ull + rd32(head), limit = 8 * st.max_in_bytes;
         if (record > limit)
             return fail("bt_bam_scan_text: the BAM record at offset " + std::to_string(s->stream_offset) + " takes " + std::to_string(record) + " bytes, more than a slab may hold (" +
                         std::to_string(limit) + ", 8 x max_in_bytes)");
     }
-    if (rest) {
-        if (grow(reinterpret_cast<void **>(&s->d_tail), &s->cap_tail, rest) != BT_OK) return BT_ERR;
-        BT_HIP(hipMemcpyAsync(s->d_tail, d_records + consumed, rest, hipMemcpyDeviceToDevice, ctx->stream));
-        BT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    s->tail = rest;
-    *d_text = s->d_text;
+    if (st.keep_tail(d_records + consumed, rest) != BT_OK) return BT_ERR;
+    *d_text = st.d_text;
     return BT_OK;
 }
 
 int bt_bam_scan_finish(bt_bam_scan *s) {
     if (!s) return fail("bt_bam_scan_finish: null argument");
     if (s->skip_left) return fail("bt_bam_scan_finish: the file ends inside the BAM header (" + std::to_string(s->skip_left) + " bytes missing): truncated");
-    if (s->tail)
-        return fail("bt_bam_scan_finish: the file ends inside the BAM record at offset " + std::to_string(s->stream_offset) + " (" + std::to_string(s->tail) + " bytes of it are there): truncated");
+    if (s->st.tail)
+        return fail("bt_bam_scan_finish: the file ends inside the BAM record at offset " + std::to_string(s->stream_offset) + " (" + std::to_string(s->st.tail) + " bytes of it are there): truncated");
     return BT_OK;
 }
 
 void bt_bam_scan_destroy(bt_bam_scan *s) {
     if (!s) return;
-    bt_ctx *ctx = s->ctx;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    // the slots go (back) to the context when they are whole and no smaller than what it holds
-    const bool whole = s->pin[0] && s->pin[1] && s->dev[0] && s->dev[1];
-    if (whole && s->stage_bytes >= ctx->kmc_stage_bytes && !ctx_caches_off()) {
-        for (int b = 0; b < 2; ++b) {
-            if (ctx->kmc_pin[b]) (void)hipHostFree(ctx->kmc_pin[b]);
-            if (ctx->kmc_dev[b]) (void)hipFree(ctx->kmc_dev[b]);
-            ctx->kmc_pin[b] = s->pin[b];
-            ctx->kmc_dev[b] = s->dev[b];
-        }
-        ctx->kmc_stage_bytes = s->stage_bytes;
-    } else
-        for (int b = 0; b < 2; ++b) {
-            if (s->pin[b]) (void)hipHostFree(s->pin[b]);
-            if (s->dev[b]) (void)hipFree(s->dev[b]);
-        }
-    for (void *p : {(void *)s->d_blocks, (void *)s->d_status, (void *)s->d_raw, (void *)s->d_tail, (void *)s->d_text})
-        if (p) (void)hipFree(p);
+    s->st.release();
     delete s;
 }
 

@@ -6,8 +6,10 @@
 //   CRC table.  Blocks are independent; no workgroup waits on another.  A block's status goes to status[block]; the smallest failing block index to
 //   status[n_blocks] (one atomic minimum per failing block), which is all the host reads back when every block is sound.
 #include <algorithm>
+#include <cstring>
 #include <memory>
 
+#include "bt_bgzf_stream.hpp"
 #include "bt_inflate.hpp"
 #include "bt_internal.hpp"
 
@@ -64,6 +66,121 @@ int bgzf_inflate_result(bt_ctx *ctx, const bt_bgzf_block *d_blocks, uint64_t n_b
     return fail(block_error(file_offset + e.in_offset, st));
 }
 
+
+// ---- the stream objects' common part (bt_bgzf_stream.hpp) ---------------------------------------------------------------------------------------------------
+int grow(void **p, uint64_t *cap, uint64_t need) {
+    if (need <= *cap) return BT_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const uint64_t bytes = need + need / 4 + 256;
+    BT_HIP(hipMalloc(p, bytes));
+    *cap = bytes;
+    return BT_OK;
+}
+
+int BgzfStream::create(const char *who, bt_ctx *c, uint64_t max_in) {
+    if (max_in < 65536 || max_in > (1ull << 30)) return fail(std::string(who) + ": max_in_bytes must lie in 64 KiB .. 1 GiB (a slab holds at least one whole BGZF block)");
+    BT_HIP(hipSetDevice(c->device));
+    ctx = c;
+    max_in_bytes = max_in;
+    const size_t need = (size_t)(max_in + 15) / 16 * 16;
+    if (c->kmc_stage_bytes >= need && c->kmc_pin[0] && c->kmc_pin[1] && c->kmc_dev[0] && c->kmc_dev[1]) {
+        stage_bytes = c->kmc_stage_bytes;
+        for (int b = 0; b < 2; ++b) {
+            pin[b] = c->kmc_pin[b];
+            dev[b] = c->kmc_dev[b];
+            c->kmc_pin[b] = c->kmc_dev[b] = nullptr;
+        }
+        c->kmc_stage_bytes = 0;
+    } else {
+        stage_bytes = need;
+        // one slot: a call is complete on return, so no transfer overlaps the kernels of the call before (the context's slots come as a pair and go back as one)
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&pin[0]), need, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dev[0]), need + 16);
+        if (e != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(e));
+    }
+    return BT_OK;
+}
+
+int BgzfStream::inflate_slab(const char *who, const uint8_t *h_blocks, uint64_t n_bytes, uint64_t *raw_out) {
+    const std::string name(who);
+    // the blocks of the slab
+    uint64_t n_blocks = 0, taken = 0, total = 0;
+    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, nullptr, 0, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
+    if (taken != n_bytes) return fail(name + ": the slab ends inside the BGZF block at offset " + std::to_string(file_offset + taken) + " (whole blocks are handed in)");
+    blocks.resize(n_blocks);
+    if (bt_bgzf_scan_blocks(h_blocks, n_bytes, blocks.data(), n_blocks, &n_blocks, &taken, &total) != BT_OK) return BT_ERR;
+    const int b = 0;   // (one slot: nothing of this call overlaps the next)
+    ++calls;
+    if (n_blocks > cap_blocks) {
+        if (d_blocks) (void)hipFree(d_blocks);
+        if (d_status) (void)hipFree(d_status);
+        d_blocks = nullptr;
+        d_status = nullptr;
+        cap_blocks = 0;
+        const uint64_t cap = n_blocks + n_blocks / 4 + 64;
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_blocks), cap * sizeof(bt_bgzf_block)));
+        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_status), (cap + 1) * 4));
+        cap_blocks = cap;
+    }
+    const uint64_t raw = tail + total;
+    if (raw >= 0xFFFFFFFFull)
+        return fail(name + ": the slab at offset " + std::to_string(file_offset) + " inflates to " + std::to_string(total) + " bytes (" + std::to_string(tail) +
+                    " carried over): 4 GiB - 2 of records is the most a call takes; hand in smaller slabs");
+    if (grow(reinterpret_cast<void **>(&d_raw), &cap_raw, raw) != BT_OK) return BT_ERR;
+    if (grow(reinterpret_cast<void **>(&d_text), &cap_text, raw) != BT_OK) return BT_ERR;
+    // through the pinned slot to the device, the tail in front, the blocks' data behind it
+    if (n_bytes) {
+        std::memcpy(pin[b], h_blocks, n_bytes);
+        BT_HIP(hipMemcpyAsync(dev[b], pin[b], n_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_blocks) BT_HIP(hipMemcpyAsync(d_blocks, blocks.data(), n_blocks * sizeof(bt_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
+    if (tail) BT_HIP(hipMemcpyAsync(d_raw, d_tail, tail, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_blocks) {
+        if (bgzf_inflate_launch(ctx, dev[b], n_bytes, d_blocks, n_blocks, d_raw + tail, total, d_status) != BT_OK) return BT_ERR;
+        if (bgzf_inflate_result(ctx, d_blocks, n_blocks, d_status, file_offset) != BT_OK) return BT_ERR;
+    }
+    BT_HIP(hipStreamSynchronize(ctx->stream));   // (the blocks' table and the pinned slot have been read)
+    file_offset += n_bytes;
+    *raw_out = raw;
+    return BT_OK;
+}
+
+int BgzfStream::keep_tail(const uint8_t *from, uint64_t rest) {
+    if (rest) {
+        if (grow(reinterpret_cast<void **>(&d_tail), &cap_tail, rest) != BT_OK) return BT_ERR;
+        BT_HIP(hipMemcpyAsync(d_tail, from, rest, hipMemcpyDeviceToDevice, ctx->stream));
+        BT_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    tail = rest;
+    return BT_OK;
+}
+
+void BgzfStream::release() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    const bool whole = pin[0] && pin[1] && dev[0] && dev[1];
+    if (whole && stage_bytes >= ctx->kmc_stage_bytes && !ctx_caches_off()) {
+        for (int b = 0; b < 2; ++b) {
+            if (ctx->kmc_pin[b]) (void)hipHostFree(ctx->kmc_pin[b]);
+            if (ctx->kmc_dev[b]) (void)hipFree(ctx->kmc_dev[b]);
+            ctx->kmc_pin[b] = pin[b];
+            ctx->kmc_dev[b] = dev[b];
+        }
+        ctx->kmc_stage_bytes = stage_bytes;
+    } else
+        for (int b = 0; b < 2; ++b) {
+            if (pin[b]) (void)hipHostFree(pin[b]);
+            if (dev[b]) (void)hipFree(dev[b]);
+        }
+    for (void *p : {(void *)d_blocks, (void *)d_status, (void *)d_raw, (void *)d_tail, (void *)d_text})
+        if (p) (void)hipFree(p);
+    pin[0] = pin[1] = dev[0] = dev[1] = nullptr;
+    d_blocks = nullptr, d_status = nullptr, d_raw = d_tail = nullptr, d_text = nullptr;
+    ctx = nullptr;
+}
 }  // namespace bt
 
 extern "C" {

@@ -1,6 +1,7 @@
 // Every read file of <prefix>.reads to the consumers of the reads scan (include/btgpu.h: bt_reads_*), whatever its format.  A file is told by its content, not by
 // its name: a BAM (BamFile::isBam) goes through the stream object of libbtgpu — compressed blocks in, reads text in device memory out (bt_bam_scan_text) — and
-// reaches `device_text`; every other file is read as FASTA / FASTQ on the host (forEachReadsSlab) and reaches `host_slab`, as before BAM was taken.
+// reaches `device_text`; so does a FASTQ compressed as BGZF (isBgzfFastq; bt_fastq_scan_text), unless BT_FASTQ_BGZF_ON_HOST=1 sends it the old way; every other
+// file is read as FASTA / FASTQ on the host (forEachReadsSlab) and reaches `host_slab`, as before BAM was taken.
 #pragma once
 #include <functional>
 #include <iostream>
@@ -20,26 +21,40 @@ struct ReadsSinks {
     std::function<void(const char *, uint64_t)> device_text;         // reads text in device memory, valid until the call returns
 };
 
-// ReadsTotals of a BAM file: bases and reads of the kept records (flag & skip_flags == 0), slabs = calls of bt_bam_scan_text
-// *bam_files (may be NULL): how many of the list's files were BAM files
+// for the BT_STAGE_TIMES rows of the reads route: which of the files went through a stream object of the device
+inline std::string deviceRouteNote(size_t bam_files, size_t bgzf_fastq_files) {
+    std::string note;
+    if (bam_files) note += " (" + std::to_string(bam_files) + " BAM file(s) on the device)";
+    if (bgzf_fastq_files) note += " (" + std::to_string(bgzf_fastq_files) + " BGZF FASTQ file(s) on the device)";
+    return note;
+}
+
+// ReadsTotals of a BAM file: bases and reads of the kept records (flag & skip_flags == 0), slabs = calls of bt_bam_scan_text; of a BGZF FASTQ file: bases and
+// reads of the records with at least one base, slabs = calls of bt_fastq_scan_text
+// *bam_files, *bgzf_fastq_files (may be NULL): how many of the list's files were BAM files, and BGZF-compressed FASTQ files read on the device
 inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const ReadsSinks &sinks,
-                                      size_t *bam_files = nullptr) {
-    std::vector<std::string> bams, texts;
-    for (const std::string &f : readReadsList(prefix)) (BamFile::isBam(f) ? bams : texts).push_back(f);
+                                      size_t *bam_files = nullptr, size_t *bgzf_fastq_files = nullptr) {
+    std::vector<std::string> bams, fastqs, texts;
+    const bool fastq_on_host = fastqBgzfOnHost();
+    for (const std::string &f : readReadsList(prefix)) (BamFile::isBam(f) ? bams : !fastq_on_host && isBgzfFastq(f) ? fastqs : texts).push_back(f);
     ReadsTotals totals;
     if (bam_files) *bam_files = bams.size();
+    if (bgzf_fastq_files) *bgzf_fastq_files = fastqs.size();
+    const size_t bgzf_slab = std::max<size_t>(slab_bytes / 2, 65536);   // compressed bytes: about a quarter of the text they hold
+    auto check = [](int rc, const std::string &file) {
+        if (rc != BT_OK) throw std::runtime_error("read file " + file + ": " + bt_last_error());
+    };
+    auto warnNoEof = [](const BgzfFile &file, const std::string &f) {
+        static std::set<std::string> warned;   // once per file and process: makeBloom -r reads a file in two passes
+        if (!file.hasEofBlock() && warned.insert(f).second) std::cerr << "WARNING: read file " << f << " has no BGZF end-of-file block: it may be truncated" << std::endl;
+    };
     if (!bams.empty()) {
         const uint32_t skip_flags = bamSkipFlags();
-        const size_t bam_slab = std::max<size_t>(slab_bytes / 2, 65536);   // compressed bytes: about a quarter of the text they hold
         bt_bam_scan *scan = nullptr;
-        auto check = [](int rc, const std::string &file) {
-            if (rc != BT_OK) throw std::runtime_error("read file " + file + ": " + bt_last_error());
-        };
         for (const std::string &f : bams) {
-            BamFile file(f, bam_slab);
-            static std::set<std::string> warned;   // once per file and process: makeBloom -r reads a file in two passes
-            if (!file.hasEofBlock() && warned.insert(f).second) std::cerr << "WARNING: read file " << f << " has no BGZF end-of-file block: it may be truncated" << std::endl;
-            check(bt_bam_scan_create(ctx, bam_slab, skip_flags, &scan), f);
+            BamFile file(f, bgzf_slab);
+            warnNoEof(file, f);
+            check(bt_bam_scan_create(ctx, bgzf_slab, skip_flags, &scan), f);
             try {
                 std::vector<uint8_t> slab;
                 for (bool first = true; file.next(slab); first = false) {
@@ -60,6 +75,35 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
             bt_bam_scan_destroy(scan);
             totals.files++;
         }
+    }
+    for (const std::string &f : fastqs) {
+        BgzfFastqFile file(f, bgzf_slab);
+        warnNoEof(file, f);
+        bt_fastq_scan *scan = nullptr;
+        check(bt_fastq_scan_create(ctx, bgzf_slab, &scan), f);
+        try {
+            std::vector<uint8_t> slab;
+            const char *d_text = nullptr;
+            uint64_t len = 0;
+            bt_fastq_stats stats;
+            auto deliver = [&]() {
+                if (len) sinks.device_text(d_text, len);
+                totals.bases += stats.bases;
+                totals.reads += stats.reads;
+            };
+            while (file.next(slab)) {
+                check(bt_fastq_scan_text(scan, slab.data(), slab.size(), &d_text, &len, &stats), f);
+                deliver();
+                totals.slabs++;
+            }
+            check(bt_fastq_scan_finish(scan, &d_text, &len, &stats), f);   // the file's last record, when its last line has no newline
+            deliver();
+        } catch (...) {
+            bt_fastq_scan_destroy(scan);
+            throw;
+        }
+        bt_fastq_scan_destroy(scan);
+        totals.files++;
     }
     if (!texts.empty()) {
         const ReadsTotals t = forEachReadsSlab(texts, kmer_size, threads, slab_bytes, sinks.host_slab);

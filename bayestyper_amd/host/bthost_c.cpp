@@ -802,6 +802,32 @@ long long bth_bam_skip_flags(char *err, unsigned err_len) {
         return stage_error(e, err, err_len);
     }
 }
+// isBgzfFastq: 1 a FASTQ compressed as BGZF, 0 anything else, -1 an error (an unreadable file; text in *err).  No GPU.
+int bth_fastq_is_bgzf(const char *path, char *err, unsigned err_len) {
+    try {
+        return isBgzfFastq(path) ? 1 : 0;
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// BgzfFastqFile: the slabs of one BGZF FASTQ file laid end to end -> buf (when it fits); stats[0..3] = file offset of the first slab, has an EOF block, slabs,
+// file bytes; returns the bytes needed, or -1 (error text in *err).  No GPU.
+long long bth_bgzf_fastq_file_slabs(const char *path, unsigned long long slab_bytes, char *buf, unsigned long long cap, unsigned long long *stats, char *err, unsigned err_len) {
+    try {
+        BgzfFastqFile file(path, (size_t)slab_bytes);
+        std::string all;
+        std::vector<uint8_t> slab;
+        uint64_t slabs = 0, first_at = 0;
+        while (file.next(slab)) {
+            if (!slabs++) first_at = file.slabOffset();
+            all.append(reinterpret_cast<const char *>(slab.data()), slab.size());
+        }
+        if (stats) stats[0] = first_at, stats[1] = file.hasEofBlock() ? 1 : 0, stats[2] = slabs, stats[3] = file.fileBytes();
+        return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
 // header fields of a KMC database: out[0..5] = k, mode, counter_size, lut_prefix_length, total_kmers, record_size; 0 on success
 int bth_kmc_info(const char *kmc_prefix, unsigned long long *out) {
     try {

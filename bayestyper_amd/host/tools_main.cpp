@@ -4,10 +4,11 @@
 // --false-positive-rate 0.001), same progress lines, byte-identical output files (insertion is an order-independent OR).  The records are
 // streamed from the memory-mapped .kmc_suf through the GPU in chunks (bt_kmc_scan_make_bloom); there is no CPU path.
 // -r/--reads-prefix <prefix> is the alternative to -k for a sample without a KMC database: the read files listed in <prefix>.reads (FASTA / FASTQ, plain or
-// gzip, through bt_reads_make_bloom_host; BAM through bt_bam_scan_text + bt_reads_make_bloom) are streamed; the filter is sized by --num-kmers, or by a first pass that estimates the number of distinct k-mers
+// gzip, through bt_reads_make_bloom_host; BAM through bt_bam_scan_text, FASTQ compressed as BGZF through bt_fastq_scan_text, + bt_reads_make_bloom) are streamed; the filter is sized by --num-kmers, or by a first pass that estimates the number of distinct k-mers
 // (bt_reads_sketch_host).  With the N of the sample's KMC database the bytes written are those of -k.
 // The VCF utilities of bayesTyperTools (convertAllele, combine, filter, annotate, addAttributes) are not part of this build.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <iostream>
@@ -39,7 +40,7 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
         if (num_kmers == 0) {
             std::cout << stamp() << "Estimating the number of distinct kmers in the reads of " << prefix << ".reads ..." << std::endl;
             std::vector<uint8_t> registers(65536, 0), device_registers(65536, 0);
-            void *d_registers = nullptr;   // the sketch of the BAM files' reads, whose text stays on the device; a register-wise maximum joins the two
+            void *d_registers = nullptr;   // the sketch of the reads whose text stays on the device (BAM, BGZF FASTQ); a register-wise maximum joins the two
             check(bt_malloc(ctx, registers.size(), &d_registers), "bt_malloc");
             try {
                 check(bt_memset(ctx, d_registers, 0, registers.size()), "bt_memset");
@@ -66,8 +67,13 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
         ReadsSinks sinks;
         sinks.host_slab = [&](const std::string &slab) { check(bt_reads_make_bloom_host(ctx, bloom, slab.data(), slab.size(), kmer_size, 0), "bt_reads_make_bloom_host"); };
         sinks.device_text = [&](const char *d_text, uint64_t len) { check(bt_reads_make_bloom(ctx, bloom, d_text, len, kmer_size), "bt_reads_make_bloom"); };
-        const ReadsTotals totals = forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks);
+        size_t bam_files = 0, bgzf_fastq_files = 0;
+        const auto t_scan = std::chrono::steady_clock::now();
+        const ReadsTotals totals = forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks, &bam_files, &bgzf_fastq_files);
         check(bt_sync(ctx), "bt_sync");
+        if (getenv("BT_STAGE_TIMES"))
+            std::cerr << "  make bloom (reads route): " << totals.bases << " bases in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan).count() << " s"
+                      << deviceRouteNote(bam_files, bgzf_fastq_files) << std::endl;
         std::cout << stamp() << "Parsed " << totals.bases << " bases of " << totals.reads << " reads in " << totals.files << " file(s)" << std::endl;
         std::cout << "\n" << stamp() << "Saving bloom filter to " << prefix << " ..." << std::endl;
         check(bt_bloom_save(bloom, prefix.c_str()), "bt_bloom_save");
@@ -85,7 +91,7 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
 int runMakeBloom(int argc, char *const argv[], unsigned kmer_size) {
     const std::vector<OptionSpec> specs = {
         {"kmc-table-prefix", 'k', "Required (one of)", false, false, "", "KMC kmer table prefix. Output is written as <kmc-table-prefix>.bloomMeta and <kmc-table-prefix>.bloomData.", 's'},
-        {"reads-prefix", 'r', "Required (one of)", false, false, "", "sample prefix without a KMC table: the read files (FASTA/FASTQ, plain or gzip, or BAM) listed in <reads-prefix>.reads are used. Output is written as <reads-prefix>.bloomMeta and <reads-prefix>.bloomData.", 's'},
+        {"reads-prefix", 'r', "Required (one of)", false, false, "", "sample prefix without a KMC table: the read files (FASTA/FASTQ, plain, gzip or BGZF, or BAM) listed in <reads-prefix>.reads are used. Output is written as <reads-prefix>.bloomMeta and <reads-prefix>.bloomData.", 's'},
         {"num-threads", 'p', "General", false, false, "1", "number of threads used (+= 1 I/O thread).", 'u'},
         {"false-positive-rate", 0, "Parameters", false, false, "0.001", "bloom filter false positive rate.", 'f'},
         {"num-kmers", 0, "Parameters", false, false, "0", "number of distinct kmers the filter is made for (--reads-prefix only; 0 = estimate it in a first pass over the reads).", 'u'},

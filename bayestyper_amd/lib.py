@@ -1374,6 +1374,104 @@ class BamScan:
             self.h = None
 
 
+class FastqStats(C.Structure):   # include/btgpu.h: bt_fastq_stats
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("lines", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+bt_fastq_reads_text = _sig("bt_fastq_reads_text", [vp, vp, C.c_uint64, C.c_int, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(FastqStats)])
+bt_diag_fastq_reads_text = _sig("bt_diag_fastq_reads_text", [vp, C.c_uint64, C.c_int, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(FastqStats)])
+bt_fastq_count_tile = _sig("bt_fastq_count_tile", [], C.c_uint32)
+bt_fastq_scan_create = _sig("bt_fastq_scan_create", [vp, C.c_uint64, C.POINTER(vp)])
+bt_fastq_scan_text = _sig("bt_fastq_scan_text", [vp, vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(FastqStats)])
+bt_fastq_scan_finish = _sig("bt_fastq_scan_finish", [vp, C.POINTER(vp), u64p, C.POINTER(FastqStats)])
+bt_fastq_scan_destroy = _sig("bt_fastq_scan_destroy", [vp], None)
+FASTQ_COUNT_TILE = int(bt_fastq_count_tile())   # bytes per workgroup of the kernels that find the lines, counted from the data's first byte
+
+
+def diag_fastq_reads_text(fastq, final=True, first_line=1, capacity=None, null=None):
+    """bt_diag_fastq_reads_text (no GPU): FASTQ text from a record boundary on -> (reads text as bytes, offset of the first record that is not whole,
+    stats).  null: "text" / "text_bytes" / "consumed" passes that argument as NULL"""
+    a = _bytes_array(fastq)
+    cap = a.size if capacity is None else capacity
+    out, n, used, st = np.full(cap + 16, 0xA5, np.uint8), C.c_uint64(), C.c_uint64(), FastqStats()
+    try:
+        check(bt_diag_fastq_reads_text(_np_ptr(a) if a.size else None, a.size, int(bool(final)), first_line, None if null == "text" else _np_ptr(out), cap,
+                                       None if null == "text_bytes" else C.byref(n), None if null == "consumed" else C.byref(used), C.byref(st)))
+    finally:
+        assert (out[cap:] == 0xA5).all()
+    assert (out[n.value:cap] == 0xA5).all()
+    return out[:n.value].tobytes(), used.value, st.as_dict()
+
+
+def fastq_reads_text(ctx, fastq, final=True, first_line=1, capacity=None, misalign=0):
+    """bt_fastq_reads_text over a host buffer (uploaded `misalign` bytes into its allocation) -> (reads text as bytes, offset of the first record that is
+    not whole, stats).  The bytes behind the text and behind the capacity are checked to be untouched."""
+    a = _bytes_array(fastq)
+    cap = a.size if capacity is None else capacity
+    d_in, d_out = DeviceBuffer(ctx, a.size + misalign), DeviceBuffer(ctx, cap + 16)
+    try:
+        if a.size:
+            check(bt_memcpy_h2d(ctx.h, d_in.ptr + misalign, _np_ptr(a), a.size))
+        check(bt_memset(ctx.h, d_out.ptr, 0xA5, d_out.nbytes))
+        n, used, st = C.c_uint64(), C.c_uint64(), FastqStats()
+        try:
+            check(bt_fastq_reads_text(ctx.h, d_in.ptr + misalign if a.size else None, a.size, int(bool(final)), first_line, d_out.ptr, cap, C.byref(n), C.byref(used), C.byref(st)))
+        finally:
+            ctx.sync()
+            out = d_out.download(np.uint8, cap + 16)
+            assert (out[cap:] == 0xA5).all()
+        assert (out[n.value:cap] == 0xA5).all()
+        return out[:n.value].tobytes(), used.value, st.as_dict()
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+class FastqScan:
+    """bt_fastq_scan: slabs of whole BGZF blocks of a BGZF-compressed FASTQ file -> reads text in device memory"""
+
+    def __init__(self, ctx, max_in_bytes):
+        self.ctx = ctx
+        h = vp()
+        check(bt_fastq_scan_create(ctx.h, max_in_bytes, C.byref(h)))
+        self.h = h.value
+
+    def text(self, blocks):
+        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
+        a = _bytes_array(blocks)
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(bt_fastq_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def finish(self):
+        """the carried tail as the file's end -> (device pointer of its text, its length, stats)"""
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(bt_fastq_scan_finish(self.h, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def _download(self, d, n, st):
+        out = np.empty(n, np.uint8)
+        if n:
+            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
+        return out.tobytes(), st
+
+    def text_bytes(self, blocks):
+        """text(), downloaded -> (bytes, stats)"""
+        return self._download(*self.text(blocks))
+
+    def finish_bytes(self):
+        """finish(), downloaded -> (bytes, stats)"""
+        return self._download(*self.finish())
+
+    def close(self):
+        if self.h:
+            bt_fastq_scan_destroy(self.h)
+            self.h = None
+
+
 def parse_genotype_text(text, index):
     """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
     dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer

@@ -984,6 +984,50 @@ int bt_bam_scan_text(bt_bam_scan *scan, const uint8_t *h_blocks, uint64_t n_byte
 int bt_bam_scan_finish(bt_bam_scan *scan);
 void bt_bam_scan_destroy(bt_bam_scan *scan);
 
+/* ------------------------------------------------------------------------------------------
+ * BGZF-compressed FASTQ samples on the device: BGZF read (as above) and FASTQ records -> reads text.  The FASTQ files a sequencer's converter or `bgzip`
+ * writes are concatenated gzip members with the BC subfield, which bt_bgzf_inflate takes as they are.  bayestyper_amd/csrc/bt_fastq.hpp holds the grammar
+ * (that of the host's ReadsFile), one text for the kernels and the host:
+ *   lines end at '\n', one trailing '\r' is stripped; a record is '@' header, bases, '+' line, as many quality values as bases; a blank line (empty, or a
+ *   lone '\r') is skipped only where a record's first line is expected, anywhere else it is that line of the record; the file's last line needs no newline.
+ * A violation is an error with the 1-based line number in the file (blank lines count) and ReadsFile's words:
+ *   "line N: a FASTQ record must start with '@' (a missing line?)", "line N: the third line of a FASTQ record must start with '+' (a missing line?)",
+ *   "FASTQ record ending at line N: X bases but Y quality values (a missing line?)", "truncated FASTQ record at the end of the file (n of 4 lines)";
+ * of several the one at the smallest line.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bt_fastq_stats {
+    uint64_t reads, bases, lines;   /* records with at least one base, their sequence bytes, lines consumed (skipped blank lines included) */
+} bt_fastq_stats;
+/* d_fastq [len] (FASTQ text from a record boundary on; len < 4 GiB - 1) -> d_text: for every WHOLE record with at least one base, in record order, its
+ * sequence bytes verbatim and '\n' (no case folding, no N mapping: the consumers' nt_code does that); a record without bases writes nothing.
+ * final == 0: a record is whole when the newline of its fourth line is there; *consumed = the offset of the first record that is not whole (blank lines
+ * in front of it are consumed); that record is judged by the complete lines that are there of it.  final == 1: the data is the file's end: a last line
+ * without a newline is a line, a record of 1 to 3 lines is the "truncated" error, *consumed == len on success.  first_line: the file's line number of
+ * d_fastq[0].  capacity >= len always suffices, a smaller one that does not is an error; nothing is written at or past capacity, or past *text_bytes.
+ * stats may be NULL.  Complete on return. */
+int bt_fastq_reads_text(bt_ctx *ctx, const char *d_fastq, uint64_t len, int final, uint64_t first_line, char *d_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed,
+                        bt_fastq_stats *stats);
+/* Host-side run of bt_fastq_reads_text (the same line code, no GPU): the same text, numbers and message. */
+int bt_diag_fastq_reads_text(const char *h_fastq, uint64_t len, int final, uint64_t first_line, char *h_text, uint64_t capacity, uint64_t *text_bytes, uint64_t *consumed,
+                             bt_fastq_stats *stats);
+/* Bytes per workgroup of the kernels that find the lines (tiles are counted from d_fastq[0]): where a test puts its line ends. */
+uint32_t bt_fastq_count_tile(void);
+
+/* The stream object, the twin of bt_bam_scan: a BGZF FASTQ file's compressed blocks in slabs -> reads text on the device.  max_in_bytes (64 KiB .. 1 GiB):
+ * the largest slab.  The slabs go through the context's pinned staging slots (taken when they are large enough, handed back by _destroy). */
+typedef struct bt_fastq_scan bt_fastq_scan;
+int bt_fastq_scan_create(bt_ctx *ctx, uint64_t max_in_bytes, bt_fastq_scan **out);
+/* h_blocks [n_bytes]: WHOLE BGZF blocks in host memory (a slab that ends inside a block is an error), in file order from call to call, from the file's
+ * first block on.  They are inflated behind the tail the previous call left (the record that was not whole) and turned into text: *d_text [*text_len] is
+ * device memory, valid until the next call on this object, and fit for bt_reads_count / bt_reads_make_bloom / bt_reads_sketch as it stands.  Blocks with
+ * ISIZE 0 are legal anywhere.  A tail of more than 8 x max_in_bytes (a record longer than a slab may hold) is refused.  A slab whose data, with the
+ * carried tail, would reach 4 GiB is refused with a message that asks for smaller slabs.  stats (may be NULL): this call's.  After an error the object
+ * can only be destroyed.  Complete on return. */
+int bt_fastq_scan_text(bt_fastq_scan *scan, const uint8_t *h_blocks, uint64_t n_bytes, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats);
+/* The carried tail judged as the file's end (final == 1) -> its text, which may be empty (*d_text is then NULL). */
+int bt_fastq_scan_finish(bt_fastq_scan *scan, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats);
+void bt_fastq_scan_destroy(bt_fastq_scan *scan);
+
 #ifdef __cplusplus
 }
 #endif

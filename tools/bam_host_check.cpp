@@ -2,7 +2,7 @@
 // (bayestyper_amd/csrc/bt_bam.hpp) run by one thread, and the BAM file reader (bayestyper_amd/host/BamFile.cpp), for a sanitizer build.  No GPU, no library.
 //
 //   hipcc --offload-host-only -x hip -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       tools/bam_host_check.cpp -x c++ bayestyper_amd/host/BamFile.cpp -lz -o bam_host_check
+//       tools/bam_host_check.cpp -x c++ bayestyper_amd/host/BamFile.cpp bayestyper_amd/host/BgzfFile.cpp -lz -o bam_host_check
 //   ./bam_host_check <slab bytes> <file>...
 // Per file: a BAM goes through BamFile's slabs, each inflated block by block behind the carried tail and turned into text, as bt_bam_scan_text does;
 // any other file is taken as a run of BGZF blocks (sound or damaged) and inflated.  Errors are printed and are the expected end of a damaged file; the
