@@ -20,6 +20,7 @@
 
 #include "bt_bgzf_stream.hpp"
 #include "bt_fastq.hpp"
+#include "bt_fastq_stream.hpp"
 #include "bt_internal.hpp"
 
 using namespace bt;
@@ -364,12 +365,57 @@ int fastq_text_host(const char *who, const uint8_t *data, uint64_t len, int fina
 
 }  // namespace
 
-// Slabs of whole BGZF blocks in, reads text out.  The decompressed bytes of a call land behind the tail the call before left (the record that was not whole).
-struct bt_fastq_scan {
-    BgzfStream st;
+// The raw-to-text-and-tail half of a FASTQ stream object (bt_fastq_stream.hpp), whatever inflated the data: bt_fastq_scan (BGZF) and bt_fastq_gz_scan
+// (one long gzip member, bt_gunzip.hip).
+struct bt::FastqText {
     uint64_t line = 1;            // the file's line number of d_raw[0]
     uint64_t stream_offset = 0;   // decompressed offset of d_raw[0]
     FastqWork work;
+};
+
+namespace bt {
+
+FastqText *fastq_text_create() { return new FastqText; }
+void fastq_text_destroy(FastqText *ft) { delete ft; }
+
+int fastq_text_slab(const char *who, BgzfStream &st, FastqText &ft, uint64_t raw, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats) {
+    uint64_t consumed = 0;
+    bt_fastq_stats now{0, 0, 0};
+    if (fastq_text_run(who, st.ctx, ft.work, st.d_raw, raw, 0, ft.line, st.d_text, st.cap_text, text_len, &consumed, &now) != BT_OK) return BT_ERR;
+    if (stats) *stats = now;
+    // what is left is the start of a record that is not whole: it waits in d_tail for the next call
+    const uint64_t rest = raw - consumed, limit = 8 * st.max_in_bytes;
+    ft.line += now.lines;
+    ft.stream_offset += consumed;
+    if (rest > limit)
+        return fail(std::string(who) + ": the FASTQ record at line " + std::to_string(ft.line) + " (offset " + std::to_string(ft.stream_offset) + ") takes more than " + std::to_string(rest) +
+                    " bytes, more than a slab may hold (" + std::to_string(limit) + ", 8 x max_in_bytes)");
+    if (st.keep_tail(st.d_raw + consumed, rest) != BT_OK) return BT_ERR;
+    *d_text = st.d_text;
+    return BT_OK;
+}
+
+int fastq_text_finish(const char *who, BgzfStream &st, FastqText &ft, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats) {
+    if (!st.tail) return BT_OK;
+    // the tail is the file's end: its last line needs no newline, and a record of fewer than four lines is a truncated file
+    if (grow(reinterpret_cast<void **>(&st.d_text), &st.cap_text, st.tail) != BT_OK) return BT_ERR;
+    uint64_t consumed = 0;
+    bt_fastq_stats now{0, 0, 0};
+    if (fastq_text_run(who, st.ctx, ft.work, st.d_tail, st.tail, 1, ft.line, st.d_text, st.cap_text, text_len, &consumed, &now) != BT_OK) return BT_ERR;
+    if (stats) *stats = now;
+    ft.line += now.lines;
+    ft.stream_offset += consumed;
+    st.tail = 0;
+    *d_text = st.d_text;
+    return BT_OK;
+}
+
+}  // namespace bt
+
+// Slabs of whole BGZF blocks in, reads text out.  The decompressed bytes of a call land behind the tail the call before left (the record that was not whole).
+struct bt_fastq_scan {
+    BgzfStream st;
+    FastqText ft;
 };
 
 extern "C" {
@@ -411,21 +457,9 @@ int bt_fastq_scan_text(bt_fastq_scan *s, const uint8_t *h_blocks, uint64_t n_byt
     if (n_bytes > st.max_in_bytes) return fail("bt_fastq_scan_text: " + std::to_string(n_bytes) + " bytes handed in, the stream was created for " + std::to_string(st.max_in_bytes));
     bt_ctx *ctx = st.ctx;
     BT_HIP(hipSetDevice(ctx->device));
-    uint64_t raw = 0, consumed = 0;
+    uint64_t raw = 0;
     if (st.inflate_slab(who, h_blocks, n_bytes, &raw) != BT_OK) return BT_ERR;
-    bt_fastq_stats now{0, 0, 0};
-    if (fastq_text_run(who, ctx, s->work, st.d_raw, raw, 0, s->line, st.d_text, st.cap_text, text_len, &consumed, &now) != BT_OK) return BT_ERR;
-    if (stats) *stats = now;
-    // what is left is the start of a record that is not whole: it waits in d_tail for the next call
-    const uint64_t rest = raw - consumed, limit = 8 * st.max_in_bytes;
-    s->line += now.lines;
-    s->stream_offset += consumed;
-    if (rest > limit)
-        return fail("bt_fastq_scan_text: the FASTQ record at line " + std::to_string(s->line) + " (offset " + std::to_string(s->stream_offset) + ") takes more than " + std::to_string(rest) +
-                    " bytes, more than a slab may hold (" + std::to_string(limit) + ", 8 x max_in_bytes)");
-    if (st.keep_tail(st.d_raw + consumed, rest) != BT_OK) return BT_ERR;
-    *d_text = st.d_text;
-    return BT_OK;
+    return fastq_text_slab(who, st, s->ft, raw, d_text, text_len, stats);
 }
 
 int bt_fastq_scan_finish(bt_fastq_scan *s, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats) {
@@ -436,19 +470,8 @@ int bt_fastq_scan_finish(bt_fastq_scan *s, const char **d_text, uint64_t *text_l
     if (stats) *stats = bt_fastq_stats{0, 0, 0};
     BgzfStream &st = s->st;
     if (!st.tail) return BT_OK;
-    bt_ctx *ctx = st.ctx;
-    BT_HIP(hipSetDevice(ctx->device));
-    // the tail is the file's end: its last line needs no newline, and a record of fewer than four lines is a truncated file
-    if (grow(reinterpret_cast<void **>(&st.d_text), &st.cap_text, st.tail) != BT_OK) return BT_ERR;
-    uint64_t consumed = 0;
-    bt_fastq_stats now{0, 0, 0};
-    if (fastq_text_run(who, ctx, s->work, st.d_tail, st.tail, 1, s->line, st.d_text, st.cap_text, text_len, &consumed, &now) != BT_OK) return BT_ERR;
-    if (stats) *stats = now;
-    s->line += now.lines;
-    s->stream_offset += consumed;
-    st.tail = 0;
-    *d_text = st.d_text;
-    return BT_OK;
+    BT_HIP(hipSetDevice(st.ctx->device));
+    return fastq_text_finish(who, st, s->ft, d_text, text_len, stats);
 }
 
 void bt_fastq_scan_destroy(bt_fastq_scan *s) {

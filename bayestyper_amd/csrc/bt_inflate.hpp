@@ -44,6 +44,7 @@ enum Status : uint32_t {
     kBadLength,        // output length != ISIZE
     kBadCrc,           // CRC-32 mismatch
     kBadTable,         // the block table's entry lies outside the input or the output
+    kBadStreamDistance,   // (bt_gunzip.hpp) a distance reaching before the first byte of a gzip member, or of the window handed in
     kNumStatus
 };
 inline const char *status_text(uint32_t s) {
@@ -58,7 +59,8 @@ inline const char *status_text(uint32_t s) {
                                     "deflate stream ends before the payload's end",
                                     "output length differs from ISIZE",
                                     "CRC-32 mismatch",
-                                    "block table entry out of range"};
+                                    "block table entry out of range",
+                                    "distance reaches before the stream's start"};
     return s < kNumStatus ? text[s] : "unknown status";
 }
 
@@ -182,6 +184,60 @@ BTD_HD inline uint32_t decode(Bits &b, const uint16_t *table, uint32_t fast, con
     return kNoSymbol;
 }
 
+// The two decode tables of a fixed (type 1, RFC 1951 3.2.6) or dynamic (type 2, 3.2.7: its header is read from b) block.  The same status on every lane.
+template <class T>
+BTD_HD inline uint32_t block_tables(Shared &sh, Bits &b, uint32_t type) {
+    uint32_t nlit = kNumLit, ndist = kNumDist;
+    if (type == 1) {   // RFC 1951 3.2.6
+        for (uint32_t s = T::lane(); s < kNumLit + kNumDist; s += T::W) sh.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
+    } else {           // 3.2.7
+        nlit = b.take(5) + 257;
+        ndist = b.take(5) + 1;
+        const uint32_t nclen = b.take(4) + 4;
+        if (b.cnt < 0) return kInputEnd;
+        if (nlit > 286 || ndist > 30) return kBadCodeLengths;
+        for (uint32_t i = 0; i < kNumClen; ++i) {
+            uint32_t v = 0;
+            if (i < nclen) {
+                b.refill();
+                v = b.take(3);
+            }
+            if (T::lane() == 0) sh.cllen[btdeflate::clen_order(i)] = (uint8_t)v;
+        }
+        if (b.cnt < 0) return kInputEnd;
+        const uint32_t st = build_table<T>(sh, sh.cllen, kNumClen, sh.lit, 7, sh.lsym, sh.lcount, false);
+        if (st != kOk) return st;
+        uint32_t prev = 0;
+        for (uint32_t i = 0; i < nlit + ndist;) {
+            b.refill();
+            const uint32_t s = decode(b, sh.lit, 7, sh.lsym, sh.lcount);
+            if (s == kNoSymbol) return b.cnt < (int32_t)kMaxBits ? kInputEnd : kBadSymbol;
+            uint32_t rep = 1, v = s;
+            if (s == 16) {
+                if (i == 0) return kBadCodeLengths;
+                v = prev, rep = 3 + b.take(2);
+            } else if (s == 17)
+                v = 0, rep = 3 + b.take(3);
+            else if (s == 18)
+                v = 0, rep = 11 + b.take(7);
+            if (b.cnt < 0) return kInputEnd;
+            if (rep > nlit + ndist - i) return kBadCodeLengths;
+            if (T::lane() == 0)
+                for (uint32_t j = 0; j < rep; ++j) {
+                    const uint32_t at = i + j;
+                    sh.len[at < nlit ? at : kNumLit + (at - nlit)] = (uint8_t)v;
+                }
+            prev = v;
+            i += rep;
+        }
+    }
+    T::sync();
+    if (sh.len[256] == 0) return kBadCodeLengths;
+    uint32_t st = build_table<T>(sh, sh.len, nlit, sh.lit, kLitBits, sh.lsym, sh.lcount, false);
+    if (st == kOk) st = build_table<T>(sh, sh.len + kNumLit, ndist, sh.dist, kDistBits, sh.dsym, sh.dcount, true);
+    return st;
+}
+
 // in[0..n): a raw deflate stream that has to end at n exactly; out[0..isize): what it has to decode to.  The same status on every lane.
 template <class T>
 BTD_HD inline uint32_t inflate_stream(Shared &sh, const uint8_t *in, uint32_t n, uint8_t *out, uint32_t isize) {
@@ -210,54 +266,7 @@ BTD_HD inline uint32_t inflate_stream(Shared &sh, const uint8_t *in, uint32_t n,
             b.cnt = 0;
             continue;
         }
-        uint32_t nlit = kNumLit, ndist = kNumDist;
-        if (type == 1) {   // RFC 1951 3.2.6
-            for (uint32_t s = T::lane(); s < kNumLit + kNumDist; s += T::W) sh.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
-        } else {           // 3.2.7
-            nlit = b.take(5) + 257;
-            ndist = b.take(5) + 1;
-            const uint32_t nclen = b.take(4) + 4;
-            if (b.cnt < 0) return kInputEnd;
-            if (nlit > 286 || ndist > 30) return kBadCodeLengths;
-            for (uint32_t i = 0; i < kNumClen; ++i) {
-                uint32_t v = 0;
-                if (i < nclen) {
-                    b.refill();
-                    v = b.take(3);
-                }
-                if (T::lane() == 0) sh.cllen[btdeflate::clen_order(i)] = (uint8_t)v;
-            }
-            if (b.cnt < 0) return kInputEnd;
-            const uint32_t st = build_table<T>(sh, sh.cllen, kNumClen, sh.lit, 7, sh.lsym, sh.lcount, false);
-            if (st != kOk) return st;
-            uint32_t prev = 0;
-            for (uint32_t i = 0; i < nlit + ndist;) {
-                b.refill();
-                const uint32_t s = decode(b, sh.lit, 7, sh.lsym, sh.lcount);
-                if (s == kNoSymbol) return b.cnt < (int32_t)kMaxBits ? kInputEnd : kBadSymbol;
-                uint32_t rep = 1, v = s;
-                if (s == 16) {
-                    if (i == 0) return kBadCodeLengths;
-                    v = prev, rep = 3 + b.take(2);
-                } else if (s == 17)
-                    v = 0, rep = 3 + b.take(3);
-                else if (s == 18)
-                    v = 0, rep = 11 + b.take(7);
-                if (b.cnt < 0) return kInputEnd;
-                if (rep > nlit + ndist - i) return kBadCodeLengths;
-                if (T::lane() == 0)
-                    for (uint32_t j = 0; j < rep; ++j) {
-                        const uint32_t at = i + j;
-                        sh.len[at < nlit ? at : kNumLit + (at - nlit)] = (uint8_t)v;
-                    }
-                prev = v;
-                i += rep;
-            }
-        }
-        T::sync();
-        if (sh.len[256] == 0) return kBadCodeLengths;
-        uint32_t st = build_table<T>(sh, sh.len, nlit, sh.lit, kLitBits, sh.lsym, sh.lcount, false);
-        if (st == kOk) st = build_table<T>(sh, sh.len + kNumLit, ndist, sh.dist, kDistBits, sh.dsym, sh.dcount, true);
+        const uint32_t st = block_tables<T>(sh, b, type);
         if (st != kOk) return st;
         for (;;) {   // a turn takes at most 15 + 5 + 15 + 13 = 48 bits; a refill leaves at least 56 unless the payload ends
             b.refill();

@@ -1,6 +1,7 @@
 // Every read file of <prefix>.reads to the consumers of the reads scan (include/btgpu.h: bt_reads_*), whatever its format.  A file is told by its content, not by
 // its name: a BAM (BamFile::isBam) goes through the stream object of libbtgpu — compressed blocks in, reads text in device memory out (bt_bam_scan_text) — and
-// reaches `device_text`; so does a FASTQ compressed as BGZF (isBgzfFastq; bt_fastq_scan_text), unless BT_FASTQ_BGZF_ON_HOST=1 sends it the old way; every other
+// reaches `device_text`; so does a FASTQ compressed as BGZF (isBgzfFastq; bt_fastq_scan_text), unless BT_FASTQ_BGZF_ON_HOST=1 sends it the old way, and, only
+// with BT_FASTQ_GZIP_ON_DEVICE=1, a FASTQ that is ordinary gzip (isGzipFastq, isBgzfFastq's counterpart for one long member; bt_fastq_gz_scan_text); every other
 // file is read as FASTA / FASTQ on the host (forEachReadsSlab) and reaches `host_slab`, as before BAM was taken.
 #pragma once
 #include <functional>
@@ -12,6 +13,7 @@
 
 #include "../../include/btgpu.h"
 #include "BamFile.hpp"
+#include "GzipFile.hpp"
 #include "ReadsFile.hpp"
 
 namespace bthost {
@@ -22,24 +24,28 @@ struct ReadsSinks {
 };
 
 // for the BT_STAGE_TIMES rows of the reads route: which of the files went through a stream object of the device
-inline std::string deviceRouteNote(size_t bam_files, size_t bgzf_fastq_files) {
+inline std::string deviceRouteNote(size_t bam_files, size_t bgzf_fastq_files, size_t gzip_fastq_files = 0) {
     std::string note;
     if (bam_files) note += " (" + std::to_string(bam_files) + " BAM file(s) on the device)";
     if (bgzf_fastq_files) note += " (" + std::to_string(bgzf_fastq_files) + " BGZF FASTQ file(s) on the device)";
+    if (gzip_fastq_files) note += " (" + std::to_string(gzip_fastq_files) + " gzip FASTQ file(s) on the device)";
     return note;
 }
 
 // ReadsTotals of a BAM file: bases and reads of the kept records (flag & skip_flags == 0), slabs = calls of bt_bam_scan_text; of a BGZF FASTQ file: bases and
-// reads of the records with at least one base, slabs = calls of bt_fastq_scan_text
-// *bam_files, *bgzf_fastq_files (may be NULL): how many of the list's files were BAM files, and BGZF-compressed FASTQ files read on the device
+// reads of the records with at least one base, slabs = calls of bt_fastq_scan_text; of a gzip FASTQ file the same, slabs = calls of bt_fastq_gz_scan_text
+// *bam_files, *bgzf_fastq_files, *gzip_fastq_files (may be NULL): how many of the list's files were BAM files, BGZF-compressed FASTQ files and ordinary gzip
+// FASTQ files read on the device
 inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const ReadsSinks &sinks,
-                                      size_t *bam_files = nullptr, size_t *bgzf_fastq_files = nullptr) {
-    std::vector<std::string> bams, fastqs, texts;
-    const bool fastq_on_host = fastqBgzfOnHost();
-    for (const std::string &f : readReadsList(prefix)) (BamFile::isBam(f) ? bams : !fastq_on_host && isBgzfFastq(f) ? fastqs : texts).push_back(f);
+                                      size_t *bam_files = nullptr, size_t *bgzf_fastq_files = nullptr, size_t *gzip_fastq_files = nullptr) {
+    std::vector<std::string> bams, fastqs, gzips, texts;
+    const bool fastq_on_host = fastqBgzfOnHost(), gzip_on_device = fastqGzipOnDevice();
+    for (const std::string &f : readReadsList(prefix))
+        (BamFile::isBam(f) ? bams : !fastq_on_host && isBgzfFastq(f) ? fastqs : gzip_on_device && isGzipFastq(f) ? gzips : texts).push_back(f);
     ReadsTotals totals;
     if (bam_files) *bam_files = bams.size();
     if (bgzf_fastq_files) *bgzf_fastq_files = fastqs.size();
+    if (gzip_fastq_files) *gzip_fastq_files = gzips.size();
     const size_t bgzf_slab = std::max<size_t>(slab_bytes / 2, 65536);   // compressed bytes: about a quarter of the text they hold
     auto check = [](int rc, const std::string &file) {
         if (rc != BT_OK) throw std::runtime_error("read file " + file + ": " + bt_last_error());
@@ -104,6 +110,39 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
         }
         bt_fastq_scan_destroy(scan);
         totals.files++;
+    }
+    if (!gzips.empty()) {
+        // compressed bytes per call: a block is a team's work, and some thousands of teams fill the device; the stream object's buffers take about 60 times as much
+        const size_t gzip_slab = std::min<size_t>(std::max<size_t>(slab_bytes, 65536), (size_t)32 << 20);
+        const uint32_t chunk_bytes = gunzipChunkBytes();
+        for (const std::string &f : gzips) {
+            GzipFastqFile file(f, gzip_slab);
+            bt_fastq_gz_scan *scan = nullptr;
+            check(bt_fastq_gz_scan_create(ctx, gzip_slab, chunk_bytes, &scan), f);
+            try {
+                std::vector<uint8_t> slab;
+                const char *d_text = nullptr;
+                uint64_t len = 0;
+                bt_fastq_stats stats;
+                auto deliver = [&]() {
+                    if (len) sinks.device_text(d_text, len);
+                    totals.bases += stats.bases;
+                    totals.reads += stats.reads;
+                };
+                while (file.next(slab)) {
+                    check(bt_fastq_gz_scan_text(scan, slab.data(), slab.size(), &d_text, &len, &stats), f);
+                    deliver();
+                    totals.slabs++;
+                }
+                check(bt_fastq_gz_scan_finish(scan, &d_text, &len, &stats), f);   // the file ends at a member boundary; its last record, when its last line has no newline
+                deliver();
+            } catch (...) {
+                bt_fastq_gz_scan_destroy(scan);
+                throw;
+            }
+            bt_fastq_gz_scan_destroy(scan);
+            totals.files++;
+        }
     }
     if (!texts.empty()) {
         const ReadsTotals t = forEachReadsSlab(texts, kmer_size, threads, slab_bytes, sinks.host_slab);

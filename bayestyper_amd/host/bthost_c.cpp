@@ -15,6 +15,7 @@
 #include "KmerHashOrder.hpp"
 #include "Parallel.hpp"
 #include "BamFile.hpp"
+#include "GzipFile.hpp"
 #include "ReadsFile.hpp"
 #include "InferenceUnit.hpp"
 #include "KmerCounter.hpp"
@@ -823,6 +824,34 @@ long long bth_bgzf_fastq_file_slabs(const char *path, unsigned long long slab_by
             all.append(reinterpret_cast<const char *>(slab.data()), slab.size());
         }
         if (stats) stats[0] = first_at, stats[1] = file.hasEofBlock() ? 1 : 0, stats[2] = slabs, stats[3] = file.fileBytes();
+        return (long long)copy_out(all, buf, cap);
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// isGzipFastq: 1 a FASTQ compressed as ordinary gzip (not BGZF), 0 anything else, -1 an error (an unreadable file; text in *err).  No GPU.
+int bth_fastq_is_gzip(const char *path, char *err, unsigned err_len) {
+    try {
+        return isGzipFastq(path) ? 1 : 0;
+    } catch (const std::exception &e) {
+        return stage_error(e, err, err_len);
+    }
+}
+// GzipFastqFile: the slabs of one gzip file laid end to end -> buf (when it fits); stats[0..2] = slabs, file bytes, the longest slab; returns the bytes
+// needed, or -1 (error text in *err).  No GPU.
+long long bth_gzip_fastq_file_slabs(const char *path, unsigned long long slab_bytes, char *buf, unsigned long long cap, unsigned long long *stats, char *err, unsigned err_len) {
+    try {
+        GzipFastqFile file(path, (size_t)slab_bytes);
+        std::string all;
+        std::vector<uint8_t> slab;
+        uint64_t slabs = 0, longest = 0;
+        while (file.next(slab)) {
+            if (file.slabOffset() != all.size()) throw std::runtime_error("slab offset out of step");
+            ++slabs;
+            longest = std::max<uint64_t>(longest, slab.size());
+            all.append(reinterpret_cast<const char *>(slab.data()), slab.size());
+        }
+        if (stats) stats[0] = slabs, stats[1] = file.fileBytes(), stats[2] = longest;
         return (long long)copy_out(all, buf, cap);
     } catch (const std::exception &e) {
         return stage_error(e, err, err_len);

@@ -1472,6 +1472,129 @@ class FastqScan:
             self.h = None
 
 
+class GunzipStats(C.Structure):   # include/btgpu.h: bt_gunzip_stats
+    _fields_ = [("rounds", C.c_uint64), ("candidates", C.c_uint64), ("links_verified", C.c_uint64), ("links_broken", C.c_uint64), ("blocks", C.c_uint64),
+                ("out_bytes", C.c_uint64)]
+
+
+def parse_gunzip_stats(st):
+    """bt_gunzip_stats -> dict"""
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+_raw_args = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(GunzipStats)]
+bt_inflate_raw = _sig("bt_inflate_raw", [vp] + _raw_args)
+bt_diag_inflate_raw = _sig("bt_diag_inflate_raw", _raw_args)
+bt_gunzip_default_chunk_bytes = _sig("bt_gunzip_default_chunk_bytes", [], C.c_uint32)
+bt_gunzip_expansion_budget = _sig("bt_gunzip_expansion_budget", [], C.c_uint32)
+bt_fastq_gz_scan_create = _sig("bt_fastq_gz_scan_create", [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)])
+bt_fastq_gz_scan_text = _sig("bt_fastq_gz_scan_text", [vp, vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(FastqStats)])
+bt_fastq_gz_scan_finish = _sig("bt_fastq_gz_scan_finish", [vp, C.POINTER(vp), u64p, C.POINTER(FastqStats)])
+bt_fastq_gz_scan_stats = _sig("bt_fastq_gz_scan_stats", [vp, C.POINTER(GunzipStats)])
+bt_fastq_gz_scan_destroy = _sig("bt_fastq_gz_scan_destroy", [vp], None)
+bt_diag_gunzip_stage_seconds = _sig("bt_diag_gunzip_stage_seconds", [C.POINTER(C.c_double), C.c_int], None)
+GUNZIP_DEFAULT_CHUNK = int(bt_gunzip_default_chunk_bytes())
+GUNZIP_EXPAND = int(bt_gunzip_expansion_budget())
+GUNZIP_GUARD = 64   # bytes behind the capacity, preset to 0xA5 and checked
+
+
+def _raw_result(out, cap, n, end, fin, crc, st):
+    assert (out[cap:] == 0xA5).all(), "bytes written at or past the capacity"
+    assert (out[n.value:cap] == 0xA5).all(), "bytes written past out_bytes"
+    return {"data": out[:n.value].tobytes(), "end_bit": int(end.value), "stream_end": int(fin.value), "crc32": int(crc.value), "stats": parse_gunzip_stats(st)}
+
+
+def diag_inflate_raw(data, start_bit=0, window=b"", chunk_bytes=0, capacity=None):
+    """bt_diag_inflate_raw (no GPU): a raw deflate stream from the block boundary start_bit on, `window` = the output before it -> dict(data, end_bit,
+    stream_end, crc32, stats).  capacity None: 16 MiB.  The bytes behind the output and behind the capacity are checked to be untouched."""
+    a, w = _bytes_array(data), _bytes_array(window)
+    cap = (16 << 20) if capacity is None else capacity
+    out = np.full(cap + GUNZIP_GUARD, 0xA5, np.uint8)
+    n, end, fin, crc, st = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint32(), GunzipStats()
+    check(bt_diag_inflate_raw(_np_ptr(a) if a.size else None, a.size, start_bit, _np_ptr(w) if w.size else None, w.size, chunk_bytes, _np_ptr(out), cap, C.byref(n), C.byref(end),
+                              C.byref(fin), C.byref(crc), C.byref(st)))
+    return _raw_result(out, cap, n, end, fin, crc, st)
+
+
+def inflate_raw(ctx, data, start_bit=0, window=b"", chunk_bytes=0, capacity=None):
+    """bt_inflate_raw over host buffers (uploaded) -> as diag_inflate_raw"""
+    a, w = _bytes_array(data), _bytes_array(window)
+    cap = (16 << 20) if capacity is None else capacity
+    d_in, d_win, d_out = DeviceBuffer(ctx, a.size + 8), DeviceBuffer(ctx, w.size + 8), DeviceBuffer(ctx, cap + GUNZIP_GUARD)
+    try:
+        if a.size:
+            d_in.upload(a)
+        if w.size:
+            d_win.upload(w)
+        check(bt_memset(ctx.h, d_out.ptr, 0xA5, d_out.nbytes))
+        n, end, fin, crc, st = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint32(), GunzipStats()
+        try:
+            check(bt_inflate_raw(ctx.h, d_in.ptr if a.size else None, a.size, start_bit, d_win.ptr if w.size else None, w.size, chunk_bytes, d_out.ptr, cap, C.byref(n), C.byref(end),
+                                 C.byref(fin), C.byref(crc), C.byref(st)))
+        finally:
+            ctx.sync()
+            out = d_out.download(np.uint8, cap + GUNZIP_GUARD)
+            assert (out[cap:] == 0xA5).all(), "bytes written at or past the capacity"
+        return _raw_result(out, cap, n, end, fin, crc, st)
+    finally:
+        d_in.free()
+        d_win.free()
+        d_out.free()
+
+
+def gunzip_stage_seconds(reset=False):
+    """bt_diag_gunzip_stage_seconds -> dict of wall seconds per stage (find, decode, windows, resolve, crc)"""
+    out = (C.c_double * 5)()
+    bt_diag_gunzip_stage_seconds(out, int(bool(reset)))
+    return dict(zip(("find", "decode", "windows", "resolve", "crc"), (float(x) for x in out)))
+
+
+class FastqGzScan:
+    """bt_fastq_gz_scan: any cuts of an ordinary gzip FASTQ file (one or more long members) -> reads text in device memory"""
+
+    def __init__(self, ctx, max_in_bytes, chunk_bytes=0):
+        self.ctx = ctx
+        h = vp()
+        check(bt_fastq_gz_scan_create(ctx.h, max_in_bytes, chunk_bytes, C.byref(h)))
+        self.h = h.value
+
+    def text(self, data):
+        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
+        a = _bytes_array(data)
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(bt_fastq_gz_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def finish(self):
+        """the file has to end at a member boundary; the carried tail as the file's end -> (device pointer of its text, its length, stats)"""
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(bt_fastq_gz_scan_finish(self.h, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def _download(self, d, n, st):
+        out = np.empty(n, np.uint8)
+        if n:
+            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
+        return out.tobytes(), st
+
+    def text_bytes(self, data):
+        return self._download(*self.text(data))
+
+    def finish_bytes(self):
+        return self._download(*self.finish())
+
+    def stats(self):
+        """the sums of the inflate calls' stats so far"""
+        st = GunzipStats()
+        check(bt_fastq_gz_scan_stats(self.h, C.byref(st)))
+        return parse_gunzip_stats(st)
+
+    def close(self):
+        if self.h:
+            bt_fastq_gz_scan_destroy(self.h)
+            self.h = None
+
+
 def parse_genotype_text(text, index):
     """text and index of bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text (layout: include/btgpu.h) -> per variant, in the string's order, a
     dictionary with the three pieces as str — "stats", "cover", "samples" with every GQ (derived here from the cell's best posterior, as the host layer

@@ -1028,6 +1028,59 @@ int bt_fastq_scan_text(bt_fastq_scan *scan, const uint8_t *h_blocks, uint64_t n_
 int bt_fastq_scan_finish(bt_fastq_scan *scan, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats);
 void bt_fastq_scan_destroy(bt_fastq_scan *scan);
 
+/* ------------------------------------------------------------------------------------------
+ * Ordinary gzip FASTQ samples on the device: ONE long gzip member (gzip, pigz, `fasterq-dump | gzip`) inflated by many wavefronts at once, then the FASTQ
+ * parse above.  Replaces zlib's `inflate` under the host's ReadsFile, one thread per file.  bayestyper_amd/csrc/bt_gunzip.hpp holds the algorithm, one text
+ * for the kernels and the host (the two-stage scheme of pugz and rapidgzip): plausible dynamic block headers are searched at every bit offset, the first of
+ * every chunk_bytes of input starts a team that decodes to 16-bit symbols (a byte, or a marker for a byte of the 32 KiB before its start, which it does
+ * not know); a team's output is used only when the team before it ended exactly where it started, so the bytes are those of a serial inflate whatever the
+ * guesses were.  Damaged input is an error naming the block ("deflate block at offset <byte> (bit <0..7>): <condition>"), never a fault or a hang.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bt_gunzip_stats {
+    uint64_t rounds;           /* decode launches of team 0 (the candidates' teams are decoded once per call) */
+    uint64_t candidates;       /* chunks behind the start's in which a plausible header was found */
+    uint64_t links_verified;   /* candidates' teams taken: the team before ended exactly at their start */
+    uint64_t links_broken;     /* rounds that ended because a team did not end at the next start (a false candidate, a team out of room) */
+    uint64_t blocks, out_bytes;
+} bt_gunzip_stats;
+/* Replaces zlib's inflate (raw deflate, windowBits -15) under ReadsFile.  d_in [in_bytes] (at most 128 MiB): a raw deflate stream, or a part of one;
+ * start_bit: a block boundary in it; d_window [window_bytes <= 32768]: the output that precedes start_bit (none at a stream's start: a distance reaching
+ * before it is an error); chunk_bytes: 0 = the default, at least 1024.  Whole blocks are decoded from start_bit into d_out: after the final block
+ * *stream_end = 1 and *end_bit is the bit behind it; otherwise *end_bit is the last block boundary whose next block is not whole inside the input or would
+ * not fit capacity (at most 1 GiB is produced per call).  Zero progress is a result (*out_bytes = 0, *end_bit = start_bit), not an error.  Nothing is
+ * written at or past capacity.  *crc32: zlib's crc32 of the bytes produced.  stats may be NULL.  The bytes, *end_bit, *stream_end and *crc32 do not depend on
+ * chunk_bytes.  Complete on return. */
+int bt_inflate_raw(bt_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, uint64_t start_bit, const uint8_t *d_window, uint64_t window_bytes, uint32_t chunk_bytes, uint8_t *d_out,
+                   uint64_t capacity, uint64_t *out_bytes, uint64_t *end_bit, int *stream_end, uint32_t *crc32, bt_gunzip_stats *stats);
+/* Host-side run of bt_inflate_raw (replaces the same zlib inflate; the same __host__ __device__ code with a team of one thread and host pointers, no GPU):
+ * the same bytes, *end_bit, message and stats, which are functions of the input and the parameters alone. */
+int bt_diag_inflate_raw(const uint8_t *h_in, uint64_t in_bytes, uint64_t start_bit, const uint8_t *h_window, uint64_t window_bytes, uint32_t chunk_bytes, uint8_t *h_out, uint64_t capacity,
+                        uint64_t *out_bytes, uint64_t *end_bit, int *stream_end, uint32_t *crc32, bt_gunzip_stats *stats);
+/* What chunk_bytes = 0 stands for, and the symbols of room a candidate's team has per compressed byte of its span. */
+uint32_t bt_gunzip_default_chunk_bytes(void);
+uint32_t bt_gunzip_expansion_budget(void);
+/* Wall seconds this process has spent in the stages of bt_inflate_raw and bt_fastq_gz_scan_text -> seconds5 (may be NULL): find, decode, windows, resolve,
+ * crc; reset != 0 zeroes them.  The windows and resolve stages are told apart only when BT_GUNZIP_STAGE_TIMES is set (it adds a synchronisation). */
+void bt_diag_gunzip_stage_seconds(double *seconds5, int reset);
+
+/* The stream object, the twin of bt_fastq_scan for a gzip file that is not BGZF (replaces zlib's inflate and gzread under ReadsFile).  max_in_bytes
+ * (64 KiB .. 64 MiB): the most a call hands in.  The object parses each member's RFC 1952 header on the host (FEXTRA, FNAME, FCOMMENT, FHCRC), carries the
+ * compressed bytes not consumed yet, the bit offset, the 32 KiB window and the running CRC-32 and length, checks each member's trailer (CRC-32 and ISIZE)
+ * and goes on into a following member. */
+typedef struct bt_fastq_gz_scan bt_fastq_gz_scan;
+int bt_fastq_gz_scan_create(bt_ctx *ctx, uint64_t max_in_bytes, uint32_t chunk_bytes /* 0 = default */, bt_fastq_gz_scan **out);
+/* h_bytes [n_bytes]: any cut of the file, in file order from call to call.  Every whole deflate block the carried bytes hold is inflated behind the FASTQ
+ * tail the previous call left and turned into text as bt_fastq_scan_text does: *d_text [*text_len] is device memory, valid until the next call on this
+ * object.  A deflate block that is not whole within max_in_bytes of carried input, or that inflates to more than 8 x max_in_bytes, is refused with a
+ * message that says so.  A damaged member is an error naming the member's and the block's file offsets.  stats (may be NULL): this call's.  After an error
+ * the object can only be destroyed.  Complete on return. */
+int bt_fastq_gz_scan_text(bt_fastq_gz_scan *scan, const uint8_t *h_bytes, uint64_t n_bytes, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats);
+/* Fails with "truncated gzip file" unless the file ended at a member boundary; then the carried FASTQ tail is judged as bt_fastq_scan_finish does. */
+int bt_fastq_gz_scan_finish(bt_fastq_gz_scan *scan, const char **d_text, uint64_t *text_len, bt_fastq_stats *stats);
+/* The sums of the inflate calls' stats so far. */
+int bt_fastq_gz_scan_stats(const bt_fastq_gz_scan *scan, bt_gunzip_stats *stats);
+void bt_fastq_gz_scan_destroy(bt_fastq_gz_scan *scan);
+
 #ifdef __cplusplus
 }
 #endif
