@@ -2,6 +2,7 @@
 //   bt_reads_count      <- KmerCounter::parseSampleKmers + parseSampleKmersCallBack (KmerCounter.cpp:388-524)
 //   bt_reads_make_bloom <- bayesTyperTools makeBloom (MakeBloom.cpp:200-295)
 //   bt_reads_sketch     (no counterpart: the number of distinct k-mers a KMC database states in its header, estimated)
+//   bt_reads_*_packed   the same three over packed reads (bt_reads_pack.hpp: 2-bit codes and validity bits), the input of a pass that reads a sample's reads pack
 // Both reference consumers are pure functions of the multiset of canonical k-mers of the reads (makeBloom of the set alone), so one streaming pass over
 // the reads text computes what they compute from the database: no database is written, no k-mer sorted.  The window code is bt_reads_window.hpp, one
 // front end over a consumer policy; the table and Bloom primitives are those of the KMC scan (bt_table_device.hpp, bt_kmer_device.hpp).
@@ -99,6 +100,31 @@ int reads_launch(bt_ctx *ctx, const char *d_text, uint64_t len, uint64_t first_e
     return BT_OK;
 }
 
+// the sibling over a packed text (bt_reads_pack.hpp): the image starts 64 positions before the tile, so it is as large as the text kernels'
+template <class Consumer>
+__global__ __launch_bounds__(BlockTeam::LANES) void reads_packed_kernel(const uint32_t *__restrict__ packed, uint64_t positions, uint64_t first_end, RollConst c, Consumer consumer) {
+    __shared__ __attribute__((aligned(16))) uint8_t codes[READS_TILE + READS_PACKED_LEAD];
+    BlockTeam team{codes};
+    reads_front_end_packed(team, packed, positions, first_end, c, consumer);
+    consumer.finish();
+}
+
+template <class Consumer>
+int reads_launch_packed(bt_ctx *ctx, const uint8_t *d_packed, uint64_t positions, uint64_t first_end, unsigned k, const Consumer &consumer) {
+    if (positions == 0 || first_end >= positions) return BT_OK;
+    BT_HIP(hipSetDevice(ctx->device));
+    const unsigned grid = grid_for(positions, (unsigned)READS_TILE, (unsigned)ctx->num_cu * 8u);
+    hipLaunchKernelGGL(reads_packed_kernel<Consumer>, dim3(grid), dim3(BlockTeam::LANES), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_packed), positions, first_end,
+                       make_roll_const(k), consumer);
+    BT_CHECK_LAUNCH();
+    return BT_OK;
+}
+int check_packed(const char *who, const void *packed, uint64_t positions) {
+    if (positions && !packed) return fail(std::string(who) + ": null argument");
+    if (reinterpret_cast<uintptr_t>(packed) & 3u) return fail(std::string(who) + ": the packed reads must be 4-byte aligned");
+    return BT_OK;
+}
+
 int check_count_args(const char *who, bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx) {
     if (!ctx || !path_bloom || !table) return fail(std::string(who) + ": null argument");
     if (path_bloom->k != table->k) return fail(std::string(who) + ": k mismatch between table and bloom");
@@ -118,16 +144,18 @@ CountConsumer count_consumer(bt_bloom *path_bloom, bt_table *table, uint32_t sam
     return CountConsumer{table->v, path_bloom->view(), sample_idx, reinterpret_cast<unsigned long long *>(d_hit_count), 0u};
 }
 
-// Host text through the context's two staging slots (the pinned and device buffers bt_kmc_scan_run_host leaves with the context: taken when they are large enough,
-// left there afterwards): copy, transfer (own stream) and scan of consecutive chunks overlap.  A chunk starts k - 1 bytes before its first new byte and the kernel
-// consumes only the windows that end at a new byte, so the chunk size changes no result.  launch(d_chunk, bytes, first_end).  Blocking.
+// Host data through the context's two staging slots (the pinned and device buffers bt_kmc_scan_run_host leaves with the context: taken when they are large enough,
+// left there afterwards): copy, transfer (own stream) and scan of consecutive chunks overlap.  next(chunk): the next chunk's bytes in host memory (at most `need`),
+// the size it is launched with and the first position whose windows are new, false when none is left.  launch(d_chunk, size, first_end).  Blocking.
+struct ReadsChunk {
+    const void *src;
+    uint64_t bytes, size, first_end;
+};
+using ReadsChunkNext = std::function<bool(ReadsChunk &)>;
 using ReadsChunkLaunch = std::function<int(const char *, uint64_t, uint64_t)>;
-int reads_stream(bt_ctx *ctx, const char *what, const char *h_text, uint64_t len, unsigned k, uint64_t chunk_bytes, const ReadsChunkLaunch &launch) {
-    if (len == 0) return BT_OK;
+int reads_stream_chunks(bt_ctx *ctx, const char *what, size_t need, const ReadsChunkNext &next, const ReadsChunkLaunch &launch) {
     BT_HIP(hipSetDevice(ctx->device));
-    const uint64_t halo = k - 1u;
-    chunk_bytes = std::max<uint64_t>(64, std::min<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), len));
-    const size_t need = (size_t)(chunk_bytes + halo + 15) / 16 * 16;
+    need = (need + 15) / 16 * 16;
     uint8_t *pin[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
     size_t have = 0;
     hipError_t e = hipSuccess;
@@ -154,21 +182,19 @@ int reads_stream(bt_ctx *ctx, const char *what, const char *h_text, uint64_t len
         if (e == hipSuccess) e = hipEventCreateWithFlags(&scanned[b], hipEventDisableTiming);
     }
     int rc = BT_OK;
-    uint64_t done = 0;
-    for (uint64_t i = 0; e == hipSuccess && rc == BT_OK && done < len; ++i) {
+    ReadsChunk chunk;
+    for (uint64_t i = 0; e == hipSuccess && rc == BT_OK && next(chunk); ++i) {
         const int b = (int)(i & 1);
-        const uint64_t end = std::min(len, done + chunk_bytes), lo = done >= halo ? done - halo : 0;
         if (i >= 2) e = hipEventSynchronize(copied[b]);   // the pinned buffer of this slot has been read by its previous transfer
         if (e != hipSuccess) break;
-        std::memcpy(pin[b], h_text + lo, end - lo);
+        std::memcpy(pin[b], chunk.src, chunk.bytes);
         if (i >= 2) e = hipStreamWaitEvent(copy_stream, scanned[b], 0);   // the device buffer of this slot has been scanned
-        if (e == hipSuccess) e = hipMemcpyAsync(dev[b], pin[b], end - lo, hipMemcpyHostToDevice, copy_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dev[b], pin[b], chunk.bytes, hipMemcpyHostToDevice, copy_stream);
         if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, copied[b], 0);
         if (e != hipSuccess) break;
-        rc = launch(reinterpret_cast<const char *>(dev[b]), end - lo, done - lo);
+        rc = launch(reinterpret_cast<const char *>(dev[b]), chunk.size, chunk.first_end);
         if (rc == BT_OK) e = hipEventRecord(scanned[b], ctx->stream);
-        done = end;
     }
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
@@ -199,6 +225,79 @@ int reads_stream(bt_ctx *ctx, const char *what, const char *h_text, uint64_t len
     return BT_OK;
 }
 
+// A reads text: a chunk starts k - 1 bytes before its first new byte and the kernel consumes only the windows that end at a new byte, so the chunk size changes
+// no result.
+int reads_stream(bt_ctx *ctx, const char *what, const char *h_text, uint64_t len, unsigned k, uint64_t chunk_bytes, const ReadsChunkLaunch &launch) {
+    if (len == 0) return BT_OK;
+    const uint64_t halo = k - 1u;
+    chunk_bytes = std::max<uint64_t>(64, std::min<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), len));
+    uint64_t done = 0;
+    return reads_stream_chunks(ctx, what, (size_t)(chunk_bytes + halo), [&](ReadsChunk &c) {
+        if (done >= len) return false;
+        const uint64_t end = std::min(len, done + chunk_bytes), lo = done >= halo ? done - halo : 0;
+        c = ReadsChunk{h_text + lo, end - lo, end - lo, done - lo};
+        done = end;
+        return true;
+    }, launch);
+}
+
+// A packed text: the text route's rule in whole blocks.  A chunk starts on the block boundary at or before done - (k - 1) and is launched with first_end = done -
+// chunk start; chunk_bytes (0: 64 MiB) counts packed bytes, at least one block.
+int reads_stream_packed(bt_ctx *ctx, const char *what, const uint8_t *h_packed, uint64_t positions, unsigned k, uint64_t chunk_bytes, const ReadsChunkLaunch &launch) {
+    if (positions == 0) return BT_OK;
+    const uint64_t halo = k - 1u, total = reads_packed_bytes(positions);
+    const uint64_t chunk_positions = std::max<uint64_t>(1, std::min<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), total) / PACK_BLOCK_BYTES) * PACK_BLOCK_POSITIONS;
+    uint64_t done = 0;   // a multiple of 128 until the end
+    return reads_stream_chunks(ctx, what, (size_t)reads_packed_bytes(chunk_positions + PACK_BLOCK_POSITIONS), [&](ReadsChunk &c) {
+        if (done >= positions) return false;
+        const uint64_t end = std::min(positions, done + chunk_positions), lo = (done >= halo ? done - halo : 0) / PACK_BLOCK_POSITIONS * PACK_BLOCK_POSITIONS;
+        c = ReadsChunk{h_packed + lo / PACK_BLOCK_POSITIONS * PACK_BLOCK_BYTES, reads_packed_bytes(end - lo), end - lo, done - lo};
+        done = end;
+        return true;
+    }, launch);
+}
+
+// the host variants of the count and of the sketch around whichever stream feeds them: stream(d_hits) / stream(d_registers) launches every chunk
+int count_host(const char *who, bt_ctx *ctx, bt_table *table, uint64_t *h_hit_count, const std::function<int(uint64_t *)> &stream) {
+    BT_HIP(hipSetDevice(ctx->device));
+    uint64_t *d_hits = nullptr;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_hits), 8));
+    unsigned long long hits = 0;
+    hipError_t e = hipMemsetAsync(d_hits, 0, 8, ctx->stream);
+    int rc = e == hipSuccess ? BT_OK : fail(std::string(who) + ": " + hipGetErrorString(e));
+    if (rc == BT_OK) rc = stream(d_hits);
+    if (rc == BT_OK) {
+        e = hipMemcpyAsync(&hits, d_hits, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_hits);
+    if (rc != BT_OK) return rc;
+    int overflowed = 0;
+    if (bt_table_status(table, nullptr, nullptr, &overflowed) != BT_OK) return BT_ERR;
+    if (overflowed) return fail(std::string(who) + ": the count table is full, matched k-mers were dropped (bt_table_reserve before the scan)");
+    if (h_hit_count) *h_hit_count = hits;
+    return BT_OK;
+}
+int sketch_host(const char *who, bt_ctx *ctx, uint8_t *h_registers, const std::function<int(uint32_t *)> &stream) {
+    BT_HIP(hipSetDevice(ctx->device));
+    uint8_t *d_reg = nullptr;
+    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_reg), SKETCH_REGISTERS));
+    hipError_t e = hipMemcpyAsync(d_reg, h_registers, SKETCH_REGISTERS, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (h_registers is pageable: the copy has left it)
+    int rc = e == hipSuccess ? BT_OK : fail(std::string(who) + ": " + hipGetErrorString(e));
+    if (rc == BT_OK) rc = stream(reinterpret_cast<uint32_t *>(d_reg));
+    if (rc == BT_OK) {
+        e = hipMemcpyAsync(h_registers, d_reg, SKETCH_REGISTERS, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_reg);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -226,29 +325,11 @@ int bt_reads_count_host(bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint
     const char *who = "bt_reads_count_host";
     if (check_count_args(who, ctx, path_bloom, table, sample_idx) != BT_OK) return BT_ERR;
     if (len && !h_text) return fail("bt_reads_count_host: null argument");
-    BT_HIP(hipSetDevice(ctx->device));
-    uint64_t *d_hits = nullptr;
-    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_hits), 8));
-    unsigned long long hits = 0;
-    hipError_t e = hipMemsetAsync(d_hits, 0, 8, ctx->stream);
-    int rc = e == hipSuccess ? BT_OK : fail(std::string(who) + ": " + hipGetErrorString(e));
-    if (rc == BT_OK)
-        rc = reads_stream(ctx, who, h_text, len, table->k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
+    return count_host(who, ctx, table, h_hit_count, [&](uint64_t *d_hits) {
+        return reads_stream(ctx, who, h_text, len, table->k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
             return reads_launch(ctx, d, n, first_end, table->k, count_consumer(path_bloom, table, sample_idx, d_hits));
         });
-    if (rc == BT_OK) {
-        e = hipMemcpyAsync(&hits, d_hits, 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_hits);
-    if (rc != BT_OK) return rc;
-    int overflowed = 0;
-    if (bt_table_status(table, nullptr, nullptr, &overflowed) != BT_OK) return BT_ERR;
-    if (overflowed) return fail("bt_reads_count_host: the count table is full, matched k-mers were dropped (bt_table_reserve before the scan)");
-    if (h_hit_count) *h_hit_count = hits;
-    return BT_OK;
+    });
 }
 
 int bt_reads_make_bloom_host(bt_ctx *ctx, bt_bloom *sample_bloom, const char *h_text, uint64_t len, uint32_t k, uint64_t chunk_bytes) {
@@ -263,24 +344,63 @@ int bt_reads_sketch_host(bt_ctx *ctx, const char *h_text, uint64_t len, uint32_t
     const char *who = "bt_reads_sketch_host";
     if (!ctx || !h_registers || (len && !h_text)) return fail("bt_reads_sketch_host: null argument");
     if (k < 1 || k > 64) return fail("bt_reads_sketch_host: k must lie in 1 .. 64");
-    BT_HIP(hipSetDevice(ctx->device));
-    uint8_t *d_reg = nullptr;
-    BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_reg), SKETCH_REGISTERS));
-    hipError_t e = hipMemcpyAsync(d_reg, h_registers, SKETCH_REGISTERS, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (h_registers is pageable: the copy has left it)
-    int rc = e == hipSuccess ? BT_OK : fail(std::string(who) + ": " + hipGetErrorString(e));
-    if (rc == BT_OK)
-        rc = reads_stream(ctx, who, h_text, len, k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
-            return reads_launch(ctx, d, n, first_end, k, SketchConsumer{reinterpret_cast<uint32_t *>(d_reg)});
+    return sketch_host(who, ctx, h_registers, [&](uint32_t *d_reg) {
+        return reads_stream(ctx, who, h_text, len, k, chunk_bytes,
+                            [&](const char *d, uint64_t n, uint64_t first_end) { return reads_launch(ctx, d, n, first_end, k, SketchConsumer{d_reg}); });
+    });
+}
+
+// The same three consumers over a packed text (bt_reads_pack.hpp), device buffers and host buffers: (packed, positions) in place of (text, len).
+int bt_reads_count_packed(bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx, const uint8_t *d_packed, uint64_t positions, uint64_t *d_hit_count) {
+    const char *who = "bt_reads_count_packed";
+    if (check_count_args(who, ctx, path_bloom, table, sample_idx) != BT_OK || check_packed(who, d_packed, positions) != BT_OK) return BT_ERR;
+    return reads_launch_packed(ctx, d_packed, positions, 0, table->k, count_consumer(path_bloom, table, sample_idx, d_hit_count));
+}
+
+int bt_reads_make_bloom_packed(bt_ctx *ctx, bt_bloom *sample_bloom, const uint8_t *d_packed, uint64_t positions, uint32_t k) {
+    const char *who = "bt_reads_make_bloom_packed";
+    if (check_bloom_args(who, ctx, sample_bloom, k) != BT_OK || check_packed(who, d_packed, positions) != BT_OK) return BT_ERR;
+    return reads_launch_packed(ctx, d_packed, positions, 0, k, BloomConsumer{sample_bloom->view()});
+}
+
+int bt_reads_sketch_packed(bt_ctx *ctx, const uint8_t *d_packed, uint64_t positions, uint32_t k, uint8_t *d_registers) {
+    const char *who = "bt_reads_sketch_packed";
+    if (!ctx || !d_registers) return fail("bt_reads_sketch_packed: null argument");
+    if (check_packed(who, d_packed, positions) != BT_OK) return BT_ERR;
+    if (k < 1 || k > 64) return fail("bt_reads_sketch_packed: k must lie in 1 .. 64");
+    if (reinterpret_cast<uintptr_t>(d_registers) & 3u) return fail("bt_reads_sketch_packed: d_registers must be 4-byte aligned");
+    return reads_launch_packed(ctx, d_packed, positions, 0, k, SketchConsumer{reinterpret_cast<uint32_t *>(d_registers)});
+}
+
+int bt_reads_count_packed_host(bt_ctx *ctx, bt_bloom *path_bloom, bt_table *table, uint32_t sample_idx, const uint8_t *h_packed, uint64_t positions, uint64_t chunk_bytes,
+                               uint64_t *h_hit_count) {
+    const char *who = "bt_reads_count_packed_host";
+    if (check_count_args(who, ctx, path_bloom, table, sample_idx) != BT_OK || check_packed(who, h_packed, positions) != BT_OK) return BT_ERR;
+    return count_host(who, ctx, table, h_hit_count, [&](uint64_t *d_hits) {
+        return reads_stream_packed(ctx, who, h_packed, positions, table->k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
+            return reads_launch_packed(ctx, reinterpret_cast<const uint8_t *>(d), n, first_end, table->k, count_consumer(path_bloom, table, sample_idx, d_hits));
         });
-    if (rc == BT_OK) {
-        e = hipMemcpyAsync(h_registers, d_reg, SKETCH_REGISTERS, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_reg);
-    return rc;
+    });
+}
+
+int bt_reads_make_bloom_packed_host(bt_ctx *ctx, bt_bloom *sample_bloom, const uint8_t *h_packed, uint64_t positions, uint32_t k, uint64_t chunk_bytes) {
+    const char *who = "bt_reads_make_bloom_packed_host";
+    if (check_bloom_args(who, ctx, sample_bloom, k) != BT_OK || check_packed(who, h_packed, positions) != BT_OK) return BT_ERR;
+    return reads_stream_packed(ctx, who, h_packed, positions, k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
+        return reads_launch_packed(ctx, reinterpret_cast<const uint8_t *>(d), n, first_end, k, BloomConsumer{sample_bloom->view()});
+    });
+}
+
+int bt_reads_sketch_packed_host(bt_ctx *ctx, const uint8_t *h_packed, uint64_t positions, uint32_t k, uint64_t chunk_bytes, uint8_t *h_registers) {
+    const char *who = "bt_reads_sketch_packed_host";
+    if (!ctx || !h_registers) return fail("bt_reads_sketch_packed_host: null argument");
+    if (check_packed(who, h_packed, positions) != BT_OK) return BT_ERR;
+    if (k < 1 || k > 64) return fail("bt_reads_sketch_packed_host: k must lie in 1 .. 64");
+    return sketch_host(who, ctx, h_registers, [&](uint32_t *d_reg) {
+        return reads_stream_packed(ctx, who, h_packed, positions, k, chunk_bytes, [&](const char *d, uint64_t n, uint64_t first_end) {
+            return reads_launch_packed(ctx, reinterpret_cast<const uint8_t *>(d), n, first_end, k, SketchConsumer{d_reg});
+        });
+    });
 }
 
 int bt_reads_sketch_estimate(const uint8_t *h_registers, double *out) {
@@ -319,6 +439,29 @@ int bt_diag_reads_kmers(const char *h_text, uint64_t len, uint32_t k, uint64_t *
     reads_front_end(team, h_text, len, 0, make_roll_const(k), consume);
     *n = count;
     if (count > capacity) return fail("bt_diag_reads_kmers: buffer too small");
+    return BT_OK;
+}
+
+int bt_diag_reads_kmers_packed(const uint8_t *h_packed, uint64_t positions, uint32_t k, uint64_t *h_kmers, uint64_t *h_hashes, uint64_t *h_ends, uint64_t capacity, uint64_t *n) {
+    if (!n) return fail("bt_diag_reads_kmers_packed: null argument");
+    if (check_packed("bt_diag_reads_kmers_packed", h_packed, positions) != BT_OK) return BT_ERR;
+    if (k < 1 || k > 64) return fail("bt_diag_reads_kmers_packed: k must lie in 1 .. 64");
+    PackedHostTeam team;
+    uint64_t count = 0;
+    auto consume = [&](Kmer can, uint64_t h, uint64_t end) {
+        if (count < capacity) {
+            if (h_kmers) {
+                h_kmers[2 * count] = can.lo;
+                h_kmers[2 * count + 1] = can.hi;
+            }
+            if (h_hashes) h_hashes[count] = h;
+            if (h_ends) h_ends[count] = end;
+        }
+        ++count;
+    };
+    reads_front_end_packed(team, reinterpret_cast<const uint32_t *>(h_packed), positions, 0, make_roll_const(k), consume);
+    *n = count;
+    if (count > capacity) return fail("bt_diag_reads_kmers_packed: buffer too small");
     return BT_OK;
 }
 

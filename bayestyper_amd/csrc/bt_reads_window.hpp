@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "bt_kmer_device.hpp"
+#include "bt_reads_pack.hpp"
 
 namespace bt {
 
@@ -66,6 +67,26 @@ __host__ __device__ inline Kmer roll_canonical(const RollState &s, uint64_t *h) 
     return use_rc ? s.rc : s.fw;
 }
 
+// One lane's walk over its run of a tile, as the packed front end calls it: run[i] is the code of position run_start - halo + i.  The first halo steps fill the
+// window; every later step that completes a window of k valid bases ending at or after first_end is consumed.  It restates the walk inside reads_front_end line
+// for line: routing the text front end through this function too changed the text kernels' device code (register allocation and address arithmetic), so that one
+// keeps its walk in place.
+template <unsigned run_len, class Consume>
+__host__ __device__ __attribute__((always_inline)) inline void reads_walk_run(const uint8_t *run, uint64_t run_start, uint64_t len, uint64_t first_end, const RollConst &c, Consume &consume) {
+    const unsigned halo = c.k - 1u;
+    RollState s = roll_start(c);
+    for (unsigned i = 0; i < halo; ++i) roll_step(s, c, run[i]);
+    const uint64_t n = len - run_start < run_len ? len - run_start : run_len;
+    for (uint64_t i = 0; i < n; ++i) {
+        roll_step(s, c, run[halo + i]);
+        if (s.valid == c.k && run_start + i >= first_end) {
+            uint64_t h;
+            const Kmer can = roll_canonical(s, &h);
+            consume(can, h, run_start + i);
+        }
+    }
+}
+
 // The front end.  Team: LANES, RUN (start positions a lane walks per tile), lane(), first_tile(), tile_stride(), codes() (LANES * RUN + READS_MAX_HALO
 // bytes shared by the team), sync().  consume(canonical, hash, end): called once for every window of k valid bases that ENDS at text[end], first_end <= end < len
 // (first_end > 0: the caller has consumed the windows ending before it with an earlier slab that overlaps this one by k - 1 bytes).
@@ -106,10 +127,52 @@ __host__ __device__ inline void reads_front_end(Team &team, const char *__restri
     }
 }
 
+// The sibling over a packed text (bt_reads_pack.hpp): the same walk, another tile fill.  A tile is a whole number of 128-position blocks, so it starts on a
+// block boundary and the halo (k - 1 <= 63) lies in the one block before it: the team's image is laid out from position tile_start - 64, and every
+// 16-position word expands to 16 code bytes (0xFF where invalid or at and beyond `positions`) stored at a 16-byte-aligned address.  Team::codes(): LANES * RUN
+// + READS_PACKED_LEAD bytes, 16-byte aligned.  `packed` holds reads_packed_bytes(positions) bytes; its padding bits are never trusted.
+constexpr unsigned READS_PACKED_LEAD = 64;
+struct alignas(16) CodeBytes16 {
+    uint32_t w[4];
+};
+template <class Team, class Consume>
+__host__ __device__ inline void reads_front_end_packed(Team &team, const uint32_t *__restrict__ packed, uint64_t positions, uint64_t first_end, const RollConst &c, Consume &consume) {
+    constexpr uint64_t TILE = (uint64_t)Team::LANES * Team::RUN;
+    static_assert(TILE % PACK_BLOCK_POSITIONS == 0 && READS_PACKED_LEAD > READS_MAX_HALO && READS_PACKED_LEAD % PACK_WORD_POSITIONS == 0, "a tile is whole blocks");
+    constexpr unsigned LEAD_WORDS = READS_PACKED_LEAD / PACK_WORD_POSITIONS, IMAGE_WORDS = (unsigned)(TILE / PACK_WORD_POSITIONS) + LEAD_WORDS;
+    const unsigned halo = c.k - 1u;
+    uint8_t *codes = team.codes();
+    const uint64_t num_tiles = (positions + TILE - 1) / TILE;
+    for (uint64_t tile = team.first_tile(); tile < num_tiles; tile += team.tile_stride()) {
+        const uint64_t tile_start = tile * TILE, tile_word = tile_start / PACK_WORD_POSITIONS;
+        // codes[j] is the code of position tile_start - 64 + j
+        for (unsigned w = team.lane(); w < IMAGE_WORDS; w += Team::LANES) {
+            CodeBytes16 q;
+            if (tile_word + w < LEAD_WORDS) q.w[0] = q.w[1] = q.w[2] = q.w[3] = 0xFFFFFFFFu;   // before the text
+            else packed_word_code_bytes(packed, tile_word + w - LEAD_WORDS, positions, q.w);
+            *reinterpret_cast<CodeBytes16 *>(codes + (size_t)w * PACK_WORD_POSITIONS) = q;
+        }
+        team.sync();
+        const uint64_t run_start = tile_start + (uint64_t)team.lane() * Team::RUN;
+        if (run_start < positions && run_start + Team::RUN > first_end)
+            reads_walk_run<Team::RUN>(codes + (READS_PACKED_LEAD - halo) + (uint64_t)team.lane() * Team::RUN, run_start, positions, first_end, c, consume);
+        team.sync();
+    }
+}
+
 // a team of one host thread
 struct HostTeam {
     static constexpr unsigned LANES = 1, RUN = 4096;
     uint8_t buf[RUN + READS_MAX_HALO];
+    unsigned lane() const { return 0; }
+    uint64_t first_tile() const { return 0; }
+    uint64_t tile_stride() const { return 1; }
+    uint8_t *codes() { return buf; }
+    void sync() {}
+};
+struct PackedHostTeam {   // RUN: a whole number of 128-position blocks
+    static constexpr unsigned LANES = 1, RUN = 4096;
+    alignas(16) uint8_t buf[RUN + READS_PACKED_LEAD];
     unsigned lane() const { return 0; }
     uint64_t first_tile() const { return 0; }
     uint64_t tile_stride() const { return 1; }

@@ -621,6 +621,7 @@ void KmerCounter::parseSampleKmers(bt_table *table, bt_bloom *path_bloom, Comm *
             check(bt_malloc(ctx, 8, &d_hits), "bt_malloc");
             ReadsTotals totals;
             size_t bam_files = 0, bgzf_fastq_files = 0, gzip_fastq_files = 0;
+            bool from_pack = false;
             try {
                 check(bt_memset(ctx, d_hits, 0, 8), "bt_memset");
                 ReadsSinks sinks;
@@ -632,7 +633,12 @@ void KmerCounter::parseSampleKmers(bt_table *table, bt_bloom *path_bloom, Comm *
                 sinks.device_text = [&](const char *d_text, uint64_t len) {
                     check(bt_reads_count(ctx, path_bloom, table, (uint32_t)s, d_text, len, (uint64_t *)d_hits), "bt_reads_count");
                 };
-                totals = forEachSampleReads(ctx, samples[s].file, kmer_size, threads, (size_t)32 << 20, sinks, &bam_files, &bgzf_fastq_files, &gzip_fastq_files);
+                sinks.host_packed = [&](const uint8_t *packed, uint64_t positions) {   // a section of the sample's reads pack (ReadsPack.hpp)
+                    uint64_t h = 0;
+                    check(bt_reads_count_packed_host(ctx, path_bloom, table, (uint32_t)s, packed, positions, 0, &h), "bt_reads_count_packed_host");
+                    hits += h;
+                };
+                totals = forEachSampleReads(ctx, samples[s].file, kmer_size, threads, (size_t)32 << 20, sinks, &bam_files, &bgzf_fastq_files, &gzip_fastq_files, &from_pack);
                 uint64_t device_hits = 0;
                 check(bt_sync(ctx), "bt_sync");
                 check(bt_memcpy_d2h(ctx, &device_hits, d_hits, 8), "bt_memcpy_d2h");
@@ -645,7 +651,7 @@ void KmerCounter::parseSampleKmers(bt_table *table, bt_bloom *path_bloom, Comm *
             if (bam_files || bgzf_fastq_files || gzip_fastq_files) checkTable(table, "parseSampleKmers");   // (bt_reads_count_host checks the table itself, bt_reads_count does not)
             const double scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan).count();
             std::cout << "[" << getLocalTime() << "] Parsed " << totals.bases << " bases (" << hits << " kmer occurrences passed the path kmer filter)" << std::endl;
-            if (getenv("BT_STAGE_TIMES")) std::cerr << "  parse sample k-mers (reads route): " << samples[s].name << " " << totals.bases << " bases in " << scan_s << " s = " << (double)totals.bases / scan_s << " bases/s" << deviceRouteNote(bam_files, bgzf_fastq_files, gzip_fastq_files) << std::endl;
+            if (getenv("BT_STAGE_TIMES")) std::cerr << "  parse sample k-mers (reads route): " << samples[s].name << " " << totals.bases << " bases in " << scan_s << " s = " << (double)totals.bases / scan_s << " bases/s" << deviceRouteNote(bam_files, bgzf_fastq_files, gzip_fastq_files) << readsPackNote(from_pack) << std::endl;
             continue;
         }
         KmcFile db(samples[s].file);

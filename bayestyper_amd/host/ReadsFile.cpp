@@ -257,4 +257,51 @@ ReadsTotals forEachReadsSlab(const std::vector<std::string> &files, unsigned kme
     return totals;
 }
 
+ReadsTotals forEachReadsSlabCounted(const std::vector<std::string> &files, unsigned kmer_size, unsigned threads, size_t slab_bytes, const SlabPrepare &prepare, const SlabConsume &consume) {
+    ReadsTotals totals;
+    totals.files = files.size();
+    std::atomic<size_t> next_file{0};
+    std::atomic<bool> stop{false};
+    std::mutex device;
+    std::exception_ptr error;
+    auto work = [&]() {
+        try {
+            std::string slab;
+            std::vector<uint8_t> prepared;
+            for (size_t f = next_file++; f < files.size() && !stop; f = next_file++) {
+                ReadsFile file(files[f], kmer_size, slab_bytes);
+                uint64_t slabs = 0, bases = 0, reads = 0;   // bases, reads: handed out with the slabs so far
+                while (!stop && file.next(slab)) {
+                    prepare(slab, prepared);   // without the lock: the other threads' slabs are prepared at the same time
+                    std::lock_guard<std::mutex> lock(device);
+                    if (stop) break;
+                    consume(slab, prepared, file.bases() - bases, file.reads() - reads);
+                    bases = file.bases(), reads = file.reads();
+                    slabs++;
+                }
+                std::lock_guard<std::mutex> lock(device);
+                if (!stop && (file.bases() != bases || file.reads() != reads)) {   // counted after the last slab was handed out: a slab of no positions carries it
+                    slab.clear();
+                    prepared.clear();
+                    consume(slab, prepared, file.bases() - bases, file.reads() - reads);
+                }
+                totals.bases += file.bases();
+                totals.reads += file.reads();
+                totals.slabs += slabs;
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> lock(device);
+            if (!error) error = std::current_exception();
+            stop = true;
+        }
+    };
+    const size_t n = std::max<size_t>(1, std::min<size_t>(threads ? threads : 1, files.size()));
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < n; t++) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    if (error) std::rethrow_exception(error);
+    return totals;
+}
+
 }  // namespace bthost

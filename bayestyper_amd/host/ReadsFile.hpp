@@ -70,5 +70,11 @@ struct ReadsTotals {
 ReadsTotals forEachReadsSlab(const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume);
 // the same over the files given (SampleReads.hpp: the FASTA / FASTQ files of a list that also names BAM files)
 ReadsTotals forEachReadsSlab(const std::vector<std::string> &files, unsigned kmer_size, unsigned threads, size_t slab_bytes, const std::function<void(const std::string &)> &consume);
+// The same for a run that also writes the reads pack (ReadsPack.hpp): prepare(slab, out) is called by the reading thread before it waits for its turn (the
+// slabs of several files are packed at the same time on the -p threads), consume(slab, prepared, bases, reads) by one thread at a time, with the bases and reads
+// the file counted since its previous slab.  What a file counts after its last slab arrives with a slab of no bytes, so the sums equal the totals.
+using SlabPrepare = std::function<void(const std::string &, std::vector<uint8_t> &)>;
+using SlabConsume = std::function<void(const std::string &, const std::vector<uint8_t> &, uint64_t, uint64_t)>;
+ReadsTotals forEachReadsSlabCounted(const std::vector<std::string> &files, unsigned kmer_size, unsigned threads, size_t slab_bytes, const SlabPrepare &prepare, const SlabConsume &consume);
 
 }  // namespace bthost

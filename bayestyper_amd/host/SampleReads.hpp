@@ -3,9 +3,12 @@
 // reaches `device_text`; so does a FASTQ compressed as BGZF (isBgzfFastq; bt_fastq_scan_text), unless BT_FASTQ_BGZF_ON_HOST=1 sends it the old way, and, only
 // with BT_FASTQ_GZIP_ON_DEVICE=1, a FASTQ that is ordinary gzip (isGzipFastq, isBgzfFastq's counterpart for one long member; bt_fastq_gz_scan_text); every other
 // file is read as FASTA / FASTQ on the host (forEachReadsSlab) and reaches `host_slab`, as before BAM was taken.
+// Before any of that the sample's reads pack is looked for (ReadsPack.hpp): when <prefix>.reads.pack is there, whole and made from what this run names, no read
+// file is opened and its sections reach `host_packed`; with BT_READS_PACK=1 a pass over the files that found no such pack writes one as it goes.
 #pragma once
 #include <functional>
 #include <iostream>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -14,13 +17,16 @@
 #include "../../include/btgpu.h"
 #include "BamFile.hpp"
 #include "GzipFile.hpp"
+#include "Options.hpp"
 #include "ReadsFile.hpp"
+#include "ReadsPack.hpp"
 
 namespace bthost {
 
 struct ReadsSinks {
     std::function<void(const std::string &)> host_slab;              // a slab of reads text in host memory
     std::function<void(const char *, uint64_t)> device_text;         // reads text in device memory, valid until the call returns
+    std::function<void(const uint8_t *, uint64_t)> host_packed;      // (bytes, positions): a section of the reads pack in host memory; unset: the pack is not looked for
 };
 
 // for the BT_STAGE_TIMES rows of the reads route: which of the files went through a stream object of the device
@@ -37,12 +43,36 @@ inline std::string deviceRouteNote(size_t bam_files, size_t bgzf_fastq_files, si
 // *bam_files, *bgzf_fastq_files, *gzip_fastq_files (may be NULL): how many of the list's files were BAM files, BGZF-compressed FASTQ files and ordinary gzip
 // FASTQ files read on the device
 inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, unsigned kmer_size, unsigned threads, size_t slab_bytes, const ReadsSinks &sinks,
-                                      size_t *bam_files = nullptr, size_t *bgzf_fastq_files = nullptr, size_t *gzip_fastq_files = nullptr) {
+                                      size_t *bam_files = nullptr, size_t *bgzf_fastq_files = nullptr, size_t *gzip_fastq_files = nullptr, bool *from_pack = nullptr) {
+    if (from_pack) *from_pack = false;
+    if (sinks.host_packed) {
+        if (std::unique_ptr<ReadsPackReader> pack = ReadsPackReader::openFor(prefix, kmer_size)) {
+            if (bam_files) *bam_files = 0;
+            if (bgzf_fastq_files) *bgzf_fastq_files = 0;
+            if (gzip_fastq_files) *gzip_fastq_files = 0;
+            if (from_pack) *from_pack = true;
+            std::cout << "[" << getLocalTime() << "] Reading the reads of " << prefix << ".reads from the reads pack " << pack->path() << std::endl;
+            const ReadsPackTotals t = pack->forEachSection(sinks.host_packed);
+            ReadsTotals totals;
+            totals.bases = t.bases;
+            totals.reads = t.reads;
+            totals.slabs = t.sections;
+            totals.files = readReadsList(prefix).size();   // (the list file; no read file is opened)
+            return totals;
+        }
+    }
     std::vector<std::string> bams, fastqs, gzips, texts;
     const bool fastq_on_host = fastqBgzfOnHost(), gzip_on_device = fastqGzipOnDevice();
     for (const std::string &f : readReadsList(prefix))
         (BamFile::isBam(f) ? bams : !fastq_on_host && isBgzfFastq(f) ? fastqs : gzip_on_device && isGzipFastq(f) ? gzips : texts).push_back(f);
     ReadsTotals totals;
+    // BT_READS_PACK=1 and no pack that serves: this pass writes one (device texts are packed where they are, host slabs on the threads that read them)
+    std::unique_ptr<ReadsPackWriter> writer;
+    if (sinks.host_packed && readsPackWanted()) writer.reset(new ReadsPackWriter(ctx, prefix, kmer_size, !bams.empty()));
+    auto deliverDevice = [&](const char *d_text, uint64_t len, uint64_t bases, uint64_t reads) {
+        if (len) sinks.device_text(d_text, len);
+        if (writer && (len || bases || reads)) writer->addDeviceText(d_text, len, bases, reads);
+    };
     if (bam_files) *bam_files = bams.size();
     if (bgzf_fastq_files) *bgzf_fastq_files = fastqs.size();
     if (gzip_fastq_files) *gzip_fastq_files = gzips.size();
@@ -68,7 +98,7 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
                     uint64_t len = 0;
                     bt_bam_stats stats;
                     check(bt_bam_scan_text(scan, slab.data(), slab.size(), first ? file.skipFirstBytes() : 0, &d_text, &len, &stats), f);
-                    if (len) sinks.device_text(d_text, len);
+                    deliverDevice(d_text, len, stats.bases, stats.kept);
                     totals.bases += stats.bases;
                     totals.reads += stats.kept;
                     totals.slabs++;
@@ -93,7 +123,7 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
             uint64_t len = 0;
             bt_fastq_stats stats;
             auto deliver = [&]() {
-                if (len) sinks.device_text(d_text, len);
+                deliverDevice(d_text, len, stats.bases, stats.reads);
                 totals.bases += stats.bases;
                 totals.reads += stats.reads;
             };
@@ -125,7 +155,7 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
                 uint64_t len = 0;
                 bt_fastq_stats stats;
                 auto deliver = [&]() {
-                    if (len) sinks.device_text(d_text, len);
+                    deliverDevice(d_text, len, stats.bases, stats.reads);
                     totals.bases += stats.bases;
                     totals.reads += stats.reads;
                 };
@@ -145,11 +175,20 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
         }
     }
     if (!texts.empty()) {
-        const ReadsTotals t = forEachReadsSlab(texts, kmer_size, threads, slab_bytes, sinks.host_slab);
+        const ReadsTotals t = !writer ? forEachReadsSlab(texts, kmer_size, threads, slab_bytes, sinks.host_slab)
+                                      : forEachReadsSlabCounted(texts, kmer_size, threads, slab_bytes, ReadsPackWriter::packHost,
+                                                                [&](const std::string &slab, const std::vector<uint8_t> &packed, uint64_t bases, uint64_t reads) {
+                                                                    if (!slab.empty()) sinks.host_slab(slab);
+                                                                    writer->addPacked(packed, slab.size(), bases, reads);
+                                                                });
         totals.bases += t.bases;
         totals.reads += t.reads;
         totals.slabs += t.slabs;
         totals.files += t.files;
+    }
+    if (writer) {
+        writer->finish();
+        std::cout << "[" << getLocalTime() << "] Wrote the reads pack " << readsPackPath(prefix) << std::endl;
     }
     return totals;
 }

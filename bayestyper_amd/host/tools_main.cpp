@@ -47,6 +47,7 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
                 ReadsSinks sinks;
                 sinks.host_slab = [&](const std::string &slab) { check(bt_reads_sketch_host(ctx, slab.data(), slab.size(), kmer_size, 0, registers.data()), "bt_reads_sketch_host"); };
                 sinks.device_text = [&](const char *d_text, uint64_t len) { check(bt_reads_sketch(ctx, d_text, len, kmer_size, (uint8_t *)d_registers), "bt_reads_sketch"); };
+                sinks.host_packed = [&](const uint8_t *packed, uint64_t positions) { check(bt_reads_sketch_packed_host(ctx, packed, positions, kmer_size, 0, registers.data()), "bt_reads_sketch_packed_host"); };
                 forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks);
                 check(bt_sync(ctx), "bt_sync");
                 check(bt_memcpy_d2h(ctx, device_registers.data(), d_registers, registers.size()), "bt_memcpy_d2h");
@@ -67,13 +68,15 @@ int runMakeBloomFromReads(const std::string &prefix, float fpr, uint64_t num_kme
         ReadsSinks sinks;
         sinks.host_slab = [&](const std::string &slab) { check(bt_reads_make_bloom_host(ctx, bloom, slab.data(), slab.size(), kmer_size, 0), "bt_reads_make_bloom_host"); };
         sinks.device_text = [&](const char *d_text, uint64_t len) { check(bt_reads_make_bloom(ctx, bloom, d_text, len, kmer_size), "bt_reads_make_bloom"); };
+        sinks.host_packed = [&](const uint8_t *packed, uint64_t positions) { check(bt_reads_make_bloom_packed_host(ctx, bloom, packed, positions, kmer_size, 0), "bt_reads_make_bloom_packed_host"); };
         size_t bam_files = 0, bgzf_fastq_files = 0, gzip_fastq_files = 0;
+        bool from_pack = false;
         const auto t_scan = std::chrono::steady_clock::now();
-        const ReadsTotals totals = forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks, &bam_files, &bgzf_fastq_files, &gzip_fastq_files);
+        const ReadsTotals totals = forEachSampleReads(ctx, prefix, kmer_size, threads, slab_bytes, sinks, &bam_files, &bgzf_fastq_files, &gzip_fastq_files, &from_pack);
         check(bt_sync(ctx), "bt_sync");
         if (getenv("BT_STAGE_TIMES"))
             std::cerr << "  make bloom (reads route): " << totals.bases << " bases in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scan).count() << " s"
-                      << deviceRouteNote(bam_files, bgzf_fastq_files, gzip_fastq_files) << std::endl;
+                      << deviceRouteNote(bam_files, bgzf_fastq_files, gzip_fastq_files) << readsPackNote(from_pack) << std::endl;
         std::cout << stamp() << "Parsed " << totals.bases << " bases of " << totals.reads << " reads in " << totals.files << " file(s)" << std::endl;
         std::cout << "\n" << stamp() << "Saving bloom filter to " << prefix << " ..." << std::endl;
         check(bt_bloom_save(bloom, prefix.c_str()), "bt_bloom_save");

@@ -789,6 +789,236 @@ def diag_reads_kmers(text, k):
     return kmers[:n.value].copy(), hashes[:n.value].copy(), ends[:n.value].copy()
 
 
+bt_reads_packed_bytes = _sig("bt_reads_packed_bytes", [C.c_uint64], C.c_uint64)
+bt_reads_pack = _sig("bt_reads_pack", [vp, vp, C.c_uint64, vp])
+bt_reads_unpack = _sig("bt_reads_unpack", [vp, vp, C.c_uint64, vp])
+bt_diag_reads_pack = _sig("bt_diag_reads_pack", [vp, C.c_uint64, vp])
+bt_diag_reads_unpack = _sig("bt_diag_reads_unpack", [vp, C.c_uint64, vp])
+bt_reads_count_packed = _sig("bt_reads_count_packed", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp])
+bt_reads_make_bloom_packed = _sig("bt_reads_make_bloom_packed", [vp, vp, vp, C.c_uint64, C.c_uint32])
+bt_reads_sketch_packed = _sig("bt_reads_sketch_packed", [vp, vp, C.c_uint64, C.c_uint32, vp])
+bt_reads_count_packed_host = _sig("bt_reads_count_packed_host", [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, u64p])
+bt_reads_make_bloom_packed_host = _sig("bt_reads_make_bloom_packed_host", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64])
+bt_reads_sketch_packed_host = _sig("bt_reads_sketch_packed_host", [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp])
+bt_diag_reads_kmers_packed = _sig("bt_diag_reads_kmers_packed", [vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, u64p])
+
+
+class ReadsPackInfo(C.Structure):   # include/btgpu.h: bt_reads_pack_info
+    _fields_ = [("version", C.c_uint32), ("k", C.c_uint32), ("block_positions", C.c_uint32), ("manifest_bytes", C.c_uint32), ("sections", C.c_uint64),
+                ("positions", C.c_uint64), ("bases", C.c_uint64), ("reads", C.c_uint64), ("max_section_positions", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+bt_reads_pack_writer_create = _sig("bt_reads_pack_writer_create", [C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(vp)])
+bt_reads_pack_writer_add = _sig("bt_reads_pack_writer_add", [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64])
+bt_reads_pack_writer_finish = _sig("bt_reads_pack_writer_finish", [vp])
+bt_reads_pack_writer_destroy = _sig("bt_reads_pack_writer_destroy", [vp], None)
+bt_reads_pack_reader_open = _sig("bt_reads_pack_reader_open", [C.c_char_p, C.POINTER(vp), C.POINTER(ReadsPackInfo)])
+bt_reads_pack_reader_manifest = _sig("bt_reads_pack_reader_manifest", [vp, vp, C.c_uint64, u64p])
+bt_reads_pack_reader_next = _sig("bt_reads_pack_reader_next", [vp, vp, C.c_uint64, u64p, u64p, u64p, C.POINTER(C.c_int)])
+bt_reads_pack_reader_close = _sig("bt_reads_pack_reader_close", [vp], None)
+bt_reads_pack_file_info = _sig("bt_reads_pack_file_info", [C.c_char_p, C.POINTER(ReadsPackInfo)])
+
+
+def reads_packed_bytes(positions):
+    """bt_reads_packed_bytes: 48 * ceil(positions / 128)"""
+    return int(bt_reads_packed_bytes(positions))
+
+
+def _packed_array(packed, positions):
+    """packed reads (bytes, or a uint8 array) as a contiguous, 4-byte aligned uint8 array of at least reads_packed_bytes(positions) bytes"""
+    a = _reads_text(packed)
+    assert a.size >= reads_packed_bytes(positions), (a.size, positions)
+    if a.ctypes.data & 3:
+        b = np.empty(a.size // 4 + 1, np.uint32).view(np.uint8)[:a.size]
+        b[:] = a
+        a = b
+    return a
+
+
+def diag_reads_pack(text):
+    """bt_diag_reads_pack (no GPU): a reads text -> its packed form, a uint8 array of reads_packed_bytes(len(text)) bytes"""
+    a = _reads_text(text)
+    out = np.zeros(reads_packed_bytes(a.size) // 4, np.uint32).view(np.uint8)
+    check(bt_diag_reads_pack(_np_ptr(a) if a.size else None, a.size, _np_ptr(out) if out.size else None))
+    return out
+
+
+def diag_reads_unpack(packed, positions):
+    """bt_diag_reads_unpack (no GPU): packed reads -> the canonical text (upper-case bases, every invalid position a newline) as bytes"""
+    p = _packed_array(packed, positions)
+    out = np.zeros(positions, np.uint8)
+    check(bt_diag_reads_unpack(_np_ptr(p) if p.size else None, positions, _np_ptr(out) if positions else None))
+    return out.tobytes()
+
+
+def reads_pack(ctx, text, misalign=0):
+    """bt_reads_pack over a host text (uploaded `misalign` bytes into its allocation) -> the packed form as a uint8 array"""
+    a = _reads_text(text)
+    n = reads_packed_bytes(a.size)
+    if not a.size:
+        check(bt_reads_pack(ctx.h, None, 0, None))
+        return np.zeros(0, np.uint8)
+    d_in, d_out = ctx.buffer(a.size + misalign), ctx.buffer(n)
+    try:
+        check(bt_memcpy_h2d(ctx.h, d_in.ptr + misalign, _np_ptr(a), a.size))
+        check(bt_memset(ctx.h, d_out.ptr, 0xA5, n))   # every word of the output is written by the kernel
+        check(bt_reads_pack(ctx.h, d_in.ptr + misalign, a.size, d_out.ptr))
+        ctx.sync()
+        return d_out.download(np.uint8, n)
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+def reads_unpack(ctx, packed, positions, misalign=0):
+    """bt_reads_unpack over a host buffer -> the canonical text as bytes (written `misalign` bytes into its allocation)"""
+    p = _packed_array(packed, positions)
+    if not positions:
+        check(bt_reads_unpack(ctx.h, None, 0, None))
+        return b""
+    d_in, d_out = ctx.to_device(p), ctx.buffer(positions + misalign + 16)
+    try:
+        check(bt_memset(ctx.h, d_out.ptr, 0x23, positions + misalign + 16))
+        check(bt_reads_unpack(ctx.h, d_in.ptr, positions, d_out.ptr + misalign))
+        ctx.sync()
+        whole = d_out.download(np.uint8, positions + misalign + 16)
+        assert (whole[:misalign] == 0x23).all() and (whole[misalign + positions:] == 0x23).all(), "bt_reads_unpack wrote outside its text"
+        return whole[misalign:misalign + positions].tobytes()
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+def reads_count_packed(ctx, bloom, table, sample_idx, packed, positions, host=False, chunk_bytes=0):
+    """bt_reads_count_packed (packed reads uploaded here) or, host=True, bt_reads_count_packed_host -> occurrences that hit the path filter"""
+    p = _packed_array(packed, positions)
+    if host:
+        hits = C.c_uint64()
+        check(bt_reads_count_packed_host(ctx.h, bloom.h, table.h, sample_idx, _np_ptr(p) if p.size else None, positions, chunk_bytes, C.byref(hits)))
+        return hits.value
+    d, h = ctx.to_device(p) if p.size else None, ctx.buffer(8).zero()
+    try:
+        check(bt_reads_count_packed(ctx.h, bloom.h, table.h, sample_idx, d.ptr if d else None, positions, h.ptr))
+        ctx.sync()
+        return int(h.download(np.uint64, 1)[0])
+    finally:
+        h.free()
+        if d:
+            d.free()
+
+
+def reads_make_bloom_packed(ctx, bloom, packed, positions, k, host=False, chunk_bytes=0):
+    """bt_reads_make_bloom_packed / bt_reads_make_bloom_packed_host: the k-mers of the packed reads are added to a sample's filter"""
+    p = _packed_array(packed, positions)
+    if host:
+        check(bt_reads_make_bloom_packed_host(ctx.h, bloom.h, _np_ptr(p) if p.size else None, positions, k, chunk_bytes))
+        return
+    d = ctx.to_device(p) if p.size else None
+    try:
+        check(bt_reads_make_bloom_packed(ctx.h, bloom.h, d.ptr if d else None, positions, k))
+        ctx.sync()
+    finally:
+        if d:
+            d.free()
+
+
+def reads_sketch_packed(ctx, packed, positions, k, registers=None, host=False, chunk_bytes=0):
+    """bt_reads_sketch_packed / bt_reads_sketch_packed_host -> the sketch registers (`registers`: those of earlier texts, merged into)"""
+    p = _packed_array(packed, positions)
+    reg = np.zeros(SKETCH_REGISTERS, np.uint8) if registers is None else np.array(registers, dtype=np.uint8)
+    assert reg.size == SKETCH_REGISTERS
+    if host:
+        check(bt_reads_sketch_packed_host(ctx.h, _np_ptr(p) if p.size else None, positions, k, chunk_bytes, _np_ptr(reg)))
+        return reg
+    d, r = ctx.to_device(p) if p.size else None, ctx.to_device(reg)
+    try:
+        check(bt_reads_sketch_packed(ctx.h, d.ptr if d else None, positions, k, r.ptr))
+        ctx.sync()
+        return r.download(np.uint8, SKETCH_REGISTERS)
+    finally:
+        r.free()
+        if d:
+            d.free()
+
+
+def diag_reads_kmers_packed(packed, positions, k):
+    """bt_diag_reads_kmers_packed (no GPU): diag_reads_kmers over packed reads -> (canonical k-mers (n, 2), hashes (n,), end positions (n,))"""
+    p = _packed_array(packed, positions)
+    cap = max(positions, 1)
+    kmers, hashes, ends = np.zeros((cap, 2), np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    n = C.c_uint64()
+    check(bt_diag_reads_kmers_packed(_np_ptr(p) if p.size else None, positions, k, _np_ptr(kmers), _np_ptr(hashes), _np_ptr(ends), cap, C.byref(n)))
+    return kmers[:n.value].copy(), hashes[:n.value].copy(), ends[:n.value].copy()
+
+
+class ReadsPackWriter:
+    """bt_reads_pack_writer: a reads pack file written section by section; nothing exists under `path` until finish()"""
+
+    def __init__(self, path, k, manifest=""):
+        self.h = vp()
+        check(bt_reads_pack_writer_create(os.fsencode(path), k, manifest.encode(), C.byref(self.h)))
+
+    def add(self, packed, positions, bases, reads):
+        p = _packed_array(packed, positions)
+        check(bt_reads_pack_writer_add(self.h, _np_ptr(p) if p.size else None, positions, bases, reads))
+
+    def finish(self):
+        check(bt_reads_pack_writer_finish(self.h))
+
+    def close(self):
+        if self.h:
+            bt_reads_pack_writer_destroy(self.h)
+            self.h = None
+
+
+class ReadsPackReader:
+    """bt_reads_pack_reader: open() validates the header, the section heads, the trailer and the file's size; sections() reads and checks the payloads"""
+
+    def __init__(self, path):
+        self.h = vp()
+        self._info = ReadsPackInfo()
+        check(bt_reads_pack_reader_open(os.fsencode(path), C.byref(self.h), C.byref(self._info)))
+
+    def info(self):
+        return self._info.as_dict()
+
+    def manifest(self):
+        buf, n = np.zeros(max(self._info.manifest_bytes, 1), np.uint8), C.c_uint64()
+        check(bt_reads_pack_reader_manifest(self.h, _np_ptr(buf), buf.size, C.byref(n)))
+        return buf[:n.value].tobytes().decode()
+
+    def next(self):
+        """-> (packed uint8 array, positions, bases, reads), or None after the last section"""
+        buf = np.zeros(max(reads_packed_bytes(self._info.max_section_positions) // 4, 1), np.uint32).view(np.uint8)
+        positions, bases, reads, end = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+        check(bt_reads_pack_reader_next(self.h, _np_ptr(buf), buf.size, C.byref(positions), C.byref(bases), C.byref(reads), C.byref(end)))
+        if end.value:
+            return None
+        return buf[:reads_packed_bytes(positions.value)], positions.value, bases.value, reads.value
+
+    def sections(self):
+        while True:
+            s = self.next()
+            if s is None:
+                return
+            yield s
+
+    def close(self):
+        if self.h:
+            bt_reads_pack_reader_close(self.h)
+            self.h = None
+
+
+def reads_pack_file_info(path):
+    """bt_reads_pack_file_info (no GPU) -> dict of the header's and the trailer's fields; an error names the defect"""
+    info = ReadsPackInfo()
+    check(bt_reads_pack_file_info(os.fsencode(path), C.byref(info)))
+    return info.as_dict()
+
+
 def kmer_stats_bins(k):
     """bins of the getKmerStats histogram: 256 counts x C(k+3,3) compositions (include/btgpu.h)"""
     return int(bt_kmer_stats_num_bins(k))
