@@ -406,6 +406,14 @@ int bt_diag_inflate_raw(const uint8_t *h_in, uint64_t in_bytes, uint64_t start_b
     return BT_OK;
 }
 
+int bt_diag_gunzip_plausible(const uint8_t *h_in, uint64_t in_bytes, uint64_t first_bit, uint64_t n_bits, uint8_t *h_flags) {
+    if ((in_bytes && !h_in) || (n_bits && !h_flags)) return fail("bt_diag_gunzip_plausible: null argument");
+    if (in_bytes > kMaxIn) return fail("bt_diag_gunzip_plausible: at most " + std::to_string(kMaxIn) + " bytes of input");
+    if (first_bit > 8 * in_bytes || n_bits > 8 * in_bytes - first_bit) return fail("bt_diag_gunzip_plausible: the bit offsets lie behind the input");
+    for (uint64_t i = 0; i < n_bits; ++i) h_flags[i] = plausible_header(h_in, (uint32_t)in_bytes, (uint32_t)(first_bit + i)) ? 1 : 0;
+    return BT_OK;
+}
+
 uint32_t bt_gunzip_default_chunk_bytes(void) { return kDefaultChunk; }
 uint32_t bt_gunzip_expansion_budget(void) { return kExpand; }
 void bt_diag_gunzip_stage_seconds(double *seconds5, int reset) {

@@ -186,7 +186,7 @@ BTD_HD inline void decode_team(Shared &sh, const uint8_t *in, uint32_t n, uint32
                 if (b.cnt < 48) b.refill();
                 const uint32_t s = decode(b, sh.lit, kLitBits, sh.lsym, sh.lcount);
                 if (s == kNoSymbol) {
-                    if (b.cnt < (int32_t)kMaxBits) stop = kStopInput;
+                    if (no_symbol_status(b) == kInputEnd) stop = kStopInput;
                     else stop = kStopError, status = kBadSymbol;
                     break;
                 }
@@ -212,7 +212,7 @@ BTD_HD inline void decode_team(Shared &sh, const uint8_t *in, uint32_t n, uint32
                 const uint32_t len = lc == 28 ? 258 : lc < 8 ? 3 + lc : 3 + ((4 + (lc & 3)) << leb) + b.take(leb);
                 const uint32_t dc = decode(b, sh.dist, kDistBits, sh.dsym, sh.dcount);
                 if (dc == kNoSymbol) {
-                    if (b.cnt < (int32_t)kMaxBits) stop = kStopInput;
+                    if (no_symbol_status(b) == kInputEnd) stop = kStopInput;
                     else stop = kStopError, status = kBadSymbol;
                     break;
                 }

@@ -184,6 +184,10 @@ BTD_HD inline uint32_t decode(Bits &b, const uint16_t *table, uint32_t fast, con
     return kNoSymbol;
 }
 
+// decode() fails only in a set that is not complete: a single code of one bit, or no code at all (build_table accepts no other).  There the first bit alone
+// says that no code follows (zlib's entry for it is one bit long), so a failure with one bit of input in the buffer is damage and not the input's end.
+BTD_HD inline uint32_t no_symbol_status(const Bits &b) { return b.cnt < 1 ? kInputEnd : kBadSymbol; }
+
 // The two decode tables of a fixed (type 1, RFC 1951 3.2.6) or dynamic (type 2, 3.2.7: its header is read from b) block.  The same status on every lane.
 template <class T>
 BTD_HD inline uint32_t block_tables(Shared &sh, Bits &b, uint32_t type) {
@@ -211,7 +215,7 @@ BTD_HD inline uint32_t block_tables(Shared &sh, Bits &b, uint32_t type) {
         for (uint32_t i = 0; i < nlit + ndist;) {
             b.refill();
             const uint32_t s = decode(b, sh.lit, 7, sh.lsym, sh.lcount);
-            if (s == kNoSymbol) return b.cnt < (int32_t)kMaxBits ? kInputEnd : kBadSymbol;
+            if (s == kNoSymbol) return no_symbol_status(b);
             uint32_t rep = 1, v = s;
             if (s == 16) {
                 if (i == 0) return kBadCodeLengths;
@@ -271,7 +275,7 @@ BTD_HD inline uint32_t inflate_stream(Shared &sh, const uint8_t *in, uint32_t n,
         for (;;) {   // a turn takes at most 15 + 5 + 15 + 13 = 48 bits; a refill leaves at least 56 unless the payload ends
             b.refill();
             const uint32_t s = decode(b, sh.lit, kLitBits, sh.lsym, sh.lcount);
-            if (s == kNoSymbol) return b.cnt < (int32_t)kMaxBits ? kInputEnd : kBadSymbol;
+            if (s == kNoSymbol) return no_symbol_status(b);
             if (s < 256) {
                 if (b.cnt < 0) return kInputEnd;
                 if (opos >= isize) return kBadLength;
@@ -287,7 +291,7 @@ BTD_HD inline uint32_t inflate_stream(Shared &sh, const uint8_t *in, uint32_t n,
             const uint32_t lc = s - 257, leb = lc < 8 || lc == 28 ? 0 : (lc >> 2) - 1;
             const uint32_t len = lc == 28 ? 258 : lc < 8 ? 3 + lc : 3 + ((4 + (lc & 3)) << leb) + b.take(leb);
             const uint32_t dc = decode(b, sh.dist, kDistBits, sh.dsym, sh.dcount);
-            if (dc == kNoSymbol) return b.cnt < (int32_t)kMaxBits ? kInputEnd : kBadSymbol;
+            if (dc == kNoSymbol) return no_symbol_status(b);
             if (dc >= 30) return kBadSymbol;
             const uint32_t deb = dc < 4 ? 0 : (dc >> 1) - 1;
             const uint32_t dist = dc < 4 ? 1 + dc : 1 + ((2 + (dc & 1)) << deb) + b.take(deb);

@@ -1715,6 +1715,7 @@ def parse_gunzip_stats(st):
 _raw_args = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(GunzipStats)]
 bt_inflate_raw = _sig("bt_inflate_raw", [vp] + _raw_args)
 bt_diag_inflate_raw = _sig("bt_diag_inflate_raw", _raw_args)
+bt_diag_gunzip_plausible = _sig("bt_diag_gunzip_plausible", [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp])
 bt_gunzip_default_chunk_bytes = _sig("bt_gunzip_default_chunk_bytes", [], C.c_uint32)
 bt_gunzip_expansion_budget = _sig("bt_gunzip_expansion_budget", [], C.c_uint32)
 bt_fastq_gz_scan_create = _sig("bt_fastq_gz_scan_create", [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)])
@@ -1770,6 +1771,18 @@ def inflate_raw(ctx, data, start_bit=0, window=b"", chunk_bytes=0, capacity=None
         d_in.free()
         d_win.free()
         d_out.free()
+
+
+def diag_gunzip_plausible(data, first_bit=0, n_bits=None):
+    """bt_diag_gunzip_plausible (no GPU): the find stage's test at the bit offsets first_bit .. first_bit + n_bits (default: to the data's end) -> uint8 array
+    of 0 / 1"""
+    a = _bytes_array(data)
+    if n_bits is None:
+        n_bits = 8 * a.size - first_bit
+    flags = np.full(max(n_bits, 0) + 16, 0xA5, np.uint8)
+    check(bt_diag_gunzip_plausible(_np_ptr(a) if a.size else None, a.size, first_bit, n_bits, _np_ptr(flags)))
+    assert (flags[n_bits:] == 0xA5).all()
+    return flags[:n_bits].copy()
 
 
 def gunzip_stage_seconds(reset=False):

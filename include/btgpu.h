@@ -1114,6 +1114,9 @@ int bt_inflate_raw(bt_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, uint64_t
  * the same bytes, *end_bit, message and stats, which are functions of the input and the parameters alone. */
 int bt_diag_inflate_raw(const uint8_t *h_in, uint64_t in_bytes, uint64_t start_bit, const uint8_t *h_window, uint64_t window_bytes, uint32_t chunk_bytes, uint8_t *h_out, uint64_t capacity,
                         uint64_t *out_bytes, uint64_t *end_bit, int *stream_end, uint32_t *crc32, bt_gunzip_stats *stats);
+/* The find stage's test alone, on the host (no GPU): h_flags[i] = 1 when a plausible non-final dynamic block header starts at bit first_bit + i of
+ * h_in [in_bytes], else 0, for i < n_bits; first_bit + n_bits <= 8 * in_bytes.  What gunzip_find_kernel asks of every bit offset, for the tests. */
+int bt_diag_gunzip_plausible(const uint8_t *h_in, uint64_t in_bytes, uint64_t first_bit, uint64_t n_bits, uint8_t *h_flags);
 /* What chunk_bytes = 0 stands for, and the symbols of room a candidate's team has per compressed byte of its span. */
 uint32_t bt_gunzip_default_chunk_bytes(void);
 uint32_t bt_gunzip_expansion_budget(void);
