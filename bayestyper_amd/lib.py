@@ -1077,6 +1077,32 @@ bt_diag_nset_replay = _sig("bt_diag_nset_replay", [C.c_uint32, vp, vp, C.c_uint6
 bt_diag_nset_max = _sig("bt_diag_nset_max", [], C.c_uint32)
 bt_diag_rng = _sig("bt_diag_rng", [C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp])
 bt_diag_bulk_bernoulli = _sig("bt_diag_bulk_bernoulli", [C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_int, vp, vp, vp])
+bt_rng_probe = _sig("bt_rng_probe", [vp, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp])
+bt_diag_rng_probe = _sig("bt_diag_rng_probe", [C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp])
+# include/btgpu.h: bt_rng_probe_gen, bt_rng_probe_step, the step kinds and the ring places
+PROBE_GEN = np.dtype([(n, np.uint32) for n in ("seed", "discard", "ring_cap", "ring_place", "step_off", "num_steps", "copies", "reserved")])
+PROBE_STEP = np.dtype([("kind", np.uint32), ("n", np.uint32), ("a", np.float64), ("b", np.float64), ("c", np.float64), ("d", np.float64)])
+(PROBE_DRAW, PROBE_TOPUP, PROBE_REOPEN, PROBE_CANONICAL, PROBE_CANONICAL2, PROBE_UNIFORM_INT, PROBE_BERNOULLI, PROBE_SHUFFLE, PROBE_NORMAL, PROBE_GAMMA, PROBE_BULK,
+ PROBE_DIRECT, PROBE_SCREEN) = range(13)
+PROBE_RING_HBM, PROBE_RING_LDS, PROBE_RING_LDS_FLAT = range(3)
+
+
+def rng_probe(ctx, lane_gen, gens, steps, row_cap):
+    """bt_rng_probe (ctx a Ctx) or its host twin bt_diag_rng_probe (ctx None) -> (rows [cases][64][row_cap], finals [cases][64][12]); the second index is the
+    lane on the device and the generator on the host"""
+    lane_gen = np.ascontiguousarray(lane_gen, np.int32).reshape(-1, 64)
+    gens = np.ascontiguousarray(gens, PROBE_GEN).reshape(-1, 64)
+    steps = np.ascontiguousarray(steps, PROBE_STEP).reshape(-1)
+    n = lane_gen.shape[0]
+    if gens.shape[0] != n:
+        raise ValueError("rng_probe: one generator table per case")
+    rows = np.zeros((n, 64, int(row_cap)), np.uint32)
+    fin = np.zeros((n, 64, 12), np.uint32)
+    args = (n, _np_ptr(lane_gen), _np_ptr(gens), _np_ptr(steps) if steps.size else None, steps.size, int(row_cap), _np_ptr(rows), _np_ptr(fin))
+    check(bt_rng_probe(ctx.h, *args) if ctx is not None else bt_diag_rng_probe(*args))
+    return rows, fin
+
+
 bt_genotype_text_sizes = _sig("bt_genotype_text_sizes", [vp, vp, C.c_uint64, u64p, u64p])
 bt_genotype_text = _sig("bt_genotype_text", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p])
 bt_gibbs_genotype_text = _sig("bt_gibbs_genotype_text", [vp, vp, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u32p])

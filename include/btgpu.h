@@ -902,6 +902,33 @@ int bt_diag_rng(uint32_t seed, int kind, const double *a, const double *b, uint6
  * next block is twisted ahead first where the position allows it.  h_flags [3][n], h_tail [3][8], h_state [2][4] = {position in block, buffer flags, ring head,
  * unread ring words} of forms 0 and 1.  All three must agree. */
 int bt_diag_bulk_bernoulli(uint32_t seed, uint64_t discard, uint32_t n, double p, uint32_t ring_cap, int ahead, uint8_t *h_flags, uint32_t *h_tail, uint32_t *h_state);
+/* A probe of the generator stack itself (csrc/bt_rng_probe.hip; a test harness, no production path launches it).  A CASE is one wavefront: h_lane_gen
+ * [num_cases][64] gives every lane the index of its generator in the case (0 .. 63) or -1 for a lane that leaves the kernel at once; the lanes that share
+ * a generator are its `copies` lockstep copies g0 + k * (64 / copies) and run one program.  h_gens [num_cases][64]: seed (as std::mt19937(seed)), words
+ * discarded first (at most 1 872), ring cap (8, 16, 32, 64), where the ring lies, and the generator's steps h_steps[step_off .. step_off + num_steps).
+ * A step (n <= 2 048 repetitions; a, b, c, d as its kind says) writes its results to the lane's row of row_cap 32-bit words, a double as two words (low, high):
+ *   DRAW n words with next() | TOPUP | REOPEN (mt_close, mt_ring_open) | CANONICAL n doubles | CANONICAL2 n pairs | UNIFORM_INT n draws of range a |
+ *   BERNOULLI n flags of probability a | SHUFFLE of 0 .. n-1 (n <= 448) | NORMAL n draws | GAMMA n draws of shape a, scale b (both with one persistent
+ *   NormalState; c != 0: one raw word after every draw) | BULK n Bernoulli(a) draws through rng_bernoulli_bulk by the generator's team: three words per draw
+ *   {flag, ballot low, ballot high}, written by the lane emit() ran on | DIRECT n words of the direct-form generator of the same seed, a = 1, 2 or 4 at a
+ *   time | SCREEN one call of the gamma second-test screen on u = a, n = b, v = c, a1 = d
+ * and after every step two words {position | buffer flags, ring head | unread words << 16}.  Words no step wrote read 0xFFFFFFFF.  h_final [num_cases][64][12]:
+ * {position, flags, head, unread} after the last step and eight more words of the stream.  A malformed program is an error, never a launch.
+ * bt_diag_rng_probe runs the same interpreter on the host, every held generator once as a team of one: there rows and finals are indexed by GENERATOR. */
+enum { BT_PROBE_DRAW = 0, BT_PROBE_TOPUP, BT_PROBE_REOPEN, BT_PROBE_CANONICAL, BT_PROBE_CANONICAL2, BT_PROBE_UNIFORM_INT, BT_PROBE_BERNOULLI, BT_PROBE_SHUFFLE,
+       BT_PROBE_NORMAL, BT_PROBE_GAMMA, BT_PROBE_BULK, BT_PROBE_DIRECT, BT_PROBE_SCREEN, BT_PROBE_KINDS };
+enum { BT_PROBE_RING_HBM = 0, BT_PROBE_RING_LDS = 1, BT_PROBE_RING_LDS_FLAT = 2 };   /* _LDS: LDS-typed pointer (mt_ring_open_as); _LDS_FLAT: generic pointer into LDS */
+typedef struct bt_rng_probe_gen {
+    uint32_t seed, discard, ring_cap, ring_place, step_off, num_steps, copies, reserved;
+} bt_rng_probe_gen;
+typedef struct bt_rng_probe_step {
+    uint32_t kind, n;
+    double a, b, c, d;
+} bt_rng_probe_step;
+int bt_rng_probe(bt_ctx *ctx, uint32_t num_cases, const int32_t *h_lane_gen, const bt_rng_probe_gen *h_gens, const bt_rng_probe_step *h_steps, uint64_t num_steps, uint32_t row_cap,
+                 uint32_t *h_rows, uint32_t *h_final);
+int bt_diag_rng_probe(uint32_t num_cases, const int32_t *h_lane_gen, const bt_rng_probe_gen *h_gens, const bt_rng_probe_step *h_steps, uint64_t num_steps, uint32_t row_cap,
+                      uint32_t *h_rows, uint32_t *h_final);
 /* Host-side run of the genotype summaries behind bt_gibbs_genotypes for ONE cluster given in host arrays (what bt_gibbs_result_fetch returns for it, entries
  * in that call's order; stats [(s * A_total + allele_base(v) + a) * 12]; ploidy [S] of the cluster's group): h_words receives the string bt_gibbs_genotypes
  * would produce for a launch of this one cluster, *num_words its length (an error when capacity is smaller; *num_words is set first). */

@@ -881,6 +881,19 @@ void orc_rng(unsigned seed, int kind, const double *a, const double *b, uint64_t
         for (size_t i = 0; i < v.size(); i++) v[i] = (uint)i;
         std::shuffle(v.begin(), v.end(), prng);
         for (size_t i = 0; i < v.size(); i++) out[i] = v[i];
+    } else if (kind == 6) {   // normal draws, one raw word after each (out: 2n): the word shows how far every draw moved the stream
+        std::normal_distribution<> nd;
+        for (uint64_t i = 0; i < n; i++) {
+            out[2 * i] = nd(prng);
+            out[2 * i + 1] = (double)prng();
+        }
+    } else if (kind == 7) {   // kind 2 with one raw word after each draw (out: 2n)
+        std::gamma_distribution<> g;
+        for (uint64_t i = 0; i < n; i++) {
+            g.param(std::gamma_distribution<>::param_type(a[i], b[i]));
+            out[2 * i] = g(prng);
+            out[2 * i + 1] = (double)prng();
+        }
     }
 }
 void orc_uset_replay(unsigned universe, const uint8_t *ops, const uint32_t *values, uint64_t num_ops, uint32_t *order, uint32_t *n) {
