@@ -7,30 +7,26 @@
 // Record starts are a dependent chain (each start comes from the previous block_size), and no workgroup may wait on another, so the chain is walked in segments
 // from guessed entries, the guesses are checked in order, and wrong ones walked again (bam_guess_kernel, bam_stitch_kernel, bam_fill_kernel: see there).  Then:
 //   bam_measure_kernel  a thread per record: fields checked, flag & skip_flags judged, l_seq + 1 (0 when skipped) into sizes[], a sum per workgroup
-//   bam_offsets_kernel  one workgroup: exclusive scan over the workgroups' sums, the text's length
-//   bam_emit_kernel     a workgroup per 256 records rebuilds its records' offsets from sizes[]; a wavefront per record, a lane per base: 64 consecutive
-//                       bytes of text per store instruction, 32 consecutive bytes of the packed sequence per load instruction
+// From sizes[] on the work is that of every reads text and is written once, in bt_reads_text.hpp (which bt_fastq.hip shares):
+//   text_offsets_kernel            one workgroup: exclusive scan over the workgroups' sums, the text's length
+//   text_emit_kernel<BamSource>    a workgroup per 256 records rebuilds its records' offsets from sizes[]; a wavefront per record, a lane per base: 64
+//                                  consecutive bytes of text per store instruction, 32 consecutive bytes of the packed sequence per load instruction
 // The first failing record is the one at the smallest offset: a 64-bit atomic minimum over offset << 2 | condition.
 #include <algorithm>
-#include <cstring>
 #include <memory>
 
 #include "bt_bam.hpp"
 #include "bt_bgzf_stream.hpp"
 #include "bt_internal.hpp"
+#include "bt_reads_text.hpp"
 
 using namespace bt;
 using namespace btbam;
 
 namespace {
 
-constexpr uint32_t kTile = 256;
-constexpr unsigned long long kNoError = ~0ull;
-
-struct BamResult {
-    unsigned long long err;   // offset << 2 | condition of the first failing record
-    unsigned long long consumed, text_bytes, kept, skipped, bases;
-    uint32_t n_records, overflow;   // overflow: 1 starts[] too small (never: it is sized for the shortest record), 2 text capacity
+struct BamResult : TextResult {   // err: offset << 2 | condition of the first failing record; overflow 1: starts[] too small (never: it is sized for the shortest record)
+    uint32_t n_records;
 };
 
 // ---- record starts ------------------------------------------------------------------------------------------------------------------------------------------
@@ -156,129 +152,50 @@ __global__ __launch_bounds__(64) void bam_fill_kernel(const uint8_t *__restrict_
     walk_segment(bam, len, entry[s], std::min<uint64_t>(len, (uint64_t)(s + 1) * seg_len), starts + base[s]);
 }
 
-__global__ __launch_bounds__(kTile) void bam_measure_kernel(const uint8_t *__restrict__ bam, uint64_t len, const uint32_t *__restrict__ starts, uint32_t n, uint32_t skip_flags,
+__global__ __launch_bounds__(kTextTile) void bam_measure_kernel(const uint8_t *__restrict__ bam, uint64_t len, const uint32_t *__restrict__ starts, uint32_t n, uint32_t skip_flags,
                                                             uint32_t *__restrict__ sizes, unsigned long long *__restrict__ sums, BamResult *res) {
-    __shared__ unsigned long long s_sum;
-    __shared__ uint32_t s_kept;
-    if (threadIdx.x == 0) s_sum = 0, s_kept = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * kTile + threadIdx.x;
+    const uint32_t i = blockIdx.x * kTextTile + threadIdx.x;
+    uint32_t size = 0;
     if (i < n) {
         const uint64_t at = starts[i];
         Record r;
         const uint32_t e = read_record(bam + at, len - at, r);   // (whole: the walk stored only whole records, of at least kHead bytes)
-        uint32_t size = 0;
         if (e != kRecOk)
             atomicMin(&res->err, (unsigned long long)at << 2 | e);
         else if (!(r.flag & skip_flags))
             size = r.l_seq + 1;
         sizes[i] = size;
-        if (size) {
-            atomicAdd(&s_sum, (unsigned long long)size);
-            atomicAdd(&s_kept, 1u);
-        }
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t in_tile = std::min<uint32_t>(kTile, n - blockIdx.x * kTile);
-        sums[blockIdx.x] = s_sum;
-        if (s_kept) atomicAdd(&res->kept, (unsigned long long)s_kept);
-        if (in_tile - s_kept) atomicAdd(&res->skipped, (unsigned long long)(in_tile - s_kept));
-        if (s_sum) atomicAdd(&res->bases, s_sum - s_kept);
-    }
+    tally_sizes(size, sums, res);
 }
 
-// sums[0..nb) -> exclusive prefix sums in place; the total is the text's length
-__global__ __launch_bounds__(256) void bam_offsets_kernel(unsigned long long *sums, uint32_t nb, BamResult *res) {
-    __shared__ unsigned long long part[256];
-    unsigned long long carry = 0;
-    for (uint32_t base = 0; base < nb; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const unsigned long long v = i < nb ? sums[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 256; d <<= 1) {
-            const unsigned long long o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-            __syncthreads();
-            part[threadIdx.x] += o;
-            __syncthreads();
-        }
-        if (i < nb) sums[i] = carry + part[threadIdx.x] - v;
-        carry += part[255];
-        __syncthreads();
+// text_emit_kernel's view of the records: the packed sequence lies behind the record's name and CIGAR
+struct BamSource {
+    const uint8_t *__restrict__ bam;
+    const uint32_t *__restrict__ starts;
+    __device__ const uint8_t *sequence(uint32_t i) const {
+        const uint8_t *rec = bam + starts[i];
+        return rec + kHead + rec[12] + 4u * rd16(rec + 16);
     }
-    if (threadIdx.x == 0) res->text_bytes = carry;
-}
+    __device__ static uint8_t byte(const uint8_t *seq, uint32_t j) { return base_at(seq, j); }
+};
 
-__global__ __launch_bounds__(kTile) void bam_emit_kernel(const uint8_t *__restrict__ bam, const uint32_t *__restrict__ starts, const uint32_t *__restrict__ sizes,
-                                                         const unsigned long long *__restrict__ sums, uint32_t n, char *__restrict__ text, uint64_t capacity, BamResult *res) {
-    __shared__ uint32_t part[kTile], size_of[kTile];
-    const uint32_t first = blockIdx.x * kTile, i = first + threadIdx.x;
-    const uint32_t v = i < n ? sizes[i] : 0;
-    part[threadIdx.x] = v;
-    size_of[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kTile; d <<= 1) {   // a tile's sizes sum to less than the slab's length: 32 bits
-        const uint32_t o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += o;
-        __syncthreads();
-    }
-    const uint64_t tile_at = sums[blockIdx.x];
-    const uint32_t lane = threadIdx.x & 63u, in_tile = std::min<uint32_t>(kTile, n - first);
-    for (uint32_t r = threadIdx.x >> 6; r < in_tile; r += kTile / 64) {
-        const uint32_t size = size_of[r];
-        if (!size) continue;
-        const uint64_t at = tile_at + part[r] - size;
-        if (at + size > capacity) {   // nothing is written past the capacity
-            if (lane == 0) res->overflow = 2;
-            continue;
-        }
-        const uint8_t *rec = bam + starts[r + first];
-        const uint8_t *seq = rec + kHead + rec[12] + 4u * rd16(rec + 16);
-        const uint32_t l_seq = size - 1;
-        for (uint32_t j = lane; j < l_seq; j += 64) text[at + j] = (char)base_at(seq, j);
-        if (lane == 0) text[at + l_seq] = '\n';
-    }
-}
-
-// device arrays of one conversion: starts and sizes per record, a sum per tile, the result
+// device arrays of one conversion beside those of every reads text: a start per record; the segments' walks
 struct BamWork {
-    uint32_t *d_starts = nullptr, *d_sizes = nullptr;
-    unsigned long long *d_sums = nullptr;
-    BamResult *d_res = nullptr;
+    TextWork<BamResult> text;
+    uint32_t *d_starts = nullptr;
     Seg *d_segs = nullptr;
     unsigned long long *d_entry = nullptr;
     uint32_t *d_base = nullptr;
-    uint64_t cap_records = 0;
+    uint64_t cap_starts = 0, cap_segs = 0, cap_entry = 0, cap_base = 0;   // bytes
     int reserve(uint64_t len) {
-        const uint64_t need = len / kHead + 1;
-        if (!d_res) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_res), sizeof(BamResult)));
-        if (!d_segs) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_segs), kMaxSegs * sizeof(Seg)));
-        if (!d_entry) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_entry), kMaxSegs * 8));
-        if (!d_base) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_base), kMaxSegs * 4));
-        if (need <= cap_records) return BT_OK;
-        release_arrays();
-        const uint64_t cap = need + need / 4;
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_starts), cap * 4));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sizes), cap * 4));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sums), (cap / kTile + 1) * 8));
-        cap_records = cap;
-        return BT_OK;
+        const uint64_t records = len / kHead + 1;
+        if (grow(reinterpret_cast<void **>(&d_segs), &cap_segs, kMaxSegs * sizeof(Seg)) != BT_OK || grow(reinterpret_cast<void **>(&d_entry), &cap_entry, kMaxSegs * 8) != BT_OK ||
+            grow(reinterpret_cast<void **>(&d_base), &cap_base, kMaxSegs * 4) != BT_OK || grow(reinterpret_cast<void **>(&d_starts), &cap_starts, records * 4) != BT_OK)
+            return BT_ERR;
+        return text.reserve(records);
     }
-    void release_arrays() {
-        if (d_starts) (void)hipFree(d_starts);
-        if (d_sizes) (void)hipFree(d_sizes);
-        if (d_sums) (void)hipFree(d_sums);
-        d_starts = d_sizes = nullptr;
-        d_sums = nullptr;
-        cap_records = 0;
-    }
-    ~BamWork() {
-        release_arrays();
-        for (void *p : {(void *)d_res, (void *)d_segs, (void *)d_entry, (void *)d_base})
-            if (p) (void)hipFree(p);
-    }
+    ~BamWork() { release(d_starts, d_segs, d_entry, d_base); }
 };
 
 std::string record_error(uint64_t offset, uint32_t e) { return "BAM record at offset " + std::to_string(offset) + ": " + record_error_text(e); }
@@ -291,41 +208,30 @@ int bam_text_run(const char *who, bt_ctx *ctx, BamWork &w, const uint8_t *d_bam,
     if (len < 4) return BT_OK;
     if (len >= 0xFFFFFFFFull) return fail(std::string(who) + ": at most 4 GiB - 2 of records per call");
     BT_HIP(hipSetDevice(ctx->device));
-    if (w.reserve(len) != BT_OK) return BT_ERR;
     BamResult r;
-    std::memset(&r, 0, sizeof r);
-    r.err = kNoError;
-    BT_HIP(hipMemcpyAsync(w.d_res, &r, sizeof r, hipMemcpyHostToDevice, ctx->stream));
-    BT_HIP(hipStreamSynchronize(ctx->stream));   // (r is pageable: the copy has left it)
+    if (w.reserve(len) != BT_OK || w.text.start(ctx, r) != BT_OK) return BT_ERR;
+    BamResult *d_res = w.text.d_res;
     const uint64_t seg_len = std::max<uint64_t>(kMinSeg, (len + kMaxSegs - 1) / kMaxSegs);
     const uint32_t num_segs = (uint32_t)((len + seg_len - 1) / seg_len);
     hipLaunchKernelGGL(bam_guess_kernel, dim3(num_segs), dim3(64), 0, ctx->stream, d_bam, len, seg_len, w.d_segs);
     BT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bam_stitch_kernel, dim3(1), dim3(256), 0, ctx->stream, d_bam, len, seg_len, num_segs, (const Seg *)w.d_segs, w.d_entry, w.d_base, w.d_res);
+    hipLaunchKernelGGL(bam_stitch_kernel, dim3(1), dim3(256), 0, ctx->stream, d_bam, len, seg_len, num_segs, (const Seg *)w.d_segs, w.d_entry, w.d_base, d_res);
     BT_CHECK_LAUNCH();
     hipLaunchKernelGGL(bam_fill_kernel, dim3((num_segs + 63) / 64), dim3(64), 0, ctx->stream, d_bam, len, seg_len, num_segs, (const unsigned long long *)w.d_entry,
-                       (const uint32_t *)w.d_base, w.d_starts, (uint32_t)std::min<uint64_t>(w.cap_records, 0xFFFFFFFFu), w.d_res);
+                       (const uint32_t *)w.d_base, w.d_starts, (uint32_t)std::min<uint64_t>(w.cap_starts / 4, 0xFFFFFFFFu), d_res);
     BT_CHECK_LAUNCH();
-    BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
-    BT_HIP(hipStreamSynchronize(ctx->stream));
+    if (w.text.fetch(ctx, r) != BT_OK) return BT_ERR;
     if (r.overflow) return fail(std::string(who) + ": more records than the shortest record allows");
-    const uint32_t n = r.n_records, nb = (n + kTile - 1) / kTile;
-    if (n) {
-        hipLaunchKernelGGL(bam_measure_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_bam, len, (const uint32_t *)w.d_starts, n, skip_flags, w.d_sizes, w.d_sums, w.d_res);
-        BT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(bam_offsets_kernel, dim3(1), dim3(256), 0, ctx->stream, w.d_sums, nb, w.d_res);
-        BT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(bam_emit_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_bam, (const uint32_t *)w.d_starts, (const uint32_t *)w.d_sizes, (const unsigned long long *)w.d_sums, n,
-                           d_text, capacity, w.d_res);
-        BT_CHECK_LAUNCH();
-        BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
-        BT_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    const uint32_t n = r.n_records;
+    auto measure = [&](uint32_t nb) {
+        hipLaunchKernelGGL(bam_measure_kernel, dim3(nb), dim3(kTextTile), 0, ctx->stream, d_bam, len, (const uint32_t *)w.d_starts, n, skip_flags, w.text.d_sizes, w.text.d_sums, d_res);
+    };
+    if (text_emit(ctx, w.text, n, measure, BamSource{d_bam, w.d_starts}, d_text, capacity, r) != BT_OK) return BT_ERR;
     if (r.err != kNoError) return fail(record_error(stream_offset + (r.err >> 2), (uint32_t)(r.err & 3u)));
-    if (r.overflow) return fail(std::string(who) + ": capacity " + std::to_string(capacity) + " below the text's " + std::to_string(r.text_bytes) + " bytes");
+    if (r.overflow) return capacity_error(who, capacity, r.text_bytes);
     *text_bytes = r.text_bytes;
     *consumed = r.consumed;
-    if (stats) *stats = bt_bam_stats{r.kept, r.skipped, r.bases};
+    if (stats) *stats = bt_bam_stats{r.kept, n - r.kept, r.bases};
     return BT_OK;
 }
 

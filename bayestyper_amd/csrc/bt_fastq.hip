@@ -10,33 +10,38 @@
 //   fastq_scan_kernel          one workgroup: exclusive scan over the tiles' summaries; the number of lines, the phase the data ends in
 //   fastq_tiles_kernel<true>   the same walk again: every newline stores its position at its line index, with the phase its line is entered in
 //   fastq_measure_kernel       a thread per line: the line judged (judge_line); for the sequence line of a whole record bases + 1 into sizes[], a sum per workgroup
-//   fastq_offsets_kernel       one workgroup: exclusive scan over the workgroups' sums, the text's length
-//   fastq_emit_kernel          a workgroup per 256 lines rebuilds its lines' offsets from sizes[]; a wavefront per read, a lane per base: 64 consecutive bytes
-//                              per load and per store instruction
+// From sizes[] on the work is that of every reads text and is written once, in bt_reads_text.hpp (which bt_bam.hip shares), as is the LDS scan of the kernels above:
+//   text_offsets_kernel            one workgroup: exclusive scan over the workgroups' sums, the text's length
+//   text_emit_kernel<FastqSource>  a workgroup per 256 lines rebuilds its lines' offsets from sizes[]; a wavefront per read, a lane per base: 64 consecutive
+//                                  bytes per load and per store instruction
 // The first violation is the one at the smallest line: a 64-bit atomic minimum over line << 2 | condition.
 #include <algorithm>
-#include <cstring>
 #include <memory>
 
 #include "bt_bgzf_stream.hpp"
 #include "bt_fastq.hpp"
 #include "bt_fastq_stream.hpp"
 #include "bt_internal.hpp"
+#include "bt_reads_text.hpp"
 
 using namespace bt;
 using namespace btfastq;
 
 namespace {
 
-constexpr uint32_t kTile = 256;                            // lines per workgroup of the measure and emit kernels
 constexpr uint32_t kBytesPerThread = 16, kCountTile = 256 * kBytesPerThread;   // bytes per workgroup of the tiles kernels
-constexpr unsigned long long kNoError = ~0ull;
 
-struct FastqResult {
-    unsigned long long err;   // (line index + 1) << 2 | condition of the first violation
-    unsigned long long consumed, text_bytes, reads, bases;
+struct FastqResult : TextResult {   // err: (line index + 1) << 2 | condition of the first violation; kept: the reads
     uint32_t newlines, n_lines, end_phase, open_phase;   // n_lines: newlines + 1 when the data's last line has none and counts; open_phase: the phase that line is entered in
-    uint32_t whole_lines, overflow;                      // whole_lines: lines of whole records and skipped blank lines; overflow: 2 text capacity
+    uint32_t whole_lines;                                // lines of whole records and skipped blank lines
+};
+
+// What a stretch of bytes does to the line finding: its newlines, and their functions composed in byte order
+struct LineSum {
+    uint32_t count, fn;
+};
+struct JoinLines {
+    __device__ LineSum operator()(LineSum earlier, LineSum later) const { return LineSum{earlier.count + later.count, compose(earlier.fn, later.fn)}; }
 };
 
 // The 16 bytes of a thread, and the summary of their newlines.  Bytes at and past len read as 0 (no newline).
@@ -50,7 +55,7 @@ __device__ inline void load_bytes(const uint8_t *__restrict__ data, uint64_t len
 template <bool kStore>
 __global__ __launch_bounds__(256) void fastq_tiles_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t *__restrict__ tile_lines, uint8_t *__restrict__ tile_fn,
                                                           uint32_t *__restrict__ ends, uint8_t *__restrict__ phases, uint32_t n_lines, const FastqResult *__restrict__ res) {
-    __shared__ uint32_t s_count[256], s_fn[256];
+    __shared__ LineSum s[256];
     const uint64_t p = (uint64_t)blockIdx.x * kCountTile + (uint64_t)threadIdx.x * kBytesPerThread;
     uint8_t b[kBytesPerThread];
     uint8_t before1 = 0, before2 = 0;
@@ -69,21 +74,11 @@ __global__ __launch_bounds__(256) void fastq_tiles_kernel(const uint8_t *__restr
             b1 = b[j];
         }
     }
-    s_count[threadIdx.x] = count;
-    s_fn[threadIdx.x] = fn;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {   // inclusive scan: the sums, and the functions composed in byte order
-        const bool has = threadIdx.x >= d;
-        const uint32_t oc = has ? s_count[threadIdx.x - d] : 0, of = has ? s_fn[threadIdx.x - d] : kIdentity;
-        __syncthreads();
-        s_count[threadIdx.x] += oc;
-        s_fn[threadIdx.x] = compose(of, s_fn[threadIdx.x]);
-        __syncthreads();
-    }
+    scan256(s, LineSum{count, fn}, LineSum{0, kIdentity}, JoinLines());
     if (!kStore) {
         if (threadIdx.x == 255) {
-            tile_lines[blockIdx.x] = s_count[255];
-            tile_fn[blockIdx.x] = (uint8_t)s_fn[255];
+            tile_lines[blockIdx.x] = s[255].count;
+            tile_fn[blockIdx.x] = (uint8_t)s[255].fn;
         }
         return;
     }
@@ -92,9 +87,9 @@ __global__ __launch_bounds__(256) void fastq_tiles_kernel(const uint8_t *__restr
         phases[n_lines - 1] = (uint8_t)res->open_phase;
     }
     if (!count) return;
-    uint32_t line = tile_lines[blockIdx.x] + s_count[threadIdx.x] - count;
+    uint32_t line = tile_lines[blockIdx.x] + s[threadIdx.x].count - count;
     uint32_t phase = apply(tile_fn[blockIdx.x], 0);
-    if (threadIdx.x) phase = apply(s_fn[threadIdx.x - 1], phase);
+    if (threadIdx.x) phase = apply(s[threadIdx.x - 1].fn, phase);
     uint8_t b1 = before1, b2 = before2;
     for (uint32_t j = 0; j < kBytesPerThread; ++j) {
         if (b[j] == '\n') {
@@ -112,28 +107,18 @@ __global__ __launch_bounds__(256) void fastq_tiles_kernel(const uint8_t *__restr
 
 // tile_lines[0..nt), tile_fn[0..nt) -> exclusive prefixes in place; the totals into res.  final: the data's last line counts when it has no newline.
 __global__ __launch_bounds__(256) void fastq_scan_kernel(const uint8_t *__restrict__ data, uint64_t len, int final, uint32_t *tile_lines, uint8_t *tile_fn, uint32_t nt, FastqResult *res) {
-    __shared__ uint32_t s_count[256], s_fn[256];
+    __shared__ LineSum s[256];
     uint32_t carry_count = 0, carry_fn = kIdentity;
     for (uint32_t base = 0; base < nt; base += 256) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t c = i < nt ? tile_lines[i] : 0, f = i < nt ? tile_fn[i] : kIdentity;
-        s_count[threadIdx.x] = c;
-        s_fn[threadIdx.x] = f;
-        __syncthreads();
-        for (uint32_t d = 1; d < 256; d <<= 1) {
-            const bool has = threadIdx.x >= d;
-            const uint32_t oc = has ? s_count[threadIdx.x - d] : 0, of = has ? s_fn[threadIdx.x - d] : kIdentity;
-            __syncthreads();
-            s_count[threadIdx.x] += oc;
-            s_fn[threadIdx.x] = compose(of, s_fn[threadIdx.x]);
-            __syncthreads();
-        }
+        scan256(s, LineSum{c, f}, LineSum{0, kIdentity}, JoinLines());
         if (i < nt) {
-            tile_lines[i] = carry_count + s_count[threadIdx.x] - c;
-            tile_fn[i] = (uint8_t)compose(carry_fn, threadIdx.x ? s_fn[threadIdx.x - 1] : kIdentity);
+            tile_lines[i] = carry_count + s[threadIdx.x].count - c;
+            tile_fn[i] = (uint8_t)compose(carry_fn, threadIdx.x ? s[threadIdx.x - 1].fn : kIdentity);
         }
-        carry_count += s_count[255];
-        carry_fn = compose(carry_fn, s_fn[255]);
+        carry_count += s[255].count;
+        carry_fn = compose(carry_fn, s[255].fn);
         __syncthreads();
     }
     if (threadIdx.x == 0) {
@@ -148,13 +133,10 @@ __global__ __launch_bounds__(256) void fastq_scan_kernel(const uint8_t *__restri
     }
 }
 
-__global__ __launch_bounds__(kTile) void fastq_measure_kernel(const uint8_t *__restrict__ data, uint64_t len, const uint32_t *__restrict__ ends, const uint8_t *__restrict__ phases,
-                                                              uint32_t *__restrict__ sizes, unsigned long long *__restrict__ sums, FastqResult *res) {
-    __shared__ unsigned long long s_sum;
-    __shared__ uint32_t s_reads;
-    if (threadIdx.x == 0) s_sum = 0, s_reads = 0;
-    __syncthreads();
-    const uint32_t n = res->n_lines, whole = res->whole_lines, i = blockIdx.x * kTile + threadIdx.x;
+__global__ __launch_bounds__(kTextTile) void fastq_measure_kernel(const uint8_t *__restrict__ data, uint64_t len, const uint32_t *__restrict__ ends, const uint8_t *__restrict__ phases,
+                                                                  uint32_t *__restrict__ sizes, unsigned long long *__restrict__ sums, FastqResult *res) {
+    const uint32_t n = res->n_lines, whole = res->whole_lines, i = blockIdx.x * kTextTile + threadIdx.x;
+    uint32_t size = 0;
     if (i < n) {
         const uint64_t start = i ? (uint64_t)ends[i - 1] + 1 : 0, end = ends[i];
         const uint32_t phase = phases[i];
@@ -163,115 +145,36 @@ __global__ __launch_bounds__(kTile) void fastq_measure_kernel(const uint8_t *__r
         if (phase == 3 && i >= 2) seq_start = i >= 3 ? (uint64_t)ends[i - 3] + 1 : 0, seq_end = ends[i - 2];
         const Line l = judge_line(data, start, end, phase, i + 1 == n && n > res->newlines, seq_start, seq_end);
         if (l.verdict != kLineOk) atomicMin(&res->err, ((unsigned long long)i + 1) << 2 | l.verdict);
-        const uint32_t size = l.bases && i < whole ? l.bases + 1 : 0;
+        size = l.bases && i < whole ? l.bases + 1 : 0;
         sizes[i] = size;
-        if (size) {
-            atomicAdd(&s_sum, (unsigned long long)size);
-            atomicAdd(&s_reads, 1u);
-        }
         if (i + 1 == whole) res->consumed = std::min<uint64_t>(end + 1, len);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = s_sum;
-        if (s_reads) {
-            atomicAdd(&res->reads, (unsigned long long)s_reads);
-            atomicAdd(&res->bases, s_sum - s_reads);
-        }
-    }
+    tally_sizes(size, sums, res);
 }
 
-// sums[0..nb) -> exclusive prefix sums in place; the total is the text's length
-__global__ __launch_bounds__(256) void fastq_offsets_kernel(unsigned long long *sums, uint32_t nb, FastqResult *res) {
-    __shared__ unsigned long long part[256];
-    unsigned long long carry = 0;
-    for (uint32_t base = 0; base < nb; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const unsigned long long v = i < nb ? sums[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 256; d <<= 1) {
-            const unsigned long long o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-            __syncthreads();
-            part[threadIdx.x] += o;
-            __syncthreads();
-        }
-        if (i < nb) sums[i] = carry + part[threadIdx.x] - v;
-        carry += part[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) res->text_bytes = carry;
-}
+// text_emit_kernel's view of the lines: a line starts behind the end of the line before it, and its bytes are the text's
+struct FastqSource {
+    const uint8_t *__restrict__ data;
+    const uint32_t *__restrict__ ends;
+    __device__ const uint8_t *sequence(uint32_t line) const { return data + (line ? (uint64_t)ends[line - 1] + 1 : 0); }   // (a sequence line is never the data's first line)
+    __device__ static uint8_t byte(const uint8_t *seq, uint32_t j) { return seq[j]; }
+};
 
-__global__ __launch_bounds__(kTile) void fastq_emit_kernel(const uint8_t *__restrict__ data, const uint32_t *__restrict__ ends, const uint32_t *__restrict__ sizes,
-                                                           const unsigned long long *__restrict__ sums, uint32_t n, char *__restrict__ text, uint64_t capacity, FastqResult *res) {
-    __shared__ uint32_t part[kTile], size_of[kTile];
-    const uint32_t first = blockIdx.x * kTile, i = first + threadIdx.x;
-    const uint32_t v = i < n ? sizes[i] : 0;
-    part[threadIdx.x] = v;
-    size_of[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kTile; d <<= 1) {   // a tile's sizes sum to less than the data's length: 32 bits
-        const uint32_t o = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += o;
-        __syncthreads();
-    }
-    const uint64_t tile_at = sums[blockIdx.x];
-    const uint32_t lane = threadIdx.x & 63u, in_tile = std::min<uint32_t>(kTile, n - first);
-    for (uint32_t r = threadIdx.x >> 6; r < in_tile; r += kTile / 64) {
-        const uint32_t size = size_of[r];
-        if (!size) continue;
-        const uint64_t at = tile_at + part[r] - size;
-        if (at + size > capacity) {   // nothing is written past the capacity
-            if (lane == 0) res->overflow = 2;
-            continue;
-        }
-        const uint32_t line = first + r;   // (a sequence line is never the data's first line)
-        const uint8_t *seq = data + (line ? (uint64_t)ends[line - 1] + 1 : 0);
-        const uint32_t bases = size - 1;
-        for (uint32_t j = lane; j < bases; j += 64) text[at + j] = (char)seq[j];
-        if (lane == 0) text[at + bases] = '\n';
-    }
-}
-
-// device arrays of one conversion: a count and a function per tile of bytes; an end, a phase and a size per line; a sum per 256 lines; the result
+// device arrays of one conversion beside those of every reads text: a count and a function per tile of bytes; an end and a phase per line
 struct FastqWork {
-    uint32_t *d_tile_lines = nullptr, *d_ends = nullptr, *d_sizes = nullptr;
+    TextWork<FastqResult> text;
+    uint32_t *d_tile_lines = nullptr, *d_ends = nullptr;
     uint8_t *d_tile_fn = nullptr, *d_phases = nullptr;
-    unsigned long long *d_sums = nullptr;
-    FastqResult *d_res = nullptr;
-    uint64_t cap_tiles = 0, cap_lines = 0;
+    uint64_t cap_tile_lines = 0, cap_tile_fn = 0, cap_ends = 0, cap_phases = 0;   // bytes
     int reserve_tiles(uint64_t tiles) {
-        if (!d_res) BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_res), sizeof(FastqResult)));
-        if (tiles <= cap_tiles) return BT_OK;
-        release(d_tile_lines, d_tile_fn);
-        cap_tiles = 0;
-        const uint64_t cap = tiles + tiles / 4 + 16;
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_tile_lines), cap * 4));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_tile_fn), cap));
-        cap_tiles = cap;
-        return BT_OK;
+        if (grow(reinterpret_cast<void **>(&d_tile_lines), &cap_tile_lines, tiles * 4) != BT_OK) return BT_ERR;
+        return grow(reinterpret_cast<void **>(&d_tile_fn), &cap_tile_fn, tiles);
     }
     int reserve_lines(uint64_t lines) {
-        if (lines <= cap_lines) return BT_OK;
-        release(d_ends, d_sizes, d_phases, d_sums);
-        cap_lines = 0;
-        const uint64_t cap = lines + lines / 4 + 16;
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_ends), cap * 4));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sizes), cap * 4));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_phases), cap));
-        BT_HIP(hipMalloc(reinterpret_cast<void **>(&d_sums), (cap / kTile + 1) * 8));
-        cap_lines = cap;
-        return BT_OK;
+        if (grow(reinterpret_cast<void **>(&d_ends), &cap_ends, lines * 4) != BT_OK || grow(reinterpret_cast<void **>(&d_phases), &cap_phases, lines) != BT_OK) return BT_ERR;
+        return text.reserve(lines);
     }
-    template <typename... P>
-    static void release(P *&...p) {
-        for (void *q : {(void *)p...})
-            if (q) (void)hipFree(q);
-        ((p = nullptr), ...);
-    }
-    ~FastqWork() { release(d_tile_lines, d_tile_fn, d_ends, d_sizes, d_phases, d_sums, d_res); }
+    ~FastqWork() { release(d_tile_lines, d_tile_fn, d_ends, d_phases); }
 };
 
 // the bases and quality values of the record whose quality line is line `i` (0-based), for the message: read back from the device
@@ -305,34 +208,25 @@ int fastq_text_run(const char *who, bt_ctx *ctx, FastqWork &w, const uint8_t *d_
     if (len >= 0xFFFFFFFFull) return fail(std::string(who) + ": at most 4 GiB - 2 of text per call");
     BT_HIP(hipSetDevice(ctx->device));
     const uint32_t nt = (uint32_t)((len + kCountTile - 1) / kCountTile);
-    if (w.reserve_tiles(nt) != BT_OK) return BT_ERR;
     FastqResult r;
-    std::memset(&r, 0, sizeof r);
-    r.err = kNoError;
-    BT_HIP(hipMemcpyAsync(w.d_res, &r, sizeof r, hipMemcpyHostToDevice, ctx->stream));
-    BT_HIP(hipStreamSynchronize(ctx->stream));   // (r is pageable: the copy has left it)
+    if (w.reserve_tiles(nt) != BT_OK || w.text.start(ctx, r) != BT_OK) return BT_ERR;
+    FastqResult *d_res = w.text.d_res;
     hipLaunchKernelGGL(fastq_tiles_kernel<false>, dim3(nt), dim3(256), 0, ctx->stream, d_data, len, w.d_tile_lines, w.d_tile_fn, (uint32_t *)nullptr, (uint8_t *)nullptr, 0u,
-                       (const FastqResult *)w.d_res);
+                       (const FastqResult *)d_res);
     BT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fastq_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, d_data, len, final, w.d_tile_lines, w.d_tile_fn, nt, w.d_res);
+    hipLaunchKernelGGL(fastq_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, d_data, len, final, w.d_tile_lines, w.d_tile_fn, nt, d_res);
     BT_CHECK_LAUNCH();
-    BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
-    BT_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t n = r.n_lines, nb = (n + kTile - 1) / kTile;
+    if (w.text.fetch(ctx, r) != BT_OK) return BT_ERR;
+    const uint32_t n = r.n_lines;
     if (n) {
         if (w.reserve_lines(n) != BT_OK) return BT_ERR;
-        hipLaunchKernelGGL(fastq_tiles_kernel<true>, dim3(nt), dim3(256), 0, ctx->stream, d_data, len, w.d_tile_lines, w.d_tile_fn, w.d_ends, w.d_phases, n, (const FastqResult *)w.d_res);
+        hipLaunchKernelGGL(fastq_tiles_kernel<true>, dim3(nt), dim3(256), 0, ctx->stream, d_data, len, w.d_tile_lines, w.d_tile_fn, w.d_ends, w.d_phases, n, (const FastqResult *)d_res);
         BT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(fastq_measure_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_data, len, (const uint32_t *)w.d_ends, (const uint8_t *)w.d_phases, w.d_sizes, w.d_sums, w.d_res);
-        BT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(fastq_offsets_kernel, dim3(1), dim3(256), 0, ctx->stream, w.d_sums, nb, w.d_res);
-        BT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(fastq_emit_kernel, dim3(nb), dim3(kTile), 0, ctx->stream, d_data, (const uint32_t *)w.d_ends, (const uint32_t *)w.d_sizes, (const unsigned long long *)w.d_sums, n,
-                           d_text, capacity, w.d_res);
-        BT_CHECK_LAUNCH();
-        BT_HIP(hipMemcpyAsync(&r, w.d_res, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
-        BT_HIP(hipStreamSynchronize(ctx->stream));
     }
+    auto measure = [&](uint32_t nb) {
+        hipLaunchKernelGGL(fastq_measure_kernel, dim3(nb), dim3(kTextTile), 0, ctx->stream, d_data, len, (const uint32_t *)w.d_ends, (const uint8_t *)w.d_phases, w.text.d_sizes, w.text.d_sums, d_res);
+    };
+    if (text_emit(ctx, w.text, n, measure, FastqSource{d_data, w.d_ends}, d_text, capacity, r) != BT_OK) return BT_ERR;
     if (r.err != kNoError) {
         const uint64_t line = (r.err >> 2) - 1;
         const uint32_t verdict = (uint32_t)(r.err & 3u);
@@ -341,10 +235,10 @@ int fastq_text_run(const char *who, bt_ctx *ctx, FastqWork &w, const uint8_t *d_
         return fail(error_text(verdict, first_line + line, bases, quals, 0));
     }
     if (final && r.end_phase) return fail(error_text(kTruncated, 0, 0, 0, r.end_phase));
-    if (r.overflow) return fail(std::string(who) + ": capacity " + std::to_string(capacity) + " below the text's " + std::to_string(r.text_bytes) + " bytes");
+    if (r.overflow) return capacity_error(who, capacity, r.text_bytes);
     *text_bytes = r.text_bytes;
     *consumed = r.consumed;
-    if (stats) *stats = bt_fastq_stats{r.reads, r.bases, r.whole_lines};
+    if (stats) *stats = bt_fastq_stats{r.kept, r.bases, r.whole_lines};
     return BT_OK;
 }
 

@@ -38,6 +38,35 @@ inline std::string deviceRouteNote(size_t bam_files, size_t bgzf_fastq_files, si
     return note;
 }
 
+// what a call of a stream object leaves: reads text in device memory (valid until the object's next call), and the bases and reads it holds
+struct DeviceText {
+    const char *text = nullptr;
+    uint64_t len = 0, bases = 0, reads = 0;
+};
+
+// One read file through a stream object of the device, slab by slab.  create(&scan), text(scan, slab, first, out) and finish(scan, out) return the library's
+// status and fill `out`, which `deliver` takes; the scan is destroyed on every path.  totals.slabs counts the calls of `text`, totals.files the files.
+template <typename Scan, typename File, typename Create, typename Text, typename Finish, typename Deliver>
+void scanOnDevice(File &file, const std::string &f, Create create, Text text, Finish finish, void (*destroy)(Scan *), Deliver deliver, ReadsTotals &totals) {
+    auto check = [&](int rc) {
+        if (rc != BT_OK) throw std::runtime_error("read file " + f + ": " + bt_last_error());
+    };
+    Scan *created = nullptr;
+    check(create(&created));
+    std::unique_ptr<Scan, void (*)(Scan *)> scan(created, destroy);
+    std::vector<uint8_t> slab;
+    for (bool first = true; file.next(slab); first = false) {
+        DeviceText out;
+        check(text(scan.get(), slab, first, out));
+        deliver(out);
+        totals.slabs++;
+    }
+    DeviceText out;
+    check(finish(scan.get(), out));
+    deliver(out);
+    totals.files++;
+}
+
 // ReadsTotals of a BAM file: bases and reads of the kept records (flag & skip_flags == 0), slabs = calls of bt_bam_scan_text; of a BGZF FASTQ file: bases and
 // reads of the records with at least one base, slabs = calls of bt_fastq_scan_text; of a gzip FASTQ file the same, slabs = calls of bt_fastq_gz_scan_text
 // *bam_files, *bgzf_fastq_files, *gzip_fastq_files (may be NULL): how many of the list's files were BAM files, BGZF-compressed FASTQ files and ordinary gzip
@@ -69,77 +98,59 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
     // BT_READS_PACK=1 and no pack that serves: this pass writes one (device texts are packed where they are, host slabs on the threads that read them)
     std::unique_ptr<ReadsPackWriter> writer;
     if (sinks.host_packed && readsPackWanted()) writer.reset(new ReadsPackWriter(ctx, prefix, kmer_size, !bams.empty()));
-    auto deliverDevice = [&](const char *d_text, uint64_t len, uint64_t bases, uint64_t reads) {
-        if (len) sinks.device_text(d_text, len);
-        if (writer && (len || bases || reads)) writer->addDeviceText(d_text, len, bases, reads);
+    auto deliver = [&](const DeviceText &t) {
+        if (t.len) sinks.device_text(t.text, t.len);
+        if (writer && (t.len || t.bases || t.reads)) writer->addDeviceText(t.text, t.len, t.bases, t.reads);
+        totals.bases += t.bases;
+        totals.reads += t.reads;
     };
     if (bam_files) *bam_files = bams.size();
     if (bgzf_fastq_files) *bgzf_fastq_files = fastqs.size();
     if (gzip_fastq_files) *gzip_fastq_files = gzips.size();
     const size_t bgzf_slab = std::max<size_t>(slab_bytes / 2, 65536);   // compressed bytes: about a quarter of the text they hold
-    auto check = [](int rc, const std::string &file) {
-        if (rc != BT_OK) throw std::runtime_error("read file " + file + ": " + bt_last_error());
-    };
     auto warnNoEof = [](const BgzfFile &file, const std::string &f) {
         static std::set<std::string> warned;   // once per file and process: makeBloom -r reads a file in two passes
         if (!file.hasEofBlock() && warned.insert(f).second) std::cerr << "WARNING: read file " << f << " has no BGZF end-of-file block: it may be truncated" << std::endl;
     };
+    // the two FASTQ stream objects take a slab and finish alike (the file's last record comes from finish when its last line has no newline)
+    auto fastqText = [](auto scan_text) {
+        return [scan_text](auto *scan, const std::vector<uint8_t> &slab, bool, DeviceText &out) {
+            bt_fastq_stats stats;
+            const int rc = scan_text(scan, slab.data(), slab.size(), &out.text, &out.len, &stats);
+            out.bases = stats.bases, out.reads = stats.reads;
+            return rc;
+        };
+    };
+    auto fastqFinish = [](auto scan_finish) {
+        return [scan_finish](auto *scan, DeviceText &out) {
+            bt_fastq_stats stats;
+            const int rc = scan_finish(scan, &out.text, &out.len, &stats);
+            out.bases = stats.bases, out.reads = stats.reads;
+            return rc;
+        };
+    };
     if (!bams.empty()) {
         const uint32_t skip_flags = bamSkipFlags();
-        bt_bam_scan *scan = nullptr;
         for (const std::string &f : bams) {
             BamFile file(f, bgzf_slab);
             warnNoEof(file, f);
-            check(bt_bam_scan_create(ctx, bgzf_slab, skip_flags, &scan), f);
-            try {
-                std::vector<uint8_t> slab;
-                for (bool first = true; file.next(slab); first = false) {
-                    const char *d_text = nullptr;
-                    uint64_t len = 0;
+            scanOnDevice<bt_bam_scan>(
+                file, f, [&](bt_bam_scan **scan) { return bt_bam_scan_create(ctx, bgzf_slab, skip_flags, scan); },
+                [&](bt_bam_scan *scan, const std::vector<uint8_t> &slab, bool first, DeviceText &out) {
                     bt_bam_stats stats;
-                    check(bt_bam_scan_text(scan, slab.data(), slab.size(), first ? file.skipFirstBytes() : 0, &d_text, &len, &stats), f);
-                    deliverDevice(d_text, len, stats.bases, stats.kept);
-                    totals.bases += stats.bases;
-                    totals.reads += stats.kept;
-                    totals.slabs++;
-                }
-                check(bt_bam_scan_finish(scan), f);
-            } catch (...) {
-                bt_bam_scan_destroy(scan);
-                throw;
-            }
-            bt_bam_scan_destroy(scan);
-            totals.files++;
+                    const int rc = bt_bam_scan_text(scan, slab.data(), slab.size(), first ? file.skipFirstBytes() : 0, &out.text, &out.len, &stats);
+                    out.bases = stats.bases, out.reads = stats.kept;
+                    return rc;
+                },
+                [](bt_bam_scan *scan, DeviceText &) { return bt_bam_scan_finish(scan); }, bt_bam_scan_destroy, deliver, totals);
         }
     }
     for (const std::string &f : fastqs) {
         BgzfFastqFile file(f, bgzf_slab);
         warnNoEof(file, f);
-        bt_fastq_scan *scan = nullptr;
-        check(bt_fastq_scan_create(ctx, bgzf_slab, &scan), f);
-        try {
-            std::vector<uint8_t> slab;
-            const char *d_text = nullptr;
-            uint64_t len = 0;
-            bt_fastq_stats stats;
-            auto deliver = [&]() {
-                deliverDevice(d_text, len, stats.bases, stats.reads);
-                totals.bases += stats.bases;
-                totals.reads += stats.reads;
-            };
-            while (file.next(slab)) {
-                check(bt_fastq_scan_text(scan, slab.data(), slab.size(), &d_text, &len, &stats), f);
-                deliver();
-                totals.slabs++;
-            }
-            check(bt_fastq_scan_finish(scan, &d_text, &len, &stats), f);   // the file's last record, when its last line has no newline
-            deliver();
-        } catch (...) {
-            bt_fastq_scan_destroy(scan);
-            throw;
-        }
-        bt_fastq_scan_destroy(scan);
-        totals.files++;
+        scanOnDevice<bt_fastq_scan>(
+            file, f, [&](bt_fastq_scan **scan) { return bt_fastq_scan_create(ctx, bgzf_slab, scan); }, fastqText(bt_fastq_scan_text), fastqFinish(bt_fastq_scan_finish),
+            bt_fastq_scan_destroy, deliver, totals);
     }
     if (!gzips.empty()) {
         // compressed bytes per call: a block is a team's work, and some thousands of teams fill the device; the stream object's buffers take about 60 times as much
@@ -147,31 +158,9 @@ inline ReadsTotals forEachSampleReads(bt_ctx *ctx, const std::string &prefix, un
         const uint32_t chunk_bytes = gunzipChunkBytes();
         for (const std::string &f : gzips) {
             GzipFastqFile file(f, gzip_slab);
-            bt_fastq_gz_scan *scan = nullptr;
-            check(bt_fastq_gz_scan_create(ctx, gzip_slab, chunk_bytes, &scan), f);
-            try {
-                std::vector<uint8_t> slab;
-                const char *d_text = nullptr;
-                uint64_t len = 0;
-                bt_fastq_stats stats;
-                auto deliver = [&]() {
-                    deliverDevice(d_text, len, stats.bases, stats.reads);
-                    totals.bases += stats.bases;
-                    totals.reads += stats.reads;
-                };
-                while (file.next(slab)) {
-                    check(bt_fastq_gz_scan_text(scan, slab.data(), slab.size(), &d_text, &len, &stats), f);
-                    deliver();
-                    totals.slabs++;
-                }
-                check(bt_fastq_gz_scan_finish(scan, &d_text, &len, &stats), f);   // the file ends at a member boundary; its last record, when its last line has no newline
-                deliver();
-            } catch (...) {
-                bt_fastq_gz_scan_destroy(scan);
-                throw;
-            }
-            bt_fastq_gz_scan_destroy(scan);
-            totals.files++;
+            scanOnDevice<bt_fastq_gz_scan>(
+                file, f, [&](bt_fastq_gz_scan **scan) { return bt_fastq_gz_scan_create(ctx, gzip_slab, chunk_bytes, scan); }, fastqText(bt_fastq_gz_scan_text),
+                fastqFinish(bt_fastq_gz_scan_finish), bt_fastq_gz_scan_destroy, deliver, totals);   // (the file has to end at a member boundary: finish says so)
         }
     }
     if (!texts.empty()) {

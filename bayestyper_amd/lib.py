@@ -1597,8 +1597,50 @@ def bam_reads_text(ctx, bam, skip_flags=BAM_SKIP_FLAGS, capacity=None, misalign=
         d_out.free()
 
 
-class BamScan:
+class _Scan:
+    """What the stream-object wrappers share: a call's text downloaded, and the handle's end.  A subclass creates self.h and names its library's destroy function in
+    _destroy."""
+
+    def _download(self, d, n, st):
+        out = np.empty(n, np.uint8)
+        if n:
+            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
+        return out.tobytes(), st
+
+    def text_bytes(self, *args, **kw):
+        """text(), downloaded -> (bytes, stats)"""
+        return self._download(*self.text(*args, **kw))
+
+    def close(self):
+        if self.h:
+            self._destroy(self.h)
+            self.h = None
+
+
+class _FastqScan(_Scan):
+    """The two FASTQ stream objects: the same calls over the functions the subclass names in _text and _finish."""
+
+    def text(self, data):
+        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
+        a = _bytes_array(data)
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(self._text(self.h, _np_ptr(a) if a.size else None, a.size, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def finish(self):
+        """the carried tail as the file's end -> (device pointer of its text, its length, stats)"""
+        d, n, st = vp(), C.c_uint64(), FastqStats()
+        check(self._finish(self.h, C.byref(d), C.byref(n), C.byref(st)))
+        return d.value, n.value, st.as_dict()
+
+    def finish_bytes(self):
+        """finish(), downloaded -> (bytes, stats)"""
+        return self._download(*self.finish())
+
+
+class BamScan(_Scan):
     """bt_bam_scan: slabs of whole BGZF blocks of a BAM file -> reads text in device memory"""
+    _destroy = bt_bam_scan_destroy
 
     def __init__(self, ctx, max_in_bytes, skip_flags=BAM_SKIP_FLAGS):
         self.ctx = ctx
@@ -1613,21 +1655,8 @@ class BamScan:
         check(bt_bam_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, skip_first_bytes, C.byref(d), C.byref(n), C.byref(st)))
         return d.value, n.value, st.as_dict()
 
-    def text_bytes(self, blocks, skip_first_bytes=0):
-        """text(), downloaded -> (bytes, stats)"""
-        d, n, st = self.text(blocks, skip_first_bytes)
-        out = np.empty(n, np.uint8)
-        if n:
-            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
-        return out.tobytes(), st
-
     def finish(self):
         check(bt_bam_scan_finish(self.h))
-
-    def close(self):
-        if self.h:
-            bt_bam_scan_destroy(self.h)
-            self.h = None
 
 
 class FastqStats(C.Structure):   # include/btgpu.h: bt_fastq_stats
@@ -1686,46 +1715,15 @@ def fastq_reads_text(ctx, fastq, final=True, first_line=1, capacity=None, misali
         d_out.free()
 
 
-class FastqScan:
+class FastqScan(_FastqScan):
     """bt_fastq_scan: slabs of whole BGZF blocks of a BGZF-compressed FASTQ file -> reads text in device memory"""
+    _text, _finish, _destroy = bt_fastq_scan_text, bt_fastq_scan_finish, bt_fastq_scan_destroy
 
     def __init__(self, ctx, max_in_bytes):
         self.ctx = ctx
         h = vp()
         check(bt_fastq_scan_create(ctx.h, max_in_bytes, C.byref(h)))
         self.h = h.value
-
-    def text(self, blocks):
-        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
-        a = _bytes_array(blocks)
-        d, n, st = vp(), C.c_uint64(), FastqStats()
-        check(bt_fastq_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, C.byref(d), C.byref(n), C.byref(st)))
-        return d.value, n.value, st.as_dict()
-
-    def finish(self):
-        """the carried tail as the file's end -> (device pointer of its text, its length, stats)"""
-        d, n, st = vp(), C.c_uint64(), FastqStats()
-        check(bt_fastq_scan_finish(self.h, C.byref(d), C.byref(n), C.byref(st)))
-        return d.value, n.value, st.as_dict()
-
-    def _download(self, d, n, st):
-        out = np.empty(n, np.uint8)
-        if n:
-            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
-        return out.tobytes(), st
-
-    def text_bytes(self, blocks):
-        """text(), downloaded -> (bytes, stats)"""
-        return self._download(*self.text(blocks))
-
-    def finish_bytes(self):
-        """finish(), downloaded -> (bytes, stats)"""
-        return self._download(*self.finish())
-
-    def close(self):
-        if self.h:
-            bt_fastq_scan_destroy(self.h)
-            self.h = None
 
 
 class GunzipStats(C.Structure):   # include/btgpu.h: bt_gunzip_stats
@@ -1818,8 +1816,10 @@ def gunzip_stage_seconds(reset=False):
     return dict(zip(("find", "decode", "windows", "resolve", "crc"), (float(x) for x in out)))
 
 
-class FastqGzScan:
-    """bt_fastq_gz_scan: any cuts of an ordinary gzip FASTQ file (one or more long members) -> reads text in device memory"""
+class FastqGzScan(_FastqScan):
+    """bt_fastq_gz_scan: any cuts of an ordinary gzip FASTQ file (one or more long members) -> reads text in device memory.  The file has to end at a member
+    boundary: finish() says so when it does not."""
+    _text, _finish, _destroy = bt_fastq_gz_scan_text, bt_fastq_gz_scan_finish, bt_fastq_gz_scan_destroy
 
     def __init__(self, ctx, max_in_bytes, chunk_bytes=0):
         self.ctx = ctx
@@ -1827,41 +1827,11 @@ class FastqGzScan:
         check(bt_fastq_gz_scan_create(ctx.h, max_in_bytes, chunk_bytes, C.byref(h)))
         self.h = h.value
 
-    def text(self, data):
-        """-> (device pointer of the text, valid until the next call; its length; this call's stats)"""
-        a = _bytes_array(data)
-        d, n, st = vp(), C.c_uint64(), FastqStats()
-        check(bt_fastq_gz_scan_text(self.h, _np_ptr(a) if a.size else None, a.size, C.byref(d), C.byref(n), C.byref(st)))
-        return d.value, n.value, st.as_dict()
-
-    def finish(self):
-        """the file has to end at a member boundary; the carried tail as the file's end -> (device pointer of its text, its length, stats)"""
-        d, n, st = vp(), C.c_uint64(), FastqStats()
-        check(bt_fastq_gz_scan_finish(self.h, C.byref(d), C.byref(n), C.byref(st)))
-        return d.value, n.value, st.as_dict()
-
-    def _download(self, d, n, st):
-        out = np.empty(n, np.uint8)
-        if n:
-            check(bt_memcpy_d2h(self.ctx.h, _np_ptr(out), d, n))
-        return out.tobytes(), st
-
-    def text_bytes(self, data):
-        return self._download(*self.text(data))
-
-    def finish_bytes(self):
-        return self._download(*self.finish())
-
     def stats(self):
         """the sums of the inflate calls' stats so far"""
         st = GunzipStats()
         check(bt_fastq_gz_scan_stats(self.h, C.byref(st)))
         return parse_gunzip_stats(st)
-
-    def close(self):
-        if self.h:
-            bt_fastq_gz_scan_destroy(self.h)
-            self.h = None
 
 
 def parse_genotype_text(text, index):

@@ -230,6 +230,17 @@ def bam_of_reads(reads, flags=None):
     return out
 
 
+MANY_RECORDS = [65536, 65537, 66000]   # 256, 257 and 258 workgroups of 256 records: the offsets scan's second round of 256 sums
+
+
+def short_records(n=MANY_RECORDS[-1]):
+    """[(record, seq, flag)] of n reads of 0 to 8 bases with flags drawn from 0, 0x10, 0x100 and 0x800 (about half are skipped under 0x900): many records in
+    few bytes (about 45 per record); the tests take prefixes of one list"""
+    rng = np.random.default_rng(n)
+    reads = [np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, size=int(b))].tobytes() for b in rng.integers(0, 9, size=n)]
+    return bam_of_reads(reads, flags=[int(f) for f in rng.choice([0, 0x10, 0x100, 0x800], size=n)])
+
+
 def invalid_records():
     """(bytes, offset of the failing record, words) — the failing record stands behind a sound one"""
     good = record(b"ACGT" * 10)

@@ -124,3 +124,12 @@ def edge_file(rng, k=55, eol=None, last_newline=True):
 
 def simple_records(rng, n, bases=20, eol=b"\n"):
     return [record(rng, i, random_seq(rng, bases), eol, header=b"@r%d" % i, kind=2) for i in range(n)]
+
+
+MANY_RECORDS = [16384, 16385, 16500]   # 65 536, 65 540 and 66 000 lines: 256, 257 and 258 workgroups of 256 lines, the offsets scan's second round of 256 sums
+
+
+def short_records(n):
+    """n records of 0 to 8 bases, '\\n' and '\\r\\n' alternating: many lines in few bytes (about 30 per record) -> the file's bytes"""
+    rng = np.random.default_rng(n)
+    return b"".join(record(rng, i, random_seq(rng, int(b)), (b"\n", b"\r\n")[i % 2], header=b"@%d" % i) for i, b in enumerate(rng.integers(0, 9, size=n)))

@@ -206,6 +206,17 @@ def test_reads_text_equals_the_expected_text(k):
     assert bd.records_text(recs, 0x900) != bd.records_text(recs, 0)
 
 
+def test_more_than_65536_records_equal_the_expected_text():
+    """the inputs of the GPU test of the same name: the host run gives the expected text and stats on them, so it is that test's reference"""
+    recs = bd.short_records()
+    for n in bd.MANY_RECORDS:
+        bam = b"".join(r for r, _, _ in recs[:n])
+        for skip in (0x900, 0):
+            kept = [s for _, s, f in recs[:n] if not f & skip]
+            assert skip == 0 or n // 3 < len(kept) < 2 * n // 3
+            assert lib.diag_bam_reads_text(bam, skip) == (bd.records_text(recs[:n], skip), len(bam), {"kept": len(kept), "skipped": n - len(kept), "bases": sum(map(len, kept))})
+
+
 def test_reads_text_every_code_and_empty_line():
     seq = bd.SEQ_CODES.encode()
     text, used, stats = lib.diag_bam_reads_text(bd.record(seq) + bd.record(b"") + bd.record(seq[:15]), 0)

@@ -119,6 +119,25 @@ def test_reads_text_equals_the_host(gpu_ctx, edge_bam):
     assert lib.bam_reads_text(gpu_ctx, long * 2 + bam[:500], 0) == lib.diag_bam_reads_text(long * 2 + bam[:500], 0)
 
 
+@pytest.fixture(scope="module")
+def many_records():
+    return bd.short_records()
+
+
+@pytest.mark.parametrize("n", bd.MANY_RECORDS)
+def test_more_than_65536_records_equal_the_host(gpu_ctx, many_records, n):
+    """256, 257 and 258 sums per 256 records: the offsets scan (text_offsets_kernel) carries its total from the first round of 256 sums into the second"""
+    from bayestyper_amd import lib
+
+    recs = many_records[:n]
+    bam = b"".join(r for r, _, _ in recs)
+    for skip in (0x900, 0):
+        kept = [s for _, s, f in recs if not f & skip]
+        want = lib.diag_bam_reads_text(bam, skip)
+        assert want == (bd.records_text(recs, skip), len(bam), {"kept": len(kept), "skipped": n - len(kept), "bases": sum(map(len, kept))})
+        assert lib.bam_reads_text(gpu_ctx, bam, skip) == want
+
+
 def test_bytes_that_look_like_records_do_not_move_a_start(gpu_ctx):
     """the device walks the slab in segments (1 KiB at this size) from guessed record starts and checks the guesses in order.  Here auxiliary arrays hold whole
     chains of well-formed records — some ending with their host record, some running over its end into the next record — so segments guess starts that are

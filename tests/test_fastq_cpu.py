@@ -41,6 +41,16 @@ def test_edge_file_equals_the_parser_and_reads_file(tmp_path, eol, last_newline)
     assert text == slabs and (st["reads"], st["bases"]) == (reads, bases)
 
 
+@pytest.mark.parametrize("n", fd.MANY_RECORDS)
+def test_more_than_65536_lines_equal_the_parser(n):
+    """the inputs of the GPU test of the same name: host run and parser agree on them, so either is that test's reference"""
+    data = fd.short_records(n)
+    want = fd.parse(data)
+    assert want[1] == len(data) and want[2]["lines"] == 4 * n and n // 2 < want[2]["reads"] < n
+    assert diag(data) == want
+    assert diag(data[:-1]) == fd.parse(data[:-1])   # the last line open
+
+
 def three_records():
     rng = np.random.default_rng(3)
     data = b"\n" + fd.record(rng, 0, b"ACGTNacgtn", b"\r\n") + b"\r\n\n" + fd.record(rng, 1, b"", b"\n") + fd.record(rng, 2, fd.random_seq(rng, 61), b"\n", kind=0) + b"\n"

@@ -50,6 +50,18 @@ def test_record_counts_around_the_line_tiles(gpu_ctx, n):
     assert lib.fastq_reads_text(gpu_ctx, data[:-1], final=False) == fd.parse(data[:-1], final=False)
 
 
+@pytest.mark.parametrize("n", fd.MANY_RECORDS)
+def test_more_than_65536_lines_equal_the_parser(gpu_ctx, n):
+    """256, 257 and 258 sums per 256 lines: the offsets scan (text_offsets_kernel) carries its total from the first round of 256 sums into the second"""
+    from bayestyper_amd import lib
+
+    data = fd.short_records(n)
+    want = fd.parse(data)
+    assert want[2]["lines"] == 4 * n
+    assert lib.fastq_reads_text(gpu_ctx, data) == want
+    assert lib.fastq_reads_text(gpu_ctx, data[:-1]) == fd.parse(data[:-1])   # the last line open
+
+
 def ending_at(rng, end, eol):
     """sound records whose last newline is byte end - 1: the last record's header is padded to fit"""
     tail = eol + b"ACGT" + eol + b"+" + eol + b"IIII" + eol
