@@ -1,21 +1,32 @@
 """Shared by the tests of the genotype text formatted on the device (bt_gibbs_genotype_text / bt_genotype_text / bt_diag_genotype_text): a hand-written
 record string with values the formatter does not cover, the text Python's own '%g' gives for a record, and the comparison of a launch's text with the host
-formatters' columns."""
+formatters' columns.  Further down: a reference for any such string made of Python's '%g' alone (Reference, check_against_reference), and the hand-built strings
+of the device tests with the conditions each has to meet — past one block of the offsets scan, the number formatter's edges, every store alignment."""
+import functools
+import math
+from fractions import Fraction
+
 import numpy as np
 
 from bayestyper_amd.host import genotypes
 
 NONE = 0xFFFF
+NO_SLOT = 0xFFFFFFFF   # kNoSlot: a ploidy-0 cell has no GQ slot
+SCAN_BLOCK = 1024      # variants per workgroup of text_scan_block_kernel
 
 
 def _f32(x):
     return np.array([x], np.float32).view(np.uint32)[0]
 
 
-def make_string(S, variants):
-    """a record string of bt_gibbs_genotypes (include/btgpu.h) with one cluster per variant.  variant: dict(dep, alleles=[(acp, ac, af, not_covered)] * A,
+def make_string(S, variants, cluster_var_off=None):
+    """a record string of bt_gibbs_genotypes (include/btgpu.h) with one cluster per variant, or with the cluster table given (ascending from 0 to the number of
+    variants; a cluster may be empty).  variant: dict(dep, alleles=[(acp, ac, af, not_covered)] * A,
     total_count, max_alt, samples=[dict(ploidy, est=(a, b), best, gpp=[G], app=[A'], filters=[A'], means=[A][3])] * S)"""
     NV = len(variants)
+    cvo = np.arange(NV + 1) if cluster_var_off is None else np.asarray(cluster_var_off)
+    Cn = len(cvo) - 1
+    assert cvo[0] == 0 and cvo[-1] == NV and (np.diff(cvo) >= 0).all()
     recs = []
     for v in variants:
         A = len(v["alleles"])
@@ -35,37 +46,133 @@ def make_string(S, variants):
             w += sw
         assert len(w) % 2 == 0
         recs.append(np.array(w, np.uint32))
-    at_rec = (4 + NV + 1 + NV + 1 + 1) & ~1
-    voff = at_rec + np.concatenate([[0], np.cumsum([len(r) for r in recs])])
+    at_rec = (4 + Cn + 1 + NV + 1 + 1) & ~1
+    voff = at_rec + np.concatenate([[0], np.cumsum([len(r) for r in recs], dtype=np.int64)]).astype(np.int64)
     head = np.zeros(at_rec, np.uint32)
-    head[:3] = (NV, NV, S)
-    head[4:4 + NV + 1] = np.arange(NV + 1)
-    head[5 + NV:5 + NV + NV + 1] = voff
+    head[:3] = (Cn, NV, S)
+    head[4:4 + Cn + 1] = cvo
+    head[5 + Cn:5 + Cn + NV + 1] = voff
     return np.concatenate([head] + recs)
+
+
+def var_off(words):
+    """the var_off table of a record string: the word at which each variant's record starts"""
+    Cn, NV = int(words[0]), int(words[1])
+    return words[5 + Cn:5 + Cn + NV + 1].astype(np.int64)
 
 
 def g6(x):
     return "%g" % float(x)
 
 
+def covered(x):
+    """the range the device formatter states for itself (bt_genotype_text.hpp): zero, or 1e-27 <= |x| < 1e6; subnormals lie below it"""
+    x = float(x)
+    return x == 0.0 or (math.isfinite(x) and 1e-27 <= abs(x) < 1e6)
+
+
+def reference_pieces(v):
+    """a make_string variant from Python alone -> (stats, cover, [(cell text without GQ, bytes in front of the GQ slot or None)] per sample, not covered).
+    float32 fields are widened exactly and printed with '%g', doubles with '%g', integers with str; a number outside `covered` prints nothing and flags the variant"""
+    flag = [False]
+
+    def num(x):
+        if covered(x):
+            return g6(x)
+        flag[0] = True
+        return ""
+
+    def f32(x):
+        return num(float(np.float32(x)))
+
+    al = v["alleles"]
+    stats = "AC=" + ",".join(str(a[1]) for a in al[1:]) + ";AF=" + ",".join(f32(a[2]) for a in al[1:]) + ";AN=%d;ACP=" % v["total_count"] + ",".join(f32(a[0]) for a in al)
+    nc = [str(i) for i, a in enumerate(al) if a[3]]
+    cover = ";ANC=" + ",".join(nc) if nc else ""
+    cells = []
+    for s in v["samples"]:
+        if s["ploidy"] == 0:
+            cells.append(("\t:.:.:.:.:.:.", None))
+            continue
+        front = "\t" + "/".join("." if e == NONE else str(e) for e in s["est"][:s["ploidy"]]) + ":"
+        m = np.asarray(s["means"], np.float64).reshape(len(al), 3)
+        rest = ":".join(["", ",".join(f32(x) for x in s["gpp"]), ",".join(f32(x) for x in s["app"])] + [",".join(num(x) for x in m[:, k]) for k in range(3)] +
+                        [",".join(str(f & 0xFFFF) for f in s["filters"])])
+        cells.append((front + rest, len(front)))
+    return stats, cover, cells, flag[0]
+
+
 def expected_pieces(v):
     """(stats, cover, samples with GQ) of a make_string variant as the host writes them, numbers through Python's '%g' (correctly rounded, as glibc's)"""
     from bayestyper_amd import lib
 
-    al = v["alleles"]
-    stats = "AC=" + ",".join(str(a[1]) for a in al[1:]) + ";AF=" + ",".join(g6(np.float32(a[2])) for a in al[1:]) + ";AN=%d;ACP=" % v["total_count"] + ",".join(g6(np.float32(a[0])) for a in al)
-    nc = [str(i) for i, a in enumerate(al) if a[3]]
-    cover = ";ANC=" + ",".join(nc) if nc else ""
+    stats, cover, cells, _ = reference_pieces(v)
     samples = ""
-    for s in v["samples"]:
-        if s["ploidy"] == 0:
-            samples += "\t:.:.:.:.:.:."
-            continue
-        gt = "/".join("." if e == NONE else str(e) for e in s["est"][:s["ploidy"]])
-        m = np.asarray(s["means"], np.float64)
-        samples += "\t" + ":".join([gt, str(lib.genotype_quality(np.float32(s["best"]))), ",".join(g6(np.float32(x)) for x in s["gpp"]), ",".join(g6(np.float32(x)) for x in s["app"])] +
-                                   [",".join(g6(x) for x in m[:, k]) for k in range(3)] + [",".join(str(f) for f in s["filters"])])
+    for (text, slot), s in zip(cells, v["samples"]):
+        samples += text if slot is None else text[:slot] + str(lib.genotype_quality(np.float32(s["best"]))) + text[slot:]
     return stats, cover, samples
+
+
+class Reference:
+    """text, index and not-covered count of a record string, from reference_pieces' lengths alone (index layout: include/btgpu.h), and where every piece lies:
+    piece_off / piece_len [NV] (the stats and cover piece, which one lane writes), has_cover [NV], cell_off / cell_len [NV][S] (offsets into the whole text)"""
+
+    def __init__(self, S, variants, cluster_var_off=None):
+        NV = len(variants)
+        cvo = np.arange(NV + 1) if cluster_var_off is None else np.asarray(cluster_var_off)
+        Cn = len(cvo) - 1
+        index = np.zeros(4 + Cn + 1 + 9 * NV + 2 * NV * S, np.uint32)
+        index[4:5 + Cn] = cvo
+        var = index[5 + Cn:5 + Cn + 9 * NV].reshape(NV, 9)
+        cell = index[5 + Cn + 9 * NV:].reshape(NV, S, 2)
+        parts, at, flags = [], 0, []
+        self.piece_off, self.piece_len, self.has_cover = np.zeros(NV, np.int64), np.zeros(NV, np.int64), np.zeros(NV, bool)
+        self.cell_off, self.cell_len = np.zeros((NV, S), np.int64), np.zeros((NV, S), np.int64)
+        for i, v in enumerate(variants):
+            stats, cover, cells, nc = reference_pieces(v)
+            assert len(cells) == S
+            n_samples = sum(len(t) for t, _ in cells)
+            var[i] = (at & 0xFFFFFFFF, at >> 32, len(stats), len(cover), n_samples, len(v["alleles"]), v["total_count"], _f32(v["max_alt"]), 1 if nc else 0)
+            self.piece_off[i], self.piece_len[i], self.has_cover[i] = at, len(stats) + len(cover), bool(cover)
+            inside = 0
+            for s, (t, slot) in enumerate(cells):
+                cell[i, s] = (_f32(v["samples"][s]["best"]), NO_SLOT if slot is None else inside + slot)
+                self.cell_off[i, s], self.cell_len[i, s] = at + len(stats) + len(cover) + inside, len(t)
+                inside += len(t)
+            parts.append(stats + cover + "".join(t for t, _ in cells))
+            at += len(parts[-1])
+            flags.append(1 if nc else 0)
+        self.flags = np.array(flags, np.int64)
+        self.not_covered = int(self.flags.sum())
+        index[:4] = (Cn, NV, S, self.not_covered)
+        self.text = np.frombuffer("".join(parts).encode("ascii"), np.uint8)
+        self.index, self.Cn, self.NV, self.S = index, Cn, NV, S
+        assert self.text.size == at
+
+    def variant_offset(self, v):
+        return int(self.piece_off[v])
+
+
+def check_against_reference(text, index, not_covered, ref, what=""):
+    """exactly the reference's bytes and words; a difference is reported at the first variant that shows it"""
+    index = np.asarray(index, np.uint32)
+    text = np.asarray(text, np.uint8)
+    assert index.size == ref.index.size, (what, "index words", index.size, ref.index.size)
+    assert [int(x) for x in index[:4]] == [ref.Cn, ref.NV, ref.S, ref.not_covered] and not_covered == ref.not_covered, (what, "index head", index[:4], not_covered, ref.not_covered)
+    Cn, NV, S = ref.Cn, ref.NV, ref.S
+    assert np.array_equal(index[4:5 + Cn], ref.index[4:5 + Cn]), (what, "cluster_var_off")
+    var, rvar = index[5 + Cn:5 + Cn + 9 * NV].reshape(NV, 9), ref.index[5 + Cn:5 + Cn + 9 * NV].reshape(NV, 9)
+    bad = np.flatnonzero((var != rvar).any(axis=1))
+    assert bad.size == 0, (what, "index words of variant", int(bad[0]), var[bad[0]].tolist(), rvar[bad[0]].tolist(), "variants that differ:", bad.size)
+    cell, rcell = index[5 + Cn + 9 * NV:].reshape(NV, S, 2), ref.index[5 + Cn + 9 * NV:].reshape(NV, S, 2)
+    bad = np.flatnonzero((cell != rcell).any(axis=(1, 2)))
+    assert bad.size == 0, (what, "cell words of variant", int(bad[0]), cell[bad[0]].tolist(), rcell[bad[0]].tolist())
+    assert text.size == ref.text.size, (what, "text bytes", text.size, ref.text.size)
+    diff = np.flatnonzero(text != ref.text)
+    if diff.size:
+        v = int(np.searchsorted(ref.piece_off, diff[0], side="right")) - 1
+        a, b = int(ref.piece_off[v]), int(ref.piece_off[v + 1]) if v + 1 < NV else text.size
+        raise AssertionError((what, "text of variant", v, "first byte", int(diff[0]), text[a:b].tobytes(), ref.text[a:b].tobytes(), "bytes that differ:", diff.size))
 
 
 def hand_written(S=2):
@@ -108,3 +215,279 @@ def assert_launch_text_equals_host(parsed, flat, res, ploidy_of_cluster, mf, wha
     assert len(parsed) == int(voff[-1])
     for c in range(flat["num_clusters"]):
         assert_cluster_text_equals_host(parsed[voff[c]:voff[c + 1]], flat, res, c, ploidy_of_cluster[c], mf, what=what)
+
+
+# ---- record strings for the device tests: past one scan block, the formatter's edges, every store alignment ---------------------------------------------
+def _digits(rng, scale=1.0):
+    """a value whose '%g' text has between one and eight characters"""
+    return round(float(rng.random()) * scale, int(rng.integers(0, 7)))
+
+
+def ordinary_variant(rng, A, ploidies):
+    """a variant of covered values; every number has a random count of digits, so the pieces' lengths differ from variant to variant"""
+    alleles = [(_digits(rng), int(rng.integers(0, 10 ** int(rng.integers(1, 6)))), _digits(rng), int(rng.random() < 0.25)) for _ in range(A)]
+    samples = []
+    for p in ploidies:
+        G = A * (A + 1) // 2 if p == 2 else (A if p == 1 else 0)
+        Ap = A if p else 0
+        est = [NONE if rng.random() < 0.2 else int(rng.integers(0, A)) for _ in range(2)]
+        means = [[-1.0] * 3 if rng.random() < 0.2 else [_digits(rng, 100.0) for _ in range(3)] for _ in range(A)]
+        samples.append(dict(ploidy=p, est=tuple(e if i < p else NONE for i, e in enumerate(est)), best=_digits(rng), gpp=[_digits(rng) for _ in range(G)],
+                            app=[_digits(rng) for _ in range(Ap)], filters=[int(rng.integers(0, 8)) for _ in range(Ap)], means=means))
+    return dict(dep=int(rng.integers(0, 2)), total_count=int(rng.integers(0, 300)), max_alt=_digits(rng), alleles=alleles, samples=samples)
+
+
+def cluster_table(NV):
+    """a cluster_var_off with several variants per cluster and with empty clusters, one of them last"""
+    cvo = [0]
+    for i in range(NV + 8):
+        if cvo[-1] == NV:
+            break
+        cvo.append(min(NV, cvo[-1] + (0, 1, 3, 2, 0, 0, 5, 1)[i % 8]))
+    return np.array(cvo + [NV], np.int64)
+
+
+def scan_not_covered(NV, S):
+    """the variants of a scan string that hold a 1e7 mean (hand_written()'s form): from 2049 variants on about every 97th, two neighbours in one wavefront,
+    and the last variant, which is alone in the last scan block at 2049 and 4097"""
+    return frozenset() if NV < 2049 or S == 0 else frozenset(range(50, NV, 97)) | {100, 101, NV - 1}
+
+
+# (NV, S, several variants per cluster)
+SCAN_CASES = [(NV, 1, False) for NV in (0, 1, 2, 3, 5, 1023, 1024, 1025, 2047, 2049, 4097)] + [(1025, 3, False), (2049, 3, False), (5, 0, False), (1025, 0, False), (1025, 1, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def scan_case(NV, S, multi=False):
+    """-> (record string, Reference, variants): ordinary variants with 2 to 4 alleles and ploidies 0 / 1 / 2 mixed"""
+    rng = np.random.default_rng(7000 + 13 * NV + S)
+    nc = scan_not_covered(NV, S)
+    variants = []
+    for v in range(NV):
+        ploidies = [int(rng.integers(0, 3)) for _ in range(S)]
+        if v in nc:
+            ploidies[-1] = 1 + v % 2
+        variants.append(ordinary_variant(rng, int(rng.integers(2, 5)), ploidies))
+        if v in nc:
+            variants[-1]["samples"][-1]["means"][0][2] = 1e7
+    cvo = cluster_table(NV) if multi else None
+    return make_string(S, variants, cvo), Reference(S, variants, cvo), variants
+
+
+def ploidy_word(words, v):
+    """the word of a record string that holds the ploidy of variant v's first sample record"""
+    at = int(var_off(words)[v])
+    return at + 4 + 4 * int(words[at])
+
+
+# -- values for format_g6 --
+def g6_ties():
+    """(D + 0.5) / 10^p whose quotient is exactly representable: the seventh digit is an exact 5, and %g rounds the sixth to even"""
+    ties = []
+    for p in range(6):
+        for D in list(range(100000, 100400)) + list(range(524280, 524300)) + list(range(999600, 1000000)) + list(range(123456, 999999, 7919)):
+            v = (D + 0.5) / 10 ** p
+            if Fraction(v) == Fraction(2 * D + 1, 2 * 10 ** p):
+                ties.append(v)
+    return ties
+
+
+def g6_near_switches():
+    """near both notation switches: 10^-5 | 10^-4 (exponent / fixed) and 10^5 | 10^6 (fixed / exponent)"""
+    return [D * 10.0 ** p + 0.5 * 10.0 ** p for p in (-10, -9, -1, 0) for D in (99999, 100000, 999999, 999998, 123456)]
+
+
+G6_RANGE_EDGES = [9.9999949e-5, 9.9999951e-5, 1e-4, 999999.4, 999999.5, 1e-27, -1.0, 0.0, -0.0, 1.0, 0.5, -0.25, 100000.0, 123456.0]
+G6_DECADES = range(-27, 6)
+G6_HALF_D = (100000, 123456, 999999)
+
+
+@functools.lru_cache(maxsize=None)
+def g6_doubles():
+    """-> {category: float64 array}, all covered.  `all` = every other category, the same negated, and both zeros"""
+    rng = np.random.default_rng(66)
+    out = {}
+    out["random"] = np.array([rng.uniform(1.0001, 9.9999) * 10.0 ** p for p in G6_DECADES for _ in range(36)])
+    half = []   # the doubles next to D * 10^(p - 5) + half a unit of the sixth digit, on both sides, and the double nearest to it
+    for p in G6_DECADES:
+        for D in G6_HALF_D:
+            t = float(Fraction(2 * D + 1, 2) * Fraction(10) ** (p - 5))
+            half += [np.nextafter(t, 0.0), t, np.nextafter(t, np.inf)]
+    out["half"] = np.array(half)
+    out["carry"] = np.array([9.9999951e-5, 999999.5] + [9.9999951 * 10.0 ** p for p in G6_DECADES] + [9.999995 * 10.0 ** p for p in G6_DECADES])   # round up into the next power of ten
+    out["tiny"] = 10.0 ** rng.uniform(-26.999, -22.001, 250)   # a = 5 - floor(log10 v) >= 27: the second multiply loop
+    out["ties"] = np.array(g6_ties())
+    out["near"] = np.array(g6_near_switches())
+    out["edges"] = np.array(G6_RANGE_EDGES)
+    positive = np.concatenate([out[k] for k in ("random", "half", "carry", "tiny", "ties", "near", "edges")])
+    out["negated"] = -positive
+    out["zeros"] = np.array([0.0, -0.0])
+    out["all"] = np.concatenate([positive, out["negated"], out["zeros"]])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def g6_floats():
+    """-> {category: float32 array}, all covered"""
+    rng = np.random.default_rng(67)
+    f32 = np.float32
+    out = {}
+    out["ties"] = (np.array(list(range(100000, 100150)) + list(range(524200, 524350)) + list(range(999850, 1000000)), np.float64) + 0.5).astype(f32)   # x + 0.5 < 2^23: exact
+    out["ratios"] = np.concatenate([np.arange(N + 1, dtype=f32)[::step] / f32(N) for N, step in ((7, 1), (120, 1), (5000, 7))])
+    out["random"] = np.array([rng.uniform(1.001, 9.999) * 10.0 ** p for p in G6_DECADES for _ in range(30)]).astype(f32)
+    near = []
+    for c in (1e-4, 1e-5):
+        near += [np.nextafter(f32(c), f32(0)), f32(c), np.nextafter(f32(c), f32(1))]
+    below = np.nextafter(f32(1e6), f32(0))   # (1e6 itself and what lies above it are not covered)
+    out["neighbours"] = np.array(near + [below, np.nextafter(below, f32(0))], f32)
+    out["all"] = np.concatenate([out[k] for k in ("ties", "ratios", "random", "neighbours")])
+    return out
+
+
+def g6_not_covered():
+    """(where it goes: a k-mer mean (double), a genotype posterior or an allele call probability (float32); the value)"""
+    return [("mean", float("nan")), ("mean", float("inf")), ("mean", float("-inf")), ("mean", 5e-324), ("mean", 2.2250738585072009e-308), ("gpp", np.float32(1e-40)),
+            ("mean", 1e6), ("mean", -1e6), ("gpp", np.float32(1e6)), ("gpp", np.float32(-1e6)), ("mean", float(np.nextafter(1e-27, 0.0))), ("gpp", np.float32("nan")),
+            ("gpp", np.float32("inf")), ("acp", np.float32("-inf")), ("acp", np.float32(1e-40))]
+
+
+def value_variants(doubles, floats, S=3):
+    """variants of 2 to 7 alleles, diploid and haploid samples, whose k-mer means are `doubles` and whose AF / ACP / GPP / APP are `floats`: every value once, in a
+    field that is printed; what one pool lacks while the other lasts is 12.5 or 0.25"""
+    d, f = [float(x) for x in doubles][::-1], [np.float32(x) for x in floats][::-1]
+
+    def td():
+        return d.pop() if d else 12.5
+
+    def tf():
+        return f.pop() if f else np.float32(0.25)
+
+    variants = []
+    while d or f:
+        i = len(variants)
+        A = (7, 5, 3, 2, 6, 4)[i % 6]
+        alleles = [(tf(), a, tf() if a else 0.0, 0) for a in range(A)]   # (AF of allele 0 is not printed)
+        samples = []
+        for s in range(S):
+            p = 1 if (i + s) % 3 == 2 else 2
+            G = A * (A + 1) // 2 if p == 2 else A
+            samples.append(dict(ploidy=p, est=(s % A, i % A if p == 2 else NONE), best=0.5, gpp=[tf() for _ in range(G)], app=[tf() for _ in range(A)], filters=[0] * A,
+                                means=[[td(), td(), td()] for _ in range(A)]))
+        variants.append(dict(dep=0, total_count=2 * S, max_alt=0.5, alleles=alleles, samples=samples))
+    return variants
+
+
+@functools.lru_cache(maxsize=None)
+def g6_case(S=3):
+    """-> (record string, Reference): every value of g6_doubles() and g6_floats() in one string"""
+    variants = value_variants(g6_doubles()["all"], g6_floats()["all"], S)
+    return make_string(S, variants), Reference(S, variants)
+
+
+@functools.lru_cache(maxsize=None)
+def not_covered_case(S=3):
+    """-> (record string, Reference, the not-covered variants): every value of g6_not_covered() in a variant of its own between covered ones"""
+    rng = np.random.default_rng(68)
+    variants, at = [ordinary_variant(rng, 3, [2] * S)], []
+    for where, x in g6_not_covered():
+        v = ordinary_variant(rng, 3, [2] * S)
+        if where == "mean":
+            v["samples"][S - 1]["means"][1][0] = x
+        elif where == "gpp":
+            v["samples"][0]["gpp"][2] = x
+        else:
+            v["alleles"][1] = (x,) + v["alleles"][1][1:]
+        at.append(len(variants))
+        variants += [v, ordinary_variant(rng, 3, [2] * S)]
+    return make_string(S, variants), Reference(S, variants), at
+
+
+# -- every store alignment --
+@functools.lru_cache(maxsize=None)
+def alignment_case(S=3, NV=300):
+    """-> (record string, Reference, variants): 1 to 4 alleles, ploidies 0 / 1 / 2, the cover piece there or not, every number with its own count of digits"""
+    rng = np.random.default_rng(404)
+    variants = [ordinary_variant(rng, int(rng.integers(1, 5)), [int(rng.integers(0, 3)) for _ in range(S)]) for _ in range(NV)]
+    return make_string(S, variants), Reference(S, variants), variants
+
+
+def alignment_pairs(ref, address):
+    """with the text at `address`: the (address of the first byte mod 4, address one past the last byte mod 4) pairs among the cells, among the variant pieces
+    (stats and cover, one lane's bytes), and at the seams.  A seam is where the variant lane's last byte meets the first cell's first byte, written by two kernels:
+    its pair is the first cell's, with whether the piece in front of it ends in a cover piece"""
+    a, b = address + ref.cell_off, address + ref.cell_off + ref.cell_len
+    cells = set(zip((a % 4).reshape(-1).tolist(), (b % 4).reshape(-1).tolist()))
+    seams = set(zip((a[:, 0] % 4).tolist(), (b[:, 0] % 4).tolist(), ref.has_cover.tolist())) if ref.S else set()
+    a, b = address + ref.piece_off, address + ref.piece_off + ref.piece_len
+    pieces = set(zip((a % 4).tolist(), (b % 4).tolist()))
+    return cells, pieces, seams
+
+
+ALL_PAIRS = {(i, j) for i in range(4) for j in range(4)}
+
+
+# -- the conditions on these inputs, asserted by the CPU and the GPU tests before they compare anything --
+def check_scan_inputs(NV, S, multi, ref, variants):
+    """variants of differing lengths (a wrong block offset then moves bytes), the stated ploidies and alleles, and the not-covered variants where DESIGN.md 4.7 says they are"""
+    if NV >= 5:
+        assert len(set((ref.piece_len + ref.cell_len.sum(axis=1)).tolist())) >= 4
+    if NV >= 1023:
+        assert {len(v["alleles"]) for v in variants} == {2, 3, 4} and (S == 0 or {s["ploidy"] for v in variants for s in v["samples"]} == {0, 1, 2})
+    if NV > SCAN_BLOCK:
+        assert ref.variant_offset(SCAN_BLOCK) == int((ref.piece_len + ref.cell_len.sum(axis=1))[:SCAN_BLOCK].sum()) > 20 * SCAN_BLOCK
+    if multi:
+        sizes = np.diff(ref.index[4:5 + ref.Cn].astype(np.int64))
+        assert ref.Cn != NV and (sizes == 0).any() and (sizes > 1).any() and sizes[-1] == 0
+    nc = sorted(scan_not_covered(NV, S))
+    assert np.array_equal(np.flatnonzero(ref.flags), nc) and ref.not_covered == len(nc)
+    if NV >= 2049 and S:
+        assert {v // SCAN_BLOCK for v in nc} == set(range((NV + SCAN_BLOCK - 1) // SCAN_BLOCK))           # one in each scan block
+        assert any(a // 64 == b // 64 and (a * S) // 64 == (b * S + S - 1) // 64 for a, b in zip(nc, nc[1:]))   # two in one wavefront of variants and of cells
+        assert NV // 97 - 1 <= len(nc) <= NV // 97 + 4
+
+
+def check_g6_inputs():
+    """every category of values holds at least its stated number, and every value is covered"""
+    d, f = g6_doubles(), g6_floats()
+    half = set(d["half"].tolist())
+    for p in G6_DECADES:
+        lo, hi = 10.0 ** p, 10.0 ** (p + 1)
+        assert int(((d["random"] >= lo) & (d["random"] < hi)).sum()) >= 24 and int(((f["random"] >= lo * 0.9999) & (f["random"] < hi)).sum()) >= 24, p
+        for D in G6_HALF_D:   # a double on either side of D * 10^(p - 5) + half a unit of the sixth digit, next to each other or next to the double that equals it
+            t = Fraction(2 * D + 1, 2) * Fraction(10) ** (p - 5)
+            mid = float(t)
+            below, above = float(np.nextafter(mid, 0.0)), float(np.nextafter(mid, np.inf))
+            assert {below, above} <= half and Fraction(below) < t < Fraction(above), (p, D)
+    assert d["half"].size >= 2 * len(G6_DECADES) * len(G6_HALF_D)
+    assert {9.9999951e-5, 999999.5} <= set(d["carry"].tolist()) and g6(9.9999951e-5) == "0.0001" and g6(999999.5) == "1e+06"
+    carried = [x for x in d["carry"] if float(g6(x)) > x and g6(x).split("e")[0].replace("0", "").replace(".", "") == "1"]   # printed as a power of ten above the value
+    assert len(carried) >= len(G6_DECADES) + 2
+    assert int(((d["all"] > 0) & (d["all"] < 1e-22)).sum()) >= 200 and int(((d["all"] < 0) & (d["all"] > -1e-22)).sum()) >= 200
+    assert d["ties"].size > 1000 and d["near"].size == 20 and d["edges"].size == len(G6_RANGE_EDGES)
+    positive = sum(d[k].size for k in ("random", "half", "carry", "tiny", "ties", "near", "edges"))
+    assert d["negated"].size == positive and d["all"].size == 2 * positive + 2 and sorted(np.signbit(d["zeros"]).tolist()) == [False, True] and not d["zeros"].any()
+    assert int((d["all"].astype(np.float32).astype(np.float64) != d["all"]).sum()) > 3000   # doubles that are not widened floats
+    assert f["ties"].size >= 300 and {524288.5, 999999.5} <= set(f["ties"].astype(np.float64).tolist())
+    assert all(float(x) == math.floor(float(x)) + 0.5 and 100000 <= float(x) < 1e6 for x in f["ties"])
+    assert f["ratios"].size >= 8 + 121 + 700 and f["neighbours"].size == 8 and f["all"].dtype == np.float32
+    for c in (1e-4, 1e-5, 1e6):
+        assert int((np.abs(f["neighbours"].astype(np.float64) / c - 1) < 3e-7).sum()) >= 2, c
+    assert all(covered(x) for x in d["all"]) and all(covered(x) for x in f["all"])
+    kinds = [x for _, x in g6_not_covered()]
+    assert not any(covered(x) for x in kinds)
+    as64 = [float(x) for x in kinds]
+    assert any(math.isnan(x) for x in as64) and float("inf") in as64 and float("-inf") in as64 and 1e6 in as64 and -1e6 in as64 and float(np.nextafter(1e-27, 0.0)) in as64
+    assert any(0 < x < 2.2250738585072014e-308 for x in as64)                                                      # a subnormal double
+    assert any(isinstance(x, np.float32) and 0 < float(x) < 1.1754943508222875e-38 for x in kinds)               # a float32 subnormal: a normal double below 1e-27
+
+
+def check_alignment_inputs(ref, variants, address):
+    """all 16 (first byte, one past the last byte) residues among the cells, among the variant pieces and at the seams (there with and without a cover piece),
+    for the text at `address`; the short pieces are there"""
+    cells, pieces, seams = alignment_pairs(ref, address)
+    assert cells == ALL_PAIRS and pieces == ALL_PAIRS, (address % 4, sorted(ALL_PAIRS - cells), sorted(ALL_PAIRS - pieces))
+    assert seams == {(i, j, c) for i, j in ALL_PAIRS for c in (False, True)}, (address % 4, len(seams))
+    assert ref.NV * ref.S > 3 * 256 and int((ref.cell_len == len("\t:.:.:.:.:.:.")).sum()) >= 50            # several wavefronts of cells; ploidy-0 cells
+    assert sum(1 for v in variants for s in v["samples"] if len(v["alleles"]) == 1 and s["ploidy"] == 1) >= 10   # haploid cells at A = 1
+    for lens in (ref.cell_len.reshape(-1), ref.piece_len):   # consecutive pieces' lengths sweep their residues
+        assert {(int(a) % 4, int(b) % 4) for a, b in zip(lens, lens[1:])} == ALL_PAIRS

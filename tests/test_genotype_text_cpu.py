@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import _oracle
-from _genotype_text import assert_cluster_text_equals_host, expected_pieces, hand_written, make_string
+from _genotype_text import (G6_RANGE_EDGES, SCAN_BLOCK, SCAN_CASES, alignment_case, assert_cluster_text_equals_host, check_against_reference, check_alignment_inputs,
+                            check_g6_inputs, check_scan_inputs, expected_pieces, g6_case, g6_doubles, g6_floats, g6_near_switches, g6_not_covered, g6_ties, hand_written,
+                            make_string, not_covered_case, ploidy_word, scan_case)
 from _genotypes_device import group_of_cluster, min_fraction, mixed_batch, multiallelic_batch
 from bayestyper_amd import lib
 
@@ -40,25 +42,18 @@ def test_double_ratios():
 
 def test_exact_ties_round_to_even():
     """(D + 0.5) / 10^p whose quotient is exactly representable: the seventh digit is an exact 5, and %g rounds the sixth to even"""
-    from fractions import Fraction
-
-    ties = []
-    for p in range(6):
-        for D in list(range(100000, 100400)) + list(range(524280, 524300)) + list(range(999600, 1000000)) + list(range(123456, 999999, 7919)):
-            v = (D + 0.5) / 10 ** p
-            if Fraction(v) == Fraction(2 * D + 1, 2 * 10 ** p):
-                ties.append(v)
+    ties = g6_ties()
     assert len(ties) > 1000   # (p = 0 always; p >= 1 when (2 D + 1) / 2 is a multiple of 5^p)
     assert sum(1 for v in ties if v != math.floor(v) + 0.5) > 10
     _check_g6(ties, "ties")
     # near both notation switches: 10^-5 | 10^-4 (exponent / fixed) and 10^5 | 10^6 (fixed / exponent)
-    near = [D * 10.0 ** p + 0.5 * 10.0 ** p for p in (-10, -9, -1, 0) for D in (99999, 100000, 999999, 999998, 123456)]
+    near = g6_near_switches()
     got = _check_g6(near, "switches")
     assert got[near.index(999999 + 0.5)] == "1e+06" and got[5].endswith("e-05") and got[6].startswith("0.0001") and got[near.index(99999.5)] == "99999.5"
 
 
 def test_range_edges():
-    edges = [9.9999949e-5, 9.9999951e-5, 1e-4, 999999.4, 999999.5, 1e-27, -1.0, 0.0, -0.0, 1.0, 0.5, -0.25, 100000.0, 123456.0]
+    edges = list(G6_RANGE_EDGES)
     got = _check_g6(edges, "edges")
     assert got[:6] == ["9.99999e-05", "0.0001", "0.0001", "999999", "1e+06", "1e-27"] and got[6:9] == ["-1", "0", "-0"]
     assert lib.diag_format_g6([np.nextafter(1e-27, 0)]) == [None]
@@ -162,3 +157,77 @@ def test_strings_of_another_layout_are_refused():
     bad = w.copy()
     bad[int(w[5 + 5]) + 4 + 4 * 2] = 3   # ploidy 3
     assert lib.bt_diag_genotype_text(bad.ctypes.data, bad.size, *args) != 0 and "layout" in lib.bt_last_error().decode()
+
+
+# ---- the inputs of the device tests (test_genotype_text_gpu.py) on the host: each meets its stated conditions, and the reference built from Python's '%g'
+# ---- alone agrees with the host run of the shared header -------------------------------------------------------------------------------------------------
+def _raw_diag(words, text, text_capacity, index, index_capacity):
+    nt, ni, nc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    rc = lib.bt_diag_genotype_text(words.ctypes.data, words.size, text, text_capacity, index, index_capacity, C.byref(nt), C.byref(ni), C.byref(nc))
+    return rc, nt.value, ni.value, nc.value
+
+
+@pytest.mark.parametrize("NV,S,multi", SCAN_CASES)
+def test_scan_strings_on_the_host(NV, S, multi):
+    """the strings that take the device's offsets scan past one workgroup, to its `base + q < num_variants` edges and through NV = 0 and S = 0"""
+    words, ref, variants = scan_case(NV, S, multi)
+    check_scan_inputs(NV, S, multi, ref, variants)
+    text, index, not_covered = lib.diag_genotype_text(words)
+    check_against_reference(text, index, not_covered, ref, (NV, S, multi))
+    if NV > SCAN_BLOCK:
+        at = 5 + ref.Cn + 9 * SCAN_BLOCK
+        assert int(index[at]) | (int(index[at + 1]) << 32) == ref.variant_offset(SCAN_BLOCK)
+    parsed = lib.parse_genotype_text(text, index)
+    assert [p["flags"] for p in parsed] == ref.flags.tolist()
+    for v in list(range(min(NV, 3))) + [NV - 1] * (NV > 3):   # (the reference's pieces are expected_pieces' without GQ: a spot check that the two agree)
+        if not ref.flags[v]:
+            assert (parsed[v]["stats"], parsed[v]["cover"], parsed[v]["samples"]) == expected_pieces(variants[v])
+
+
+def test_a_malformed_record_past_the_first_scan_block_writes_nothing():
+    words, ref, _ = scan_case(2049, 1)
+    bad = words.copy()
+    bad[ploidy_word(words, 1500)] = 3
+    text, index = np.full(ref.text.size, 0xAA, np.uint8), np.full(ref.index.size, 0xAAAAAAAA, np.uint32)
+    rc, _, _, _ = _raw_diag(bad, text.ctypes.data, text.size, index.ctypes.data, index.size)
+    assert rc != 0 and "layout" in lib.bt_last_error().decode() and (text == 0xAA).all() and (index == 0xAAAAAAAA).all()
+    rc, nt, ni, _ = _raw_diag(words, text.ctypes.data, text.size, index.ctypes.data, index.size)   # the string itself is accepted with these buffers
+    assert rc == 0 and (nt, ni) == (text.size, index.size)
+
+
+def test_format_g6_edges_in_records_on_the_host():
+    """the values the device test carries into the kernels as k-mer means (doubles) and AF / ACP / GPP / APP (float32)"""
+    check_g6_inputs()
+    d, f = g6_doubles()["all"], g6_floats()["all"]
+    _check_g6(d, "doubles")
+    _check_g6(f.astype(np.float64), "floats")
+    words, ref = g6_case()
+    raw = ref.text.tobytes().decode()
+    missing = [x for x in list(d[::97]) + list(f[::53]) if "%g" % float(x) not in raw]   # (make_string placed them: every 97th and 53rd looked up)
+    assert not missing and ref.not_covered == 0 and {int(w) for w in ref.index[5 + ref.Cn + 5:5 + ref.Cn + 9 * ref.NV:9]} == set(range(2, 8))
+    text, index, not_covered = lib.diag_genotype_text(words)
+    check_against_reference(text, index, not_covered, ref, "format_g6 values")
+
+
+def test_not_covered_values_in_records_on_the_host():
+    words, ref, at = not_covered_case()
+    assert len(at) == len(g6_not_covered()) == ref.not_covered and np.array_equal(np.flatnonzero(ref.flags), at) and all(b - a == 2 for a, b in zip(at, at[1:]))
+    text, index, not_covered = lib.diag_genotype_text(words)
+    check_against_reference(text, index, not_covered, ref, "not covered")
+    assert [p["flags"] for p in lib.parse_genotype_text(text, index)] == ref.flags.tolist()
+
+
+def test_store_alignment_on_the_host():
+    """StoreSink at every (first byte, one past the last byte) residue, the text at base + 0 .. 3 between guard bytes"""
+    words, ref, variants = alignment_case()
+    n = ref.text.size
+    for shift in range(4):
+        buf = np.full(n + 128 + 8, 0xAA, np.uint8)
+        start = (-buf.ctypes.data) % 4 + 64 + shift   # base + shift with a 4-aligned base
+        assert (buf.ctypes.data + start) % 4 == shift
+        check_alignment_inputs(ref, variants, buf.ctypes.data + start)
+        index = np.zeros(ref.index.size, np.uint32)
+        rc, nt, ni, nc = _raw_diag(words, buf.ctypes.data + start, n, index.ctypes.data, index.size)
+        assert rc == 0 and (nt, ni) == (n, index.size)
+        check_against_reference(buf[start:start + n], index, nc, ref, f"shift {shift}")
+        assert (buf[:start] == 0xAA).all() and (buf[start + n:] == 0xAA).all(), shift

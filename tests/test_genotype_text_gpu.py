@@ -1,13 +1,15 @@
 """bt_gibbs_genotype_text / bt_genotype_text: the genotype text of a launch formatted on the device against the same header code run on the host
 (bt_diag_genotype_text over the records Gibbs.genotypes returns from the same sampler: bytes and words) and against the host layer's stream formatters
-(byte for byte).  Every sampler runs 3 chains x (10 + 40) sweeps."""
+(byte for byte).  Every sampler runs 3 chains x (10 + 40) sweeps.  Then hand-built record strings (_genotype_text.py) through bt_genotype_text against a reference
+made of Python's '%g' alone and against bt_diag_genotype_text: the offsets scan past one workgroup, format_g6 at its edges, StoreSink at every alignment."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import _oracle
-from _genotype_text import assert_launch_text_equals_host, hand_written, make_string
+from _genotype_text import (SCAN_BLOCK, SCAN_CASES, alignment_case, assert_launch_text_equals_host, check_against_reference, check_alignment_inputs, check_g6_inputs,
+                            check_scan_inputs, g6_case, hand_written, make_string, not_covered_case, ploidy_word, scan_case)
 from _genotypes_device import group_of_cluster, min_fraction, mixed_batch, multiallelic_batch
 from test_genotype_text_cpu import check_hand_written
 from test_genotypes_device_gpu import same_results
@@ -135,3 +137,95 @@ def test_errors(gpu_ctx, oracle):
     g.noise_chain_end()
     _check_launch(g, flat, ploidy, S, "after the chain")
     g.close()
+
+
+# ---- hand-built strings: each has a twin in test_genotype_text_cpu.py that checks the input's conditions and the reference without a GPU ----------------------
+GUARD = 64
+
+
+def _device_against_reference_and_host(gpu_ctx, words, ref, what, shift=0):
+    """bt_genotype_text with the text at a 4-aligned address + shift, its capacity the exact size, GUARD bytes of 0xAA on both sides: the text, the index, the
+    sizes and the count are the reference's and bt_diag_genotype_text's, and no byte outside the text changed.  -> (index, address of the text)"""
+    from bayestyper_amd import lib
+
+    h_text, h_index, h_nc = lib.diag_genotype_text(words)
+    d = gpu_ctx.to_device(words)
+    n = ref.text.size
+    assert lib.genotype_text_sizes(gpu_ctx, d.ptr, words.size) == (n, ref.index.size), what
+    d_buf, d_index = gpu_ctx.to_device(np.full(n + 2 * GUARD + 8, 0xAA, np.uint8)), gpu_ctx.to_device(np.full(ref.index.size, 0xAAAAAAAA, np.uint32))
+    start = (-d_buf.ptr) % 4 + GUARD + shift
+    nt, ni, nc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    lib.check(lib.bt_genotype_text(gpu_ctx.h, d.ptr, words.size, d_buf.ptr + start, n, d_index.ptr, ref.index.size, C.byref(nt), C.byref(ni), C.byref(nc)))
+    buf, index = d_buf.download(np.uint8, n + 2 * GUARD + 8), d_index.download(np.uint32, ref.index.size)
+    address = d_buf.ptr + start
+    for b in (d, d_buf, d_index):
+        b.free()
+    assert (nt.value, ni.value) == (n, ref.index.size), what
+    text = buf[start:start + n]
+    check_against_reference(text, index, nc.value, ref, what)
+    assert nc.value == h_nc and np.array_equal(index, h_index) and np.array_equal(text, h_text), what
+    assert (buf[:start] == 0xAA).all() and (buf[start + n:] == 0xAA).all(), (what, "bytes outside the text were written")
+    return index, address
+
+
+@pytest.mark.parametrize("NV,S,multi", SCAN_CASES)
+def test_scan_past_one_workgroup(gpu_ctx, NV, S, multi):
+    """text_scan_block_kernel / text_scan_add_kernel with one to five workgroups, NV = 1, 2, 3 mod 4, NV = 0, S = 0, C != NV; from 2049 variants on with
+    not-covered variants in every scan block"""
+    from bayestyper_amd import lib
+
+    words, ref, variants = scan_case(NV, S, multi)
+    check_scan_inputs(NV, S, multi, ref, variants)
+    index, _ = _device_against_reference_and_host(gpu_ctx, words, ref, f"NV={NV} S={S} multi={multi}")
+    if NV > SCAN_BLOCK:   # (check_against_reference has compared every offset; this names the scan)
+        at = 5 + ref.Cn + 9 * SCAN_BLOCK
+        assert int(index[at]) | (int(index[at + 1]) << 32) == ref.variant_offset(SCAN_BLOCK), "the offset of the second scan block's first variant"
+    assert index[5 + ref.Cn + 8:5 + ref.Cn + 9 * NV:9].tolist() == ref.flags.tolist()
+    d = gpu_ctx.to_device(words)   # the wrapper that sizes its own buffers
+    text, index2, not_covered = lib.genotype_text(gpu_ctx, d.ptr, words.size)
+    d.free()
+    check_against_reference(text, index2, not_covered, ref, "lib.genotype_text")
+
+
+def test_a_malformed_record_past_the_first_scan_block_writes_nothing(gpu_ctx):
+    from bayestyper_amd import lib
+
+    words, ref, _ = scan_case(2049, 1)
+    bad = words.copy()
+    bad[ploidy_word(words, 1500)] = 3
+    d, d_text, d_index = gpu_ctx.to_device(bad), gpu_ctx.to_device(np.full(ref.text.size, 0xAA, np.uint8)), gpu_ctx.to_device(np.full(ref.index.size, 0xAAAAAAAA, np.uint32))
+    nt, ni, nc = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    assert lib.bt_genotype_text(gpu_ctx.h, d.ptr, bad.size, d_text.ptr, ref.text.size, d_index.ptr, ref.index.size, C.byref(nt), C.byref(ni), C.byref(nc)) != 0
+    assert "layout" in lib.bt_last_error().decode()
+    assert (d_text.download(np.uint8, ref.text.size) == 0xAA).all() and (d_index.download(np.uint32, ref.index.size) == 0xAAAAAAAA).all()
+    for b in (d, d_text, d_index):
+        b.free()
+
+
+def test_format_g6_edges_on_the_device(gpu_ctx):
+    """the device's digits against Python's '%g': ties, both notation switches, negative values, doubles that are no widened floats, 5 - floor(log10 v) >= 27"""
+    check_g6_inputs()
+    words, ref = g6_case()
+    assert ref.not_covered == 0
+    _device_against_reference_and_host(gpu_ctx, words, ref, "format_g6 values")
+
+
+def test_not_covered_values_on_the_device(gpu_ctx):
+    """NaN, the infinities, subnormals, 1e6 and what lies below 1e-27, each in a variant of its own: flagged and counted, nothing printed for the value, the
+    variants between them untouched"""
+    words, ref, at = not_covered_case()
+    assert ref.not_covered == len(at) > 10
+    index, _ = _device_against_reference_and_host(gpu_ctx, words, ref, "not covered")
+    assert np.flatnonzero(index[5 + ref.Cn + 8:5 + ref.Cn + 9 * ref.NV:9]).tolist() == at
+
+
+@pytest.mark.parametrize("shift", [0, 1, 2, 3])
+def test_store_alignment(gpu_ctx, shift):
+    """StoreSink's whole-dword and byte stores: every (first byte, one past the last byte) residue among the cells, the variant pieces and the seams between
+    the two write kernels, the text buffer at a 4-aligned address + shift, guard bytes on both sides"""
+    words, ref, variants = alignment_case()
+    for a in range(4):   # (a condition on the lengths: it holds at every address)
+        check_alignment_inputs(ref, variants, a)
+    _, address = _device_against_reference_and_host(gpu_ctx, words, ref, f"shift {shift}", shift)
+    assert address % 4 == shift
+    check_alignment_inputs(ref, variants, address)
